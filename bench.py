@@ -19,7 +19,12 @@ exchange the path has).  torch.distributed (gloo) is the control plane only: it 
 RCCL id to the other ranks, and carries the barrier and the max-over-ranks time.  At N=1 the
 step runs the same all-reduce on a single-rank communicator.
 
-Prints ONE JSON line on rank 0 (see README "Benchmark contract").
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0: the
+headline (`value`, `ms_per_step`) with the stage times and counters the timed steps themselves
+collect.  `--dump-outputs DIR` also writes what the last timed step computed (a fixed, seeded
+sample of the per-read results, and the per-bin counts) as DIR/<name>.npy.  `--full` adds what
+takes work of its own after the timed region: the roofline and per-kernel tables (a read-back of
+every result, the committed PMC tables), the PCIe-inclusive runs and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -352,9 +357,8 @@ def reads_desc(args, what: str) -> str:
     return f"{args.shards[0]} {what} per GPU"
 
 
-def chop_line(args, world, K, value, elapsed, ms, lengths, n_hits, n_segs, cutoff, gen_s,
-              label_lens):
-    """pychopper-style reorientation (01_pychopper.sh).  Dominant kernel: dmx::chop_kernel."""
+def chop_roofline(args, K, ms, lengths, n_hits, n_segs, cutoff, label_lens):
+    """--full: (roofline, valu) of the reorientation step.  Dominant kernel: dmx::chop_kernel."""
     L = lengths.astype(np.float64)
     alg_bytes = (float(np.sum(np.ceil(L / 4) + np.ceil(L / 8) + 12.0)) + 8.0 * len(L)
                  + 16.0 * (n_hits + n_segs))
@@ -366,7 +370,28 @@ def chop_line(args, world, K, value, elapsed, ms, lengths, n_hits, n_segs, cutof
     traffic, traffic_src = pmc_traffic("chop", args.reads)
     vi = pmc_valu_insts("chop", args.reads, "chop_kernel", last_only=True)
     ops_col = vi * 64 / cols if vi else None
-    return {
+    roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
+                "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": round(alg_bytes),
+                "kernel": "dmx::chop_kernel", "avg_launch_ms": round(kern_ms, 3),
+                "note": "VALU-bound bit-vector scan (DESIGN.md §8d)"}
+    valu = {"columns_per_s": cols / (kern_ms / 1e3),
+            "lane_ops_per_column": ops_col,
+            "lane_ops_per_s": cols / (kern_ms / 1e3) * ops_col if ops_col else None,
+            "frac_of_measured_ceiling": (cols / (kern_ms / 1e3) * ops_col / VALU_CEILING
+                                         if ops_col else None),
+            "measured_ceiling_lane_ops_per_s": VALU_CEILING,
+            "measured_ceiling_what": VALU_CEILING_WHAT,
+            "source": "ops/column = SQ_INSTS_VALU x 64 of the PMC'd timed launch "
+                      "(profiles/kernel_pmc.json 'chop:<reads>') / its Myers columns"}
+    return roofline, valu
+
+
+def chop_line(args, world, K, value, elapsed, ms, lengths, n_hits, n_segs, cutoff, gen_s,
+              label_lens):
+    """pychopper-style reorientation (01_pychopper.sh)."""
+    out = {
         "metric": "Mreads/s pychopper-style reorientation (01_pychopper.sh: -m edlib -p, "
                   "M13 SP5/SP27 primers)",
         "value": round(value, 4), "unit": "Mreads/s", "n_gpus": world,
@@ -378,35 +403,24 @@ def chop_line(args, world, K, value, elapsed, ms, lengths, n_hits, n_segs, cutof
                                "M13_seqs_for_pychopper.fa, layout +:SP5,-SP27|-:SP27,-SP5, "
                                "-p, inputs resident in HBM",
                    "cutoff": cutoff, "reads_per_gpu": args.shards, "reads_total": args.total_reads,
-                   "parallelism": f"dp{world}"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": round(alg_bytes),
-                     "kernel": "dmx::chop_kernel", "avg_launch_ms": round(kern_ms, 3),
-                     "note": "VALU-bound bit-vector scan (DESIGN.md §8d)"},
-        "valu": {"columns_per_s": cols / (kern_ms / 1e3),
-                 "lane_ops_per_column": ops_col,
-                 "lane_ops_per_s": cols / (kern_ms / 1e3) * ops_col if ops_col else None,
-                 "frac_of_measured_ceiling": (cols / (kern_ms / 1e3) * ops_col / VALU_CEILING
-                                              if ops_col else None),
-                 "measured_ceiling_lane_ops_per_s": VALU_CEILING,
-                 "measured_ceiling_what": VALU_CEILING_WHAT,
-                 "source": "ops/column = SQ_INSTS_VALU x 64 of the PMC'd timed launch "
-                           "(profiles/kernel_pmc.json 'chop:<reads>') / its Myers columns"},
+                   "parallelism": f"dp{world}"}}
+    if args.full:
+        out["roofline"], out["valu"] = chop_roofline(args, K, ms, lengths, n_hits, n_segs,
+                                                     cutoff, label_lens)
+    out.update({
         "stage_ms_per_step": {k: round(v / K, 3) for k, v in ms.items()},
-        "hits_per_read": round(n_hits / max(1, len(L)), 4),
-        "segments_per_read": round(n_segs / max(1, len(L)), 4),
+        "hits_per_read": round(n_hits / max(1, len(lengths)), 4),
+        "segments_per_read": round(n_segs / max(1, len(lengths)), 4),
         "gen_s": round(gen_s, 1),
-    }
+    })
+    return out
 
 
-def two_round_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, gen_s,
-                   clusters, windows, windows_raw, resolved, traces, filter_tasks):
-    st = stage_split(stage)
+def two_round_roofline(args, K, elapsed, st, lengths, res):
+    """--full: (roofline, per-kernel table, reads entering round 2) of the two-round step, from
+    the stage times of the timed steps, every read's result and the committed PMC tables."""
     pieces = st.get("pieces0", 0.0) > 0 or st.get("pieces1", 0.0) > 0
     stages = KERNEL_STAGES_PIECES if pieces else KERNEL_STAGES_FULL
-    res = ctx.fetch()
     m2 = res["bin1"] >= 0
     n2 = int(m2.sum())
     len2 = (lengths[m2] - res["m1_rstop"][m2]).astype(np.int64)
@@ -429,7 +443,6 @@ def two_round_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, 
         traffic, traffic_src = pmc_traffic(args.workload, args.reads)
     vi = pmc_valu_insts(args.workload, args.reads, dom_kernel)
     dom_rate = vi * 64 / ((st[f"{dom}0"] + st[f"{dom}1"]) / K / 1e3) if vi else None
-    A0, A1 = ctx.panel_sizes
     read_stream = None
     if pieces:   # the piece screen reads every base of every view (the old filter's role)
         pm = (st["pieces0"] + st["pieces1"]) / (2 * K)
@@ -447,7 +460,42 @@ def two_round_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, 
             "pscan_traffic_bytes_per_launch": ps_traffic,
             "what": "the same §8(d) bytes over the piece screen stage's live time (HIP events "
                     "from the round start to the filter tasks; its memsets included)"}
-    return {
+    roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                "traffic": traffic, "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": round(alg_bytes),
+                "algorithmic_bytes_per_launch_r1_r2": [round(sb0), round(sb1)],
+                "algorithmic_bytes_rule": "SURVEY.md §8(d) B(read) = ceil(L/4) + 8 + "
+                                          "ceil(L/64) + 24 over the launch's views, mean "
+                                          "of the round-1 and round-2 launches",
+                "traffic_over_algorithmic": (round(traffic / alg_bytes, 3)
+                                             if traffic else None),
+                "per_step": {"bytes": round(step_bytes), "ms": round(step_ms, 3),
+                             "achieved_gbs": round(step_bytes / (step_ms / 1e3) / 1e9, 3),
+                             "frac": round(step_bytes / (step_ms / 1e3) / 1e9
+                                           / HBM_PEAK_GBS, 6),
+                             "what": "§8(d) bytes of every read once per step (round 2 "
+                                     "reuses the resident read) / ms_per_step"},
+                "kernel": "dmx::" + dom_kernel, "avg_launch_ms": round(dom_ms, 3),
+                "share_of_step": round(2 * dom_ms / step_ms, 4),
+                "note": "the dominant kernel (the single-kernel stage with the largest share "
+                        "of the step, see 'kernels'); integer/bit work, VALU- or "
+                        "latency-bound by construction (DESIGN.md §5): roofline.valu gives "
+                        "its issue rate against the VALU peak at the clock it ran at",
+                "valu": valu_roof(dom_rate,
+                                  pmc_clock(args.workload, args.reads, dom_kernel),
+                                  f"dmx::{dom_kernel}, both rounds"),
+                "read_stream": read_stream}
+    return (roofline, kernel_table(args.workload, args.reads, st, K, elapsed / K * 1e3, stages),
+            n2)
+
+
+def two_round_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, gen_s,
+                   clusters, windows, windows_raw, resolved, traces, filter_tasks, res):
+    """The result line of the two-round step; `res` (every read's result) only with --full."""
+    st = stage_split(stage)
+    A0, A1 = ctx.panel_sizes
+    out = {
         "metric": METRIC, "value": round(value, 4), "unit": "Mreads/s", "n_gpus": world,
         "steps": K, "warmup": args.warmup, "ms_per_step": round(elapsed / K * 1e3, 3),
         "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "u64",
@@ -457,34 +505,11 @@ def two_round_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, 
                                "inputs resident in HBM",
                    "panel": f"{A0}x{A1}", "reads_per_gpu": args.shards,
                    "reads_total": args.total_reads,
-                   "parallelism": f"dp{world}"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": round(alg_bytes),
-                     "algorithmic_bytes_per_launch_r1_r2": [round(sb0), round(sb1)],
-                     "algorithmic_bytes_rule": "SURVEY.md §8(d) B(read) = ceil(L/4) + 8 + "
-                                               "ceil(L/64) + 24 over the launch's views, mean "
-                                               "of the round-1 and round-2 launches",
-                     "traffic_over_algorithmic": (round(traffic / alg_bytes, 3)
-                                                  if traffic else None),
-                     "per_step": {"bytes": round(step_bytes), "ms": round(step_ms, 3),
-                                  "achieved_gbs": round(step_bytes / (step_ms / 1e3) / 1e9, 3),
-                                  "frac": round(step_bytes / (step_ms / 1e3) / 1e9
-                                                / HBM_PEAK_GBS, 6),
-                                  "what": "§8(d) bytes of every read once per step (round 2 "
-                                          "reuses the resident read) / ms_per_step"},
-                     "kernel": "dmx::" + dom_kernel, "avg_launch_ms": round(dom_ms, 3),
-                     "share_of_step": round(2 * dom_ms / step_ms, 4),
-                     "note": "the dominant kernel (the single-kernel stage with the largest share "
-                             "of the step, see 'kernels'); integer/bit work, VALU- or "
-                             "latency-bound by construction (DESIGN.md §5): roofline.valu gives "
-                             "its issue rate against the VALU peak at the clock it ran at",
-                     "valu": valu_roof(dom_rate,
-                                       pmc_clock(args.workload, args.reads, dom_kernel),
-                                       f"dmx::{dom_kernel}, both rounds"),
-                     "read_stream": read_stream},
-        "kernels": kernel_table(args.workload, args.reads, st, K, elapsed / K * 1e3, stages),
+                   "parallelism": f"dp{world}"}}
+    if args.full:
+        out["roofline"], out["kernels"], out["reads_round2_per_gpu"] = two_round_roofline(
+            args, K, elapsed, st, lengths, res)
+    out.update({
         "stage_ms_per_step": {k: round(v / K, 3) for k, v in st.items()},
         "clusters_per_step": (clusters / K).tolist(),
         "filter_tasks_per_step": (filter_tasks / K).tolist(),
@@ -492,19 +517,17 @@ def two_round_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, 
         "filter_windows_per_step": (windows / K).tolist(),
         "resolved_clusters_per_step": (resolved / K).tolist(),
         "tracebacks_per_step": (traces / K).tolist(),
-        "reads_round2_per_gpu": n2,
         "unknown_round1": int(counts[0]) if counts is not None else None,
         "gen_s": round(gen_s, 1),
-    }
+    })
+    return out
 
 
-def linked_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, gen_s):
-    """Config 5: linked primers.  Dominant kernel: round 1's full scan (every front primer over
-    every consensus: one lane per (read, pair))."""
-    res = ctx.fetch()
+def linked_roofline(args, K, stage, lengths, res):
+    """--full: (roofline, trimmed fraction) of config 5.  Dominant kernel: round 1's full scan
+    (every front primer over every consensus: one lane per (read, pair))."""
     trimmed = int((res["bin1"] >= 0).sum())
     scan_ms = stage["scan0"] / K
-    A0, _ = ctx.panel_sizes
     L = lengths.astype(np.float64)
     alg_bytes = survey_bytes(lengths)   # SURVEY.md §8(d) B(read) over the consensuses
     layout_bytes = float(np.sum(np.ceil(L / 4) + np.ceil(L / 8) + 12.0))
@@ -512,7 +535,27 @@ def linked_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, gen
     traffic, traffic_src = pmc_traffic("c5", args.reads)
     vi = pmc_valu_insts("c5", args.reads, "scan_kernel<true>", first_only=True)
     rate = vi * 64 / (scan_ms / 1e3) if vi else None
-    return {
+    roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
+                "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": round(alg_bytes),
+                "algorithmic_bytes_rule": "SURVEY.md §8(d) B(read) = ceil(L/4) + 8 + "
+                                          "ceil(L/64) + 24 over the launch's reads",
+                "layout_bytes_per_launch": round(layout_bytes),
+                "traffic_over_algorithmic": (round(traffic / alg_bytes, 3)
+                                             if traffic else None),
+                "kernel": "dmx::scan_kernel<true>", "avg_launch_ms": round(scan_ms, 3),
+                "note": "VALU-bound bit-vector scan (DESIGN.md §5); the round-1 launch "
+                        "(every front primer over every consensus)",
+                "valu": valu_roof(rate, pmc_clock("c5", args.reads, "scan_kernel<true>", 0),
+                                  "dmx::scan_kernel<true>, round 1 (fronts)")}
+    return roofline, round(trimmed / max(1, len(lengths)), 4)
+
+
+def linked_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, gen_s, res):
+    """Config 5: linked primers; `res` (every read's result) only with --full."""
+    A0, _ = ctx.panel_sizes
+    out = {
         "metric": "Mreads/s linked-primer trimming (config 5, cutadapt -g F...R per pair)",
         "value": round(value, 4), "unit": "Mreads/s", "n_gpus": world,
         "steps": K, "warmup": args.warmup, "ms_per_step": round(elapsed / K * 1e3, 3),
@@ -522,25 +565,67 @@ def linked_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, gen
                                "§8d config 5), linked COI_primers.fa pairs, -e 0.1, no --rc, "
                                "inputs resident in HBM",
                    "pairs": A0, "reads_per_gpu": args.shards, "reads_total": args.total_reads,
-                   "parallelism": f"dp{world}"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": round(alg_bytes),
-                     "algorithmic_bytes_rule": "SURVEY.md §8(d) B(read) = ceil(L/4) + 8 + "
-                                               "ceil(L/64) + 24 over the launch's reads",
-                     "layout_bytes_per_launch": round(layout_bytes),
-                     "traffic_over_algorithmic": (round(traffic / alg_bytes, 3)
-                                                  if traffic else None),
-                     "kernel": "dmx::scan_kernel<true>", "avg_launch_ms": round(scan_ms, 3),
-                     "note": "VALU-bound bit-vector scan (DESIGN.md §5); the round-1 launch "
-                             "(every front primer over every consensus)",
-                     "valu": valu_roof(rate, pmc_clock("c5", args.reads, "scan_kernel<true>", 0),
-                                       "dmx::scan_kernel<true>, round 1 (fronts)")},
+                   "parallelism": f"dp{world}"}}
+    if args.full:
+        out["roofline"], out["trimmed_fraction"] = linked_roofline(args, K, stage, lengths, res)
+    out.update({
         "stage_ms_per_step": {k: round(v / K, 3) for k, v in stage.items()},
-        "trimmed_fraction": round(trimmed / max(1, len(lengths)), 4),
         "gen_s": round(gen_s, 1),
-    }
+    })
+    return out
+
+
+# --dump-outputs: the per-read results of a fixed, seeded sample of this many reads (17 fields,
+# 84 B per read as float32 / float64), and this many leading hit / segment records (32 B each)
+DUMP_READS = 400_000
+DUMP_RECORDS = 500_000
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample(n: int) -> np.ndarray:
+    """The reads --dump-outputs writes: all n, or a sorted sample drawn with a fixed seed."""
+    if n <= DUMP_READS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(20241019).choice(n, DUMP_READS, replace=False))
+
+
+def dump_outputs(dirname: str, rank: int, world: int, arrays: dict):
+    """Write each array as DIR/<name>.npy (DIR/rank<r>_<name>.npy with several ranks): integers of
+    up to 16 bits as float32, wider ones as float64, so every value is held exactly."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes")
+        np.save(os.path.join(dirname, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), a)
+
+
+def dump_results(dirname: str, rank: int, world: int, res: np.ndarray, counts):
+    """The two-round / linked step's outputs: every field of the sampled reads' dmx_result
+    records (ctx.fetch()) and the all-reduced per-bin counts."""
+    idx = dump_sample(len(res))
+    arrays = {"sample_index": idx, "counts": counts}
+    for f in res.dtype.names:
+        if f != "pad":
+            arrays[f] = res[f][idx]
+    dump_outputs(dirname, rank, world, arrays)
+
+
+def dump_chop(dirname: str, rank: int, world: int, ctx, tot):
+    """The reorientation step's outputs: the totals dmx_chop_exec returns, the sampled reads'
+    segment and hit counts, and the leading segment and hit records (read order)."""
+    nseg, nhit, sg, ht = ctx.chop_fetch(segs=True, hits=True)
+    idx = dump_sample(len(nseg))
+    arrays = {"sample_index": idx, "totals": np.array(tot, dtype=np.uint64),
+              "segments_per_read": nseg[idx], "hits_per_read": nhit[idx]}
+    for f in sg.dtype.names:
+        arrays["seg_" + f] = sg[f][:DUMP_RECORDS]
+    for f in ht.dtype.names:
+        arrays["hit_" + f] = ht[f][:DUMP_RECORDS]
+    dump_outputs(dirname, rank, world, arrays)
 
 
 def main():
@@ -562,13 +647,24 @@ def main():
                     help="strong scaling: this many reads in total, split over the ranks in "
                          "contiguous ranges balanced on the sum of read lengths (BASELINE "
                          "configs[2]: --reads-total 10000000 on 8 GPUs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as "
+                         "DIR/<name>.npy (float32 / float64; a fixed, seeded sample of the "
+                         "per-read results, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the roofline and per-kernel tables, the "
+                         "PCIe-inclusive runs and the CPU baseline (a plain run prints the "
+                         "headline with the stage times and counters of the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="threads of the CPU baseline; default one per physical host core "
                          "available to this process")
     ap.add_argument("--no-pcie", action="store_true",
-                    help="skip the PCIe-inclusive dmx_run after the timed region")
+                    help="with --full: skip the PCIe-inclusive dmx_run after the timed region")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus is not None and args.gpus > 1:
@@ -642,7 +738,7 @@ def main():
         ctx.set_mode(lib.MODE_TWO_ROUND)
     ctx.load(packed)
     # kept for the PCIe-inclusive run after the timed region (dmx_run from host memory)
-    host_batch = packed if not linked else None
+    host_batch = packed if args.full and not linked and not args.no_pcie else None
     del packed
 
     def allreduce_counts():
@@ -708,14 +804,20 @@ def main():
 
     K = args.steps
     value = args.total_reads * K / elapsed / 1e6
+    # every read's result of the last timed step: read back only where something uses it
+    res = ctx.fetch() if args.full or args.dump_outputs else None
+    if args.dump_outputs:
+        dump_results(args.dump_outputs, rank, world, res, counts)
     if linked:
-        out = linked_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, gen_s)
+        out = linked_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, gen_s,
+                          res)
     else:
         out = two_round_line(args, world, K, value, elapsed, stage, lengths, ctx, counts, gen_s,
-                             clusters, windows, windows_raw, resolved, traces, filter_tasks)
+                             clusters, windows, windows_raw, resolved, traces, filter_tasks, res)
+    del res
     out["step_wall_ms"] = [round(x, 3) for x in step_wall]   # this rank's, for outliers
     pcie = None
-    if host_batch is not None and not args.no_pcie:
+    if host_batch is not None:
         # the boundary's host-memory path: upload, both rounds, download of every result, with
         # copies overlapped with kernels (dmx_run's double-buffered chunks); not the headline.
         # Inputs as a resident host pipeline holds them: the no-match mask as its exceptions
@@ -772,7 +874,7 @@ def main():
 
     if pcie is not None:
         out["pcie_inclusive"] = pcie
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cores, how = host_cores()
         if args.cpu_threads:
             cores, how = args.cpu_threads, f"--cpu-threads {args.cpu_threads}; detected: {how}"
@@ -834,9 +936,11 @@ def chop_main(args, ctx, packed, tune, lengths, gen_s, world, rank, dist, on_gpu
         elapsed = float(tt.item())
     K = args.steps
     value = args.total_reads * K / elapsed / 1e6
+    if args.dump_outputs:
+        dump_chop(args.dump_outputs, rank, world, ctx, tot)
     out = chop_line(args, world, K, value, elapsed, ms, lengths, tot[0], tot[1], cutoff, gen_s,
                     [len(p[1]) for p in primers for _ in (0, 1)])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cores, how = host_cores()
         if args.cpu_threads:
             cores, how = args.cpu_threads, f"--cpu-threads {args.cpu_threads}; detected: {how}"

@@ -103,3 +103,91 @@ def test_roofline_bytes_follow_survey_8d():
     assert 340 < per < 365
     # the layout figure (1-bit mask, 40-B windows) is a different, larger number
     assert bench.filter_layout_bytes(d["lengths"], 0) > bench.survey_bytes(d["lengths"])
+
+
+def test_dump_sample_is_fixed_and_dump_outputs_hold_values_exactly(tmp_path):
+    """--dump-outputs: the sampled reads are the same from run to run, and the arrays are written
+    as float32 (up to 16-bit integers) or float64 (wider ones), so every value is exact."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_sample(1000).tolist() == list(range(1000))
+    a, b = bench.dump_sample(10_000_000), bench.dump_sample(10_000_000)
+    assert len(a) == bench.DUMP_READS and a.tolist() == b.tolist()
+    assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < 10_000_000
+    # the per-read sample (17 result fields, the read indices) stays under the 64 MB limit
+    assert bench.DUMP_READS * (84 + 8) + 8 * 627 <= bench.DUMP_MAX_BYTES
+    assert bench.DUMP_READS * 24 + 2 * bench.DUMP_RECORDS * 32 <= bench.DUMP_MAX_BYTES
+    arrays = {"small": np.array([-1, 32767], dtype=np.int16),
+              "wide": np.array([2**31 - 1, -5], dtype=np.int32),
+              "counts": np.array([2**40 + 1], dtype=np.uint64)}
+    bench.dump_outputs(str(tmp_path / "d"), 0, 1, arrays)
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in arrays}
+    assert got["small"].dtype == np.float32 and got["wide"].dtype == np.float64
+    assert got["counts"].dtype == np.float64
+    for n, a in arrays.items():
+        assert got[n].astype(a.dtype).tolist() == a.tolist()
+    bench.dump_outputs(str(tmp_path / "d"), 1, 2, {"small": arrays["small"]})
+    assert (tmp_path / "d" / "rank1_small.npy").exists()
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), 0, 1,
+                           {"x": np.zeros(bench.DUMP_MAX_BYTES // 8 + 1, dtype=np.int64)})
+
+
+def test_steps_must_be_positive():
+    r = _bench(["--gpus", "1", "--steps", "0"], {})
+    assert r.returncode != 0 and "--steps" in r.stderr and r.stdout == ""
+
+
+FULL_ONLY = ("roofline", "kernels", "reads_round2_per_gpu", "pcie_inclusive", "cpu_baseline")
+HEADLINE = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run prints the headline without the --full legs; --steps sets the timed steps;
+    --dump-outputs writes the results a caller of the timed path receives (here every read's:
+    the batch is smaller than the sample), equal to a fresh run of the same inputs."""
+    import json
+    from dmx import lib
+    n = 3000
+    r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "c1", "--reads",
+                str(n), "--dump-outputs", str(tmp_path / "o")], {})
+    assert r.returncode == 0, r.stderr
+    lines = r.stdout.strip().split("\n")
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert all(k in d for k in HEADLINE) and not any(k in d for k in FULL_ONLY)
+    assert d["steps"] == 2 and len(d["step_wall_ms"]) == 2 and d["ms_per_step"] > 0
+    assert abs(d["value"] - n / d["ms_per_step"] / 1e3) <= 1e-3 * d["value"] + 1e-4
+    s = synth.generate("c1", n=n)
+    with lib.Context(0) as c:
+        c.set_panel(0, s["sp5"], lib.DMX_FRONT | lib.DMX_RC, 0.1)
+        c.set_panel(1, s["sp27"], lib.DMX_BACK | lib.DMX_RC, 0.1)
+        c.set_mode(lib.MODE_TWO_ROUND)
+        want = c.run(lib.pack(s["blob"], s["offsets"], s["lengths"]))
+        counts = c.counts()
+    out = tmp_path / "o"
+    assert np.load(out / "sample_index.npy").tolist() == list(range(n))
+    total = 0
+    for f in want.dtype.names:
+        if f == "pad":
+            continue
+        got = np.load(out / f"{f}.npy")
+        assert got.dtype == (np.float32 if want.dtype[f].itemsize <= 2 else np.float64)
+        assert got.tolist() == want[f].astype(np.float64).tolist(), f
+        total += got.nbytes
+    assert np.load(out / "counts.npy").tolist() == counts.astype(np.float64).tolist()
+    assert total <= 64 << 20 and (want["bin2"] >= 0).any()
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_other_measurements():
+    """--full adds the roofline, the per-kernel table and the PCIe-inclusive runs (the CPU
+    baseline, a 12 s sample, is switched off here to keep the test short)."""
+    import json
+    r = _bench(["--gpus", "1", "--steps", "1", "--warmup", "1", "--workload", "c1", "--reads",
+                "3000", "--full", "--no-cpu-baseline"], {})
+    assert r.returncode == 0, r.stderr
+    d = json.loads(r.stdout.strip())
+    assert all(k in d for k in HEADLINE + FULL_ONLY[:-1]) and "cpu_baseline" not in d
+    assert d["roofline"]["achieved"] > 0 and d["pcie_inclusive"]["value"] > 0

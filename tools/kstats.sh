@@ -6,5 +6,5 @@ out=$1; shift
 mkdir -p "$out"
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o run -- \
-  python3 bench.py --no-cpu-baseline --no-pcie --steps 3 --warmup 1 "$@" > "$out/bench.json" \
+  python3 bench.py --full --no-cpu-baseline --no-pcie --steps 3 --warmup 1 "$@" > "$out/bench.json" \
   2> "$out/bench.err"

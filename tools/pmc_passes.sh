@@ -17,5 +17,5 @@ i=0
 for p in "${passes[@]}"; do
   i=$((i + 1))
   timeout -k 10 300 rocprofv3 --pmc $p --output-format csv -d "$out/p$i" -o run -- \
-    python3 bench.py --no-cpu-baseline "$@" > "$out/p$i.log" 2>&1
+    python3 bench.py --full --no-cpu-baseline "$@" > "$out/p$i.log" 2>&1
 done

@@ -26,6 +26,6 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/
   > "$out/stats_c4.log" 2>&1
 cp "$out/stats_c4/run_kernel_stats.csv" "$out/kernel_stats_c4_6.25M_$tag.csv"
 export DMX_KERNEL_PMC="$out/kernel_pmc.json" DMX_FILTER_TRAFFIC="$out/filter_pmc_traffic.json"
-timeout -k 10 400 python3 bench.py --workload c4 --reads 6250000 > "$out/bench_c4.json" \
+timeout -k 10 400 python3 bench.py --full --workload c4 --reads 6250000 > "$out/bench_c4.json" \
   2> "$out/bench_c4.err"
-timeout -k 10 400 python3 bench.py > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 400 python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err"

@@ -32,8 +32,8 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/
   -- python3 bench.py --no-cpu-baseline --no-pcie > "$out/stats.log" 2>&1
 cp "$out/stats/run_kernel_stats.csv" "$out/kernel_stats_c2x24_10M.csv"
 export DMX_KERNEL_PMC="$out/kernel_pmc.json" DMX_FILTER_TRAFFIC="$out/filter_pmc_traffic.json"
-timeout -k 10 300 python3 bench.py --workload c4 --reads 6250000 --no-cpu-baseline \
+timeout -k 10 300 python3 bench.py --full --workload c4 --reads 6250000 --no-cpu-baseline \
   > "$out/bench_c4.json" 2> "$out/bench_c4.err"
-timeout -k 10 300 python3 bench.py --workload c5 --no-cpu-baseline > "$out/bench_c5.json" \
+timeout -k 10 300 python3 bench.py --full --workload c5 --no-cpu-baseline > "$out/bench_c5.json" \
   2> "$out/bench_c5.err"
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"

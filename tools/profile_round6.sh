@@ -25,8 +25,8 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/
   > "$out/stats_c4.log" 2>&1
 cp "$out/stats_c4/run_kernel_stats.csv" "$out/kernel_stats_c4_6.25M_$tag.csv"
 export DMX_KERNEL_PMC="$out/kernel_pmc.json"
-timeout -k 10 400 python3 bench.py --workload c4 --reads 6250000 > "$out/bench_c4.json" \
+timeout -k 10 400 python3 bench.py --full --workload c4 --reads 6250000 > "$out/bench_c4.json" \
   2> "$out/bench_c4.err"
-DMX_NO_PIECES=1 timeout -k 10 400 python3 bench.py --no-cpu-baseline --no-pcie \
+DMX_NO_PIECES=1 timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --no-pcie \
   > "$out/bench_nopieces.json" 2> "$out/bench_nopieces.err"
-timeout -k 10 400 python3 bench.py > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 400 python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err"

@@ -9,6 +9,6 @@ for v in "$@"; do
   name=${v%%:*}
   lib=nanopore-barcoding-orc_amd/dmx/libdmx.so
   [ "$name" != default ] && lib=nanopore-barcoding-orc_amd/dmx/libdmx_$name.so
-  DMX_LIBDMX=$PWD/$lib timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-pcie --steps 4 \
+  DMX_LIBDMX=$PWD/$lib timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-pcie --steps 4 \
     --warmup 2 > "$out/bench_$name.json" 2> "$out/bench_$name.err"
 done
