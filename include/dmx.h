@@ -298,6 +298,44 @@ int dmx_chop_fetch(dmx_ctx* ctx, uint32_t* n_seg, uint32_t* n_hit, dmx_chop_seg*
  * global hit lists (more primer hits than the 512-entry LDS list holds). */
 int dmx_chop_stats(dmx_ctx* ctx, float* ms, int n_ms);
 
+/* ---- Pairwise read distance: the amplicon-sorting stage's similarity pass --------------------
+ * Replaces: the edlib.align(A1, A2, task='distance', mode=...) calls of
+ * scripts/auxiliary_code/amplicon_sorter.py: distance() (:225-235) as similarity() (:777-808)
+ * calls it for every pair process_list() makes (mode 'NW', repeated on the reverse complement
+ * when the forward identity is below 0.5), and the 'HW' comparisons of finetune() (:840-852).
+ * edlib is not vendored; edit distance has one right answer, so parity is pinned by a
+ * full-matrix DP (dmx_pairdist_host).  Clustering and consensus building are not replaced.
+ * Runs on the batch made resident by dmx_load.  Symbols: A, C, G, T and the no-match mask as a
+ * fifth symbol (edlib compares bytes, so N equals N and nothing else).
+ * DMX_PD_NW: Levenshtein distance of the two whole reads.  DMX_PD_HW: the least edit distance
+ * between the query and any substring of the target, the empty one included (edlib's infix
+ * mode).  Pair flag DMX_PD_RC: the target is taken reverse-complemented (read backwards in
+ * place, masked positions stay masked).  Reads of 1..DMX_PD_MAX_LEN nt (DMX_E_UNSUPPORTED
+ * otherwise); a pair index >= the batch's reads, an unknown flag or mode is DMX_E_INVALID.
+ * Everything is checked on the host before anything is launched.  Pairs may repeat and come in
+ * any order.  Lists above DMX_PD_CHUNK pairs (environment, default 2^20) run as several
+ * launches with bounded device memory (same results). */
+#define DMX_PD_NW 0
+#define DMX_PD_HW 1
+#define DMX_PD_RC 0x1            /* pair flag: target reverse-complemented */
+#define DMX_PD_MAX_LEN 16384
+/* Edit distance of read q[i] (query) against read t[i] (target) of the resident batch.
+ * flags, caps may be NULL (0 / no cap).  out[i] = min(d, caps[i] + 1).  Synchronous. */
+int dmx_pairdist(dmx_ctx* ctx, int mode, const uint32_t* q, const uint32_t* t,
+                 const uint8_t* flags, const uint32_t* caps, size_t n_pairs, uint32_t* out);
+/* Host only (no GPU; tests, CPU baseline): the same contract on a dmx_pack layout, by a plain
+ * full-matrix DP (a different algorithm from the kernel's on purpose).  Errors: the message is
+ * dmx_last_error(NULL). */
+int dmx_pairdist_host(int mode, const uint32_t* seq2b, const uint32_t* nmask,
+                      const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
+                      const uint32_t* q, const uint32_t* t, const uint8_t* flags,
+                      const uint32_t* caps, size_t n_pairs, uint32_t* out, int n_threads);
+float dmx_pairdist_ms(dmx_ctx* ctx);  /* device time of the last dmx_pairdist (HIP events) */
+/* Host only: the lane-group sizes G the kernel cuts a wave into (first `cap` written, ascending;
+ * returns their number).  A query of w = ceil(len / 64) words runs in the smallest G >= w, one
+ * word per lane; above 64 words it runs in stripes of 64 G rows with G = 64. */
+int dmx_pairdist_group_sizes(int* out, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -340,6 +340,7 @@ void dmx_close(dmx_ctx* c) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     chop_release(c);
+    pd_release(c);
     comm_release(c);
     void* bufs[] = {c->d_seq_alloc, c->d_nmask_alloc,     c->d_offs,     c->d_lens,      c->d_res,
                     c->d_winner[0], c->d_winner[1], c->d_origin[0], c->d_origin[1], c->d_lb[0], c->d_lb[1], c->d_cl[0],

@@ -13,6 +13,7 @@ struct ncclComm;   // RCCL (rccl/rccl.h: ncclComm_t = ncclComm*)
 namespace dmx {
 
 struct ChopState;   // read reorientation (dmx_chop.hip)
+struct PdState;     // pairwise read distance (dmx_pairdist.hip)
 
 // Reach of a panel's gathers around a view, in nt (panel_reach below).
 struct PanelReach {
@@ -140,6 +141,7 @@ struct Ctx {
                               // [15+r] after the piece screen (its filter tasks follow)
     bool executed = false;
     ChopState* chop = nullptr;   // dmx_chop_* state, created by dmx_chop_set
+    PdState* pd = nullptr;       // dmx_pairdist buffers, created by its first call
 
     // RCCL communicator for the per-bin count exchange (dmx_comm.cpp)
     ncclComm* comm = nullptr;
@@ -149,6 +151,7 @@ struct Ctx {
 };
 
 void chop_release(Ctx* c);
+void pd_release(Ctx* c);
 void comm_release(Ctx* c);
 int reset_counts(Ctx* c);      // size d_counts for the current panels/mode and zero it (sync)
 // The last error of a call that has no context to keep it in (dmx_comm_unique_id's RCCL load),

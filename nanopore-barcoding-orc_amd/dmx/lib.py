@@ -40,11 +40,14 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_chop_stats", "dmx_comm_unique_id", "dmx_comm_init_rank", "dmx_comm_init_all",
            "dmx_comm_size", "dmx_allreduce_counts", "dmx_debug_fetch", "dmx_run_sparse",
            "dmx_mask_exceptions", "dmx_host_register", "dmx_host_unregister", "dmx_panel_reach",
-           "dmx_debug_bounds_selftest", "dmx_panel_pieces"]
+           "dmx_debug_bounds_selftest", "dmx_panel_pieces", "dmx_pairdist", "dmx_pairdist_host",
+           "dmx_pairdist_group_sizes"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
 LOC_IGNORE_CASE, LOC_ONLY_POSITIVE = 0x1, 0x2
+# include/dmx.h dmx_pairdist: modes, the pair flag, the longest read
+PD_NW, PD_HW, PD_RC, PD_MAX_LEN = 0, 1, 0x1, 16384
 HIT_DTYPE = np.dtype([("seq", "<u8"), ("pattern", "<i4"), ("strand", "<i4"), ("start", "<i4"),
                       ("end", "<i4")])
 assert HIT_DTYPE.itemsize == 24
@@ -138,6 +141,13 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "dmx_panel_pieces"):
         L.dmx_panel_pieces.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_int),
                                        c_int, ctypes.c_double, c_int, c_int, P, c_int, P, c_int]
+    if hasattr(L, "dmx_pairdist"):
+        L.dmx_pairdist.argtypes = [P, c_int, P, P, P, P, c_size, P]
+        L.dmx_pairdist_host.argtypes = [c_int, P, P, c_u64p, P, c_size, P, P, P, P, c_size, P,
+                                        c_int]
+        L.dmx_pairdist_ms.argtypes = [P]
+        L.dmx_pairdist_ms.restype = ctypes.c_float
+        L.dmx_pairdist_group_sizes.argtypes = [ctypes.POINTER(c_int), c_int]
     # DMX_ALLOW_ABI=1: load an older in-tree build for a regression A/B (tools/replay_sweep.py)
     if L.dmx_abi_version() != ABI_VERSION and os.environ.get("DMX_ALLOW_ABI") != "1":
         raise DmxError("libdmx ABI mismatch")
@@ -367,6 +377,23 @@ class Context:
         nbig = self._check(self._L.dmx_chop_stats(self._h, ms, 2), "dmx_chop_stats")
         return {"chop": float(ms[0]), "order": float(ms[1]), "big_blocks": int(nbig)}
 
+    # ---- pairwise read distance (include/dmx.h dmx_pairdist) ---------------------
+    def pairdist(self, q, t, mode: int = PD_NW, flags=None, caps=None) -> np.ndarray:
+        """Edit distance of resident read q[i] (query) against t[i] (target): PD_NW whole reads,
+        PD_HW query against any substring of the target.  flags: PD_RC per pair (target
+        reverse-complemented); caps: out[i] = min(d, caps[i] + 1).  Returns uint32."""
+        qa, ta, fa, ca = _pair_arrays(q, t, flags, caps)
+        out = np.zeros(len(qa), dtype=np.uint32)
+        self._check(self._L.dmx_pairdist(self._h, int(mode), qa.ctypes.data, ta.ctypes.data,
+                                         fa.ctypes.data if fa is not None else None,
+                                         ca.ctypes.data if ca is not None else None, len(qa),
+                                         out.ctypes.data), "dmx_pairdist")
+        return out
+
+    def pairdist_ms(self) -> float:
+        """Device time (ms) of the last pairdist call."""
+        return float(self._L.dmx_pairdist_ms(self._h))
+
     def n_counts(self) -> int:
         a1 = 0 if self.mode == MODE_SINGLE else self.panel_sizes[1]
         return (self.panel_sizes[0] + 1) * (a1 + 1) + 2
@@ -421,6 +448,47 @@ class Context:
                 "traces": cl[6:8].tolist(), "windows_raw": cl[8:10].tolist(),
                 "tasks": cl[10:12].tolist(), "filter_tasks": cl[12:14].tolist(),
                 "flags": fl.value}
+
+
+def _pair_arrays(q, t, flags, caps):
+    qa = np.ascontiguousarray(q, dtype=np.uint32)
+    ta = np.ascontiguousarray(t, dtype=np.uint32)
+    if qa.ndim != 1 or qa.shape != ta.shape:
+        raise DmxError("pairdist: q and t must be one-dimensional and of equal length")
+    fa = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+    ca = None if caps is None else np.ascontiguousarray(caps, dtype=np.uint32)
+    for a in (fa, ca):
+        if a is not None and a.shape != qa.shape:
+            raise DmxError("pairdist: flags and caps must have one entry per pair")
+    return qa, ta, fa, ca
+
+
+def pairdist_host(p: "Packed", q, t, mode: int = PD_NW, flags=None, caps=None,
+                  n_threads: int = 1) -> np.ndarray:
+    """dmx_pairdist's contract on the host, by a plain full-matrix DP (no GPU): the checker of
+    the kernel and the CPU baseline of tools/bench_pairdist.py."""
+    L = load()
+    qa, ta, fa, ca = _pair_arrays(q, t, flags, caps)
+    out = np.zeros(len(qa), dtype=np.uint32)
+    rc = L.dmx_pairdist_host(int(mode), p.seq2b.ctypes.data, p.nmask.ctypes.data,
+                             p.offsets.ctypes.data, p.lengths.ctypes.data, p.n_reads,
+                             qa.ctypes.data, ta.ctypes.data,
+                             fa.ctypes.data if fa is not None else None,
+                             ca.ctypes.data if ca is not None else None, len(qa),
+                             out.ctypes.data, int(n_threads))
+    if rc < 0:
+        msg = L.dmx_last_error(None)
+        raise DmxError(f"dmx_pairdist_host failed ({rc}): {msg.decode() if msg else ''}")
+    return out
+
+
+def pairdist_group_sizes() -> list:
+    """The lane-group sizes dmx_pairdist's kernel cuts a wave into (dmx_pairdist_group_sizes)."""
+    L = load()
+    n = L.dmx_pairdist_group_sizes(None, 0)
+    out = (ctypes.c_int * n)()
+    L.dmx_pairdist_group_sizes(out, n)
+    return [int(x) for x in out]
 
 
 def panel_reach(seqs, flags: int, max_errors: float = 0.1, min_overlap: int = 3,

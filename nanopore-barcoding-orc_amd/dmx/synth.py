@@ -181,3 +181,38 @@ def shard_bounds(config: str, n_total: int, world: int, seed: int | None = None)
 def to_strings(d) -> list[str]:
     b = d["blob"]
     return [b[o:o + l].tobytes().decode("ascii") for o, l in zip(d["offsets"], d["lengths"])]
+
+
+def amplicon_bin(n: int, families: int = 3, length=(1150, 1250), mutate=(0.03, 0.12),
+                 rc_frac: float = 0.1, n_reads_with_n: int = 0, seed: int = 7) -> list[str]:
+    """One demultiplexed bin for the similarity pass (dmx.sorter): `n` reads drawn from
+    `families` random amplicons of length[0]..length[1] nt, each read a copy of its family with a
+    fraction mutate[0]..mutate[1] of substitutions, insertions and deletions, a fraction rc_frac
+    of the reads reverse-complemented, and the first n_reads_with_n reads carrying a few N."""
+    rng = random.Random(seed)
+    fams = ["".join(rng.choice("ACGT") for _ in range(rng.randint(*length)))
+            for _ in range(families)]
+    comp = str.maketrans("ACGT", "TGCA")
+    reads = []
+    for i in range(n):
+        src = fams[rng.randrange(families)]
+        rate = rng.uniform(*mutate)
+        out = []
+        for ch in src:
+            r = rng.random()
+            if r < rate / 3:
+                continue                                  # deletion
+            if r < 2 * rate / 3:
+                out.append(rng.choice("ACGT"))            # insertion before ch
+            elif r < rate:
+                ch = rng.choice("ACGT".replace(ch, ""))   # substitution
+            out.append(ch)
+        s = "".join(out)
+        if i < n_reads_with_n:
+            for _ in range(3):
+                p = rng.randrange(len(s))
+                s = s[:p] + "N" + s[p + 1:]
+        if rng.random() < rc_frac:
+            s = s.translate(comp)[::-1]
+        reads.append(s)
+    return reads
