@@ -336,6 +336,45 @@ float dmx_pairdist_ms(dmx_ctx* ctx);  /* device time of the last dmx_pairdist (H
  * word per lane; above 64 words it runs in stripes of 64 G rows with G = 64. */
 int dmx_pairdist_group_sizes(int* out, int cap);
 
+/* ---- Global alignment with the edit path ----------------------------------------
+ * The GPU counterpart of edlib.align(q, t, mode='NW', task='path'), which create_alignment()
+ * of amplicon_sorter.py (:333-339) runs for every read of every group it builds a consensus
+ * of.  The consensus loop itself is NOT replaced (its alignments are sequential and their
+ * targets carry gaps: DESIGN.md §8f).  Alphabet, equality, DMX_PD_RC, the length limits and
+ * the argument checks are dmx_pairdist's; additionalEqualities is not supported.
+ * The query is the rows, the target the columns (edlib's orientation); ops carry edlib's
+ * numbering.  An INSERT is a step up (a gap in the target), a DELETE a step left (a gap in
+ * the query).  The distance has one right answer, a path has not, so the tie rule is part of
+ * the contract: walking back from (m, n), at (i, j) with i, j > 0
+ *   1. D(i-1, j) + 1 == D(i, j): INSERT;  2. else D(i, j-1) + 1 == D(i, j): DELETE;
+ *   3. else the diagonal, MATCH on equal symbols and MISMATCH otherwise;
+ * on row 0 only DELETE, on column 0 only INSERT.  Ops are reported in forward order.  Whether
+ * edlib breaks ties the same way is not pinned (edlib is not vendored); the host version below
+ * applies the rule literally on a full matrix and the kernel equals it op for op. */
+#define DMX_PA_MATCH 0           /* consumes query and target */
+#define DMX_PA_INSERT 1          /* consumes query only */
+#define DMX_PA_DELETE 2          /* consumes target only */
+#define DMX_PA_MISMATCH 3        /* consumes query and target */
+/* dist[i] and the path of read q[i] against read t[i] of the resident batch: pair i's ops are
+ * ops[op_off[i] .. op_off[i + 1]) (op_off has n_pairs + 1 entries).  ops_cap must be at least
+ * the sum over the pairs of both reads' lengths (DMX_E_INVALID otherwise).  flags may be NULL.
+ * The forward pass keeps a trace of about 18 bytes per (64-row word, column); the pair list
+ * runs in as many launches as keep one launch's trace under DMX_PA_TRACE_MB MiB (environment,
+ * default 1024; one pair at least per launch), with the same results.  Synchronous. */
+int dmx_pairalign(dmx_ctx* ctx, const uint32_t* q, const uint32_t* t, const uint8_t* flags,
+                  size_t n_pairs, uint32_t* dist, uint64_t* op_off, uint8_t* ops, size_t ops_cap);
+/* Host only (no GPU; tests, CPU baseline): the same contract on a dmx_pack layout, by a plain
+ * full-matrix DP and the tie rule applied literally (2 bytes per cell and thread).  Errors: the
+ * message is dmx_last_error(NULL). */
+int dmx_pairalign_host(const uint32_t* seq2b, const uint32_t* nmask, const uint64_t* offsets,
+                       const uint32_t* lens, size_t n_reads, const uint32_t* q, const uint32_t* t,
+                       const uint8_t* flags, size_t n_pairs, uint32_t* dist, uint64_t* op_off,
+                       uint8_t* ops, size_t ops_cap, int n_threads);
+float dmx_pairalign_ms(dmx_ctx* ctx);  /* device time of both kernels, last dmx_pairalign */
+/* ms[0] = the forward pass, ms[1] = the traceback of the last dmx_pairalign (first n_ms
+ * written); returns the number of launches the pair list was cut into. */
+int dmx_pairalign_stats(dmx_ctx* ctx, float* ms, int n_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ namespace dmx {
 
 struct ChopState;   // read reorientation (dmx_chop.hip)
 struct PdState;     // pairwise read distance (dmx_pairdist.hip)
+struct PaState;     // pairwise alignment with edit path (dmx_pairdist.hip)
 
 // Reach of a panel's gathers around a view, in nt (panel_reach below).
 struct PanelReach {
@@ -142,6 +143,7 @@ struct Ctx {
     bool executed = false;
     ChopState* chop = nullptr;   // dmx_chop_* state, created by dmx_chop_set
     PdState* pd = nullptr;       // dmx_pairdist buffers, created by its first call
+    PaState* pa = nullptr;       // dmx_pairalign buffers, created by its first call
 
     // RCCL communicator for the per-bin count exchange (dmx_comm.cpp)
     ncclComm* comm = nullptr;

@@ -4451,10 +4451,11 @@ int bounds_check(Ctx* c, const char* where) {
         "select_cand_kernel", "resolve_kernel", "select_kernel", "finalize0_kernel",
         "finalize1_kernel", "finalize0_linked_kernel", "finalize1_linked_kernel",
         "finalize2_linked_kernel", "chop_kernel", "chop_big_kernel", "chop_start",
-        "bounds_selftest_kernel", "pscreen_kernel", "pairdist_kernel"};
+        "bounds_selftest_kernel", "pscreen_kernel", "pairdist_kernel", "pairalign_kernel",
+        "pairalign_traceback_kernel"};
     static const char* const kBuf[] = {"?", "seq", "nmask", "winner slots", "items", "results",
                                        "counts", "reads", "linked keys", "candidates", "chop",
-                                       "pairdist scratch"};
+                                       "pairdist scratch", "pairalign trace", "pairalign ops"};
     uint32_t rec[4];
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess)

@@ -41,13 +41,16 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_comm_size", "dmx_allreduce_counts", "dmx_debug_fetch", "dmx_run_sparse",
            "dmx_mask_exceptions", "dmx_host_register", "dmx_host_unregister", "dmx_panel_reach",
            "dmx_debug_bounds_selftest", "dmx_panel_pieces", "dmx_pairdist", "dmx_pairdist_host",
-           "dmx_pairdist_group_sizes"]
+           "dmx_pairdist_group_sizes", "dmx_pairalign", "dmx_pairalign_host",
+           "dmx_pairalign_stats"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
 LOC_IGNORE_CASE, LOC_ONLY_POSITIVE = 0x1, 0x2
 # include/dmx.h dmx_pairdist: modes, the pair flag, the longest read
 PD_NW, PD_HW, PD_RC, PD_MAX_LEN = 0, 1, 0x1, 16384
+# include/dmx.h dmx_pairalign: the ops of an edit path (edlib's numbering)
+PA_MATCH, PA_INSERT, PA_DELETE, PA_MISMATCH = 0, 1, 2, 3
 HIT_DTYPE = np.dtype([("seq", "<u8"), ("pattern", "<i4"), ("strand", "<i4"), ("start", "<i4"),
                       ("end", "<i4")])
 assert HIT_DTYPE.itemsize == 24
@@ -148,6 +151,13 @@ def load() -> ctypes.CDLL:
         L.dmx_pairdist_ms.argtypes = [P]
         L.dmx_pairdist_ms.restype = ctypes.c_float
         L.dmx_pairdist_group_sizes.argtypes = [ctypes.POINTER(c_int), c_int]
+    if hasattr(L, "dmx_pairalign"):
+        L.dmx_pairalign.argtypes = [P, P, P, P, c_size, P, c_u64p, P, c_size]
+        L.dmx_pairalign_host.argtypes = [P, P, c_u64p, P, c_size, P, P, P, c_size, P, c_u64p, P,
+                                         c_size, c_int]
+        L.dmx_pairalign_ms.argtypes = [P]
+        L.dmx_pairalign_ms.restype = ctypes.c_float
+        L.dmx_pairalign_stats.argtypes = [P, ctypes.POINTER(ctypes.c_float), c_int]
     # DMX_ALLOW_ABI=1: load an older in-tree build for a regression A/B (tools/replay_sweep.py)
     if L.dmx_abi_version() != ABI_VERSION and os.environ.get("DMX_ALLOW_ABI") != "1":
         raise DmxError("libdmx ABI mismatch")
@@ -289,6 +299,7 @@ class Context:
                                      p.offsets.ctypes.data, p.lengths.ctypes.data, p.n_words,
                                      p.n_reads), "dmx_load")
         self._n_loaded = p.n_reads
+        self._lengths = np.array(p.lengths, dtype=np.uint32)   # pairalign sizes its output by them
 
     def exec(self):
         self._check(self._L.dmx_exec(self._h), "dmx_exec")
@@ -394,6 +405,31 @@ class Context:
         """Device time (ms) of the last pairdist call."""
         return float(self._L.dmx_pairdist_ms(self._h))
 
+    # ---- global alignment with the edit path (include/dmx.h dmx_pairalign; DESIGN.md §8f) -------
+    def pairalign(self, q, t, flags=None):
+        """NW alignment of resident read q[i] (query, rows) against t[i] (target, columns), as
+        edlib.align(mode='NW', task='path').  flags: PD_RC per pair.  Returns (dist uint32,
+        op_off uint64 of n + 1 entries, ops uint8): pair i's path is ops[op_off[i]:op_off[i + 1]]
+        in forward order, PA_MATCH / PA_INSERT / PA_DELETE / PA_MISMATCH (see cigar())."""
+        qa, ta, fa, _ = _pair_arrays(q, t, flags, None)
+        dist, off, ops = _pairalign_buffers(getattr(self, "_lengths", None), qa, ta)
+        self._check(self._L.dmx_pairalign(self._h, qa.ctypes.data, ta.ctypes.data,
+                                          fa.ctypes.data if fa is not None else None, len(qa),
+                                          dist.ctypes.data, off.ctypes.data, ops.ctypes.data,
+                                          len(ops)), "dmx_pairalign")
+        return dist, off, ops[:int(off[-1])]
+
+    def pairalign_ms(self) -> float:
+        """Device time (ms) of both kernels of the last pairalign call."""
+        return float(self._L.dmx_pairalign_ms(self._h))
+
+    def pairalign_stats(self) -> dict:
+        """Device time (ms) of the last pairalign call by pass (the forward pass that writes the
+        trace, the traceback) and the launches its pair list was cut into (DMX_PA_TRACE_MB)."""
+        ms = (ctypes.c_float * 2)()
+        n = self._check(self._L.dmx_pairalign_stats(self._h, ms, 2), "dmx_pairalign_stats")
+        return {"forward": float(ms[0]), "traceback": float(ms[1]), "launches": int(n)}
+
     def n_counts(self) -> int:
         a1 = 0 if self.mode == MODE_SINGLE else self.panel_sizes[1]
         return (self.panel_sizes[0] + 1) * (a1 + 1) + 2
@@ -480,6 +516,55 @@ def pairdist_host(p: "Packed", q, t, mode: int = PD_NW, flags=None, caps=None,
         msg = L.dmx_last_error(None)
         raise DmxError(f"dmx_pairdist_host failed ({rc}): {msg.decode() if msg else ''}")
     return out
+
+
+def _pairalign_buffers(lengths, qa, ta):
+    """dist, op_off and an ops buffer of the sum of both lengths per pair (the library's bound).
+    Pairs the library will refuse (an index outside the batch) count as empty here."""
+    n = 0 if lengths is None else len(lengths)
+    ln = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        ln[:n] = lengths
+    cap = int(ln[np.minimum(qa, n)].sum() + ln[np.minimum(ta, n)].sum())
+    return (np.zeros(len(qa), dtype=np.uint32), np.zeros(len(qa) + 1, dtype=np.uint64),
+            np.zeros(max(cap, 1), dtype=np.uint8))
+
+
+def pairalign_host(p: "Packed", q, t, flags=None, n_threads: int = 1, ops_cap=None):
+    """dmx_pairalign's contract on the host: a plain full-matrix DP and the tie rule applied
+    literally (no GPU).  The checker of the kernels and the CPU baseline of
+    tools/bench_pairalign.py.  ops_cap: the room given to the library instead of the sum of
+    both lengths per pair (to see it refused).  Returns (dist, op_off, ops) as
+    Context.pairalign."""
+    L = load()
+    qa, ta, fa, _ = _pair_arrays(q, t, flags, None)
+    dist, off, ops = _pairalign_buffers(p.lengths, qa, ta)
+    rc = L.dmx_pairalign_host(p.seq2b.ctypes.data, p.nmask.ctypes.data, p.offsets.ctypes.data,
+                              p.lengths.ctypes.data, p.n_reads, qa.ctypes.data, ta.ctypes.data,
+                              fa.ctypes.data if fa is not None else None, len(qa),
+                              dist.ctypes.data, off.ctypes.data, ops.ctypes.data,
+                              len(ops) if ops_cap is None else int(ops_cap), int(n_threads))
+    if rc < 0:
+        msg = L.dmx_last_error(None)
+        raise DmxError(f"dmx_pairalign_host failed ({rc}): {msg.decode() if msg else ''}")
+    return dist, off, ops[:int(off[-1])]
+
+
+def cigar(ops, extended: bool = False) -> str:
+    """edlib's CIGAR of one path (a slice of pairalign's ops), run-length encoded: standard
+    (M for a match or a mismatch, I, D) or extended (=, X, I, D)."""
+    a = np.asarray(ops, dtype=np.uint8)
+    if a.ndim != 1:
+        raise DmxError("cigar: one path (a one-dimensional array of ops)")
+    if len(a) == 0:
+        return ""
+    if int(a.max()) > PA_MISMATCH:
+        raise DmxError("cigar: an op outside 0..3")
+    sym = np.frombuffer(b"=IDX" if extended else b"MIDM", dtype=np.uint8)[a]
+    cut = np.flatnonzero(sym[1:] != sym[:-1]) + 1
+    start = np.concatenate([[0], cut])
+    runs = np.diff(np.concatenate([start, [len(sym)]]))
+    return "".join(f"{int(n)}{chr(sym[s0])}" for s0, n in zip(start, runs))
 
 
 def pairdist_group_sizes() -> list:

@@ -7,6 +7,13 @@ Clustering, species grouping and consensus building are NOT replaced: this modul
 similarity lines (`i:j:iden`, `i:j:iden:reverse`) the reference's later steps read.  The random
 selection modes (-ra, -a) are out of scope.  Alphabet: A, C, G, T, N (a read with any other
 byte is refused; the reference would compare such bytes literally).
+
+gapped() restates one iteration of create_alignment (:340-355) on a path of dmx_pairalign: the
+two gapped rows a read and a fresh, ungapped consensus get.  The loop over the reads of a group
+is NOT restated: the reference aligns read k against a consensus list that has already
+received the '-' gaps of reads 0..k-1 (`z.insert(i, '-')` edits the target in place, it is
+alignlist[0]), so a group's alignments are sequential and their targets hold a symbol that is
+not in the packed batch.
 """
 from __future__ import annotations
 
@@ -94,6 +101,28 @@ def identity_cap(length: int, threshold: float) -> int:
     while d < length and identity(d + 1, length) >= threshold:
         d += 1
     return d
+
+
+def gapped(query, target, ops):
+    """One iteration of create_alignment (:340-355) for a fresh, ungapped consensus `target`
+    and the read `query`, from the path `ops` of query against target (lib.pairalign): the
+    consensus row with a '-' wherever the read inserts (I), and the read's row with a '-'
+    wherever it deletes (D).  Both rows have len(ops) columns.  Returns (target_row,
+    query_row) as str."""
+    q = query.decode("ascii") if isinstance(query, (bytes, bytearray)) else str(query)
+    t = target.decode("ascii") if isinstance(target, (bytes, bytearray)) else str(target)
+    a = np.asarray(ops, dtype=np.uint8)
+    takes_q = a != lib.PA_DELETE
+    takes_t = a != lib.PA_INSERT
+    if int(takes_q.sum()) != len(q) or int(takes_t.sum()) != len(t):
+        raise DmxError("gapped: the path does not span the query and the target")
+    qi = np.cumsum(takes_q) - 1
+    ti = np.cumsum(takes_t) - 1
+    qrow = np.where(takes_q, np.frombuffer((q or "-").encode(), dtype=np.uint8)[np.maximum(qi, 0)],
+                    ord("-")).astype(np.uint8)
+    trow = np.where(takes_t, np.frombuffer((t or "-").encode(), dtype=np.uint8)[np.maximum(ti, 0)],
+                    ord("-")).astype(np.uint8)
+    return trow.tobytes().decode(), qrow.tobytes().decode()
 
 
 def _clean(reads) -> list:
