@@ -13,13 +13,20 @@
 //
 // dmx_pairalign (edlib.align(mode='NW', task='path') of create_alignment,
 // amplicon_sorter.py:333-339) runs the same scheme with a trace of every word's Pv / Mv and
-// last-row score per column (pairalign_kernel), and a second kernel that walks the edit path
-// back through it (pairalign_traceback_kernel).
+// last-row score per column, and a second kernel that walks the edit path back through it
+// (pairalign_traceback_kernel).
+//
+// Both forms share one forward pass (pd_forward: pairdist_kernel and pairalign_kernel are its two
+// instantiations, told apart at compile time by their argument struct) and one host path: the
+// chunk planner (pd_plan: chunk limits, sort, wave packing, pair records), the staging of a
+// launch (pd_stage: buffers, upload, the arguments both kernels take) and the buffers themselves
+// (PdBufs).  A change to the block step, the stripes or the planner is made once.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <thread>
+#include <type_traits>
 
 #include "dmx_internal.h"
 
@@ -34,55 +41,40 @@ constexpr size_t kPdChunkDefault = 1u << 20;          // pairs per launch (DMX_P
 constexpr size_t kPdScratchMax = 64u << 20;           // scratch bytes per launch
 
 struct PdPair {
-    uint32_t q, t, cap, flags;   // flags: DMX_PD_RC | 0x100 (cap given)
+    uint32_t q, t, flags, cap;   // flags: DMX_PD_RC | 0x100 (cap given)
     uint64_t soff;               // the pair's scratch row (queries of more than one stripe)
+};
+static_assert(sizeof(PdPair) == 24, "the distance form uploads 24 bytes per pair");
+// dmx_pairalign's record carries on where dmx_pairdist's ends (no cap: cap and its flag are 0)
+struct PaPair : PdPair {
+    uint64_t toff;               // its trace: word-step (wi, j) is entry toff + wi * n + j
+    uint64_t roff;               // its (m + n)-byte op region
 };
 struct PdWave {
     uint32_t first, count, G, steps;   // pairs[first .. first + count), one group of G lanes each
 };
 
-struct PdArgs {
+// What both forms' kernels are given (pd_stage fills it).  `out` is not here but at the end of
+// both argument structs, and `flags` comes before `cap`: with this layout the trace form
+// compiles to the same instructions as before it shared its body.  The forward pass of a short
+// list (about one wave per SIMD) is sensitive to where its loop lies in the code.
+template <class Pair>
+struct PdHead {
     Packed pk;
     const uint64_t* offs;
     const uint32_t* lens;
-    const PdPair* pairs;
+    const Pair* pairs;
     const PdWave* waves;
     uint32_t n_waves;
     uint32_t n_pairs;
+    uint8_t* scratch;
+    uint64_t scratch_bytes;
+};
+struct PdArgs : PdHead<PdPair> {
     int mode;
-    uint8_t* scratch;
-    uint64_t scratch_bytes;
-    uint32_t* out;
+    uint32_t* out;               // per pair: the distance
 };
-
-struct PdState {
-    PdPair* d_pairs = nullptr;
-    PdWave* d_waves = nullptr;
-    uint32_t* d_out = nullptr;
-    uint8_t* d_scratch = nullptr;
-    size_t pair_cap = 0, wave_cap = 0, scratch_cap = 0;
-    hipEvent_t ev[2] = {};
-    float ms = 0.f;
-};
-
-// ---- dmx_pairalign: the NW distance and the edit path -------------------------
-struct PaPair {
-    uint32_t q, t, flags, pad;
-    uint64_t soff;               // the pair's scratch row (queries of more than one stripe)
-    uint64_t toff;               // its trace: word-step (wi, j) is entry toff + wi * n + j
-    uint64_t roff;               // its (m + n)-byte op region
-};
-
-struct PaArgs {
-    Packed pk;
-    const uint64_t* offs;
-    const uint32_t* lens;
-    const PaPair* pairs;
-    const PdWave* waves;
-    uint32_t n_waves;
-    uint32_t n_pairs;
-    uint8_t* scratch;
-    uint64_t scratch_bytes;
+struct PaArgs : PdHead<PaPair> {
     ulonglong2* pm;              // trace: Pv, Mv of a word after a column
     uint16_t* sc;                // trace: D(word's last row, column)
     uint64_t trace_steps;        // entries of pm / sc
@@ -91,39 +83,58 @@ struct PaArgs {
     uint32_t* out;               // per pair: distance, path length
 };
 
-struct PaState {
-    PaPair* d_pairs = nullptr;
-    PdWave* d_waves = nullptr;
-    uint32_t* d_out = nullptr;
-    uint8_t* d_scratch = nullptr;
-    ulonglong2* d_pm = nullptr;
-    uint16_t* d_sc = nullptr;
-    uint8_t* d_ops = nullptr;
-    size_t pair_cap = 0, wave_cap = 0, scratch_cap = 0, trace_cap = 0, ops_cap = 0;
-    hipEvent_t ev[3] = {};
+// A device buffer that grows on demand, never shrinks, and is freed with its owner.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;   // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) hipFree(p);
+    }
+    hipError_t reserve(size_t n) {   // room for n elements (one at least); the content is not kept
+        if (p && cap >= n) return hipSuccess;
+        if (p) hipFree(p);
+        p = nullptr;
+        cap = 0;
+        n = std::max<size_t>(n, 1);
+        const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
+        if (e == hipSuccess) cap = n;
+        return e;
+    }
+};
+
+// The buffers and events of either form; they go with the context (pd_release).
+template <class Pair>
+struct PdBufs {
+    DevBuf<Pair> pairs;
+    DevBuf<PdWave> waves;
+    DevBuf<uint32_t> out;
+    DevBuf<uint8_t> scratch;
+    hipEvent_t ev[3] = {};       // before the forward pass, after it, after the traceback
+    ~PdBufs() {
+        for (auto& e : ev)
+            if (e) hipEventDestroy(e);
+    }
+};
+struct PdState : PdBufs<PdPair> {
+    float ms = 0.f;
+};
+struct PaState : PdBufs<PaPair> {
+    DevBuf<ulonglong2> pm;
+    DevBuf<uint16_t> sc;
+    DevBuf<uint8_t> ops;
     float ms[2] = {0.f, 0.f};    // forward pass, traceback
     int launches = 0;            // chunks of the last call
 };
 
 void pd_release(Ctx* c) {
-    if (PdState* s = c->pd) {
-        void* bufs[] = {s->d_pairs, s->d_waves, s->d_out, s->d_scratch};
-        for (void* b : bufs)
-            if (b) hipFree(b);
-        for (auto& e : s->ev)
-            if (e) hipEventDestroy(e);
-        delete s;
-        c->pd = nullptr;
-    }
-    if (PaState* s = c->pa) {
-        void* bufs[] = {s->d_pairs, s->d_waves, s->d_out, s->d_scratch, s->d_pm, s->d_sc, s->d_ops};
-        for (void* b : bufs)
-            if (b) hipFree(b);
-        for (auto& e : s->ev)
-            if (e) hipEventDestroy(e);
-        delete s;
-        c->pa = nullptr;
-    }
+    delete c->pd;
+    delete c->pa;
+    c->pd = nullptr;
+    c->pa = nullptr;
 }
 
 // The five match masks (A, C, G, T, N) of query rows 64 wi .. 64 wi + 63, built in registers
@@ -160,7 +171,16 @@ __device__ __forceinline__ void pd_masks(const Packed& pk, uint64_t qoff, uint32
     peq[4] = nb;
 }
 
-__global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs A) {
+// The forward pass of both forms, told apart at compile time by the argument struct.
+// PdArgs, the distance: NW or HW (A.mode); only the lane of the query's last word follows the
+// score (and, for HW, its minimum over the columns); out[k] = the distance, clamped by the cap.
+// PaArgs, the trace (dmx_pairalign's forward pass): NW; every live lane follows D(r, j) of its
+// word's last row r = min(64 (wi + 1), m) and leaves Pv, Mv and that score of every column in
+// the pair's trace at [wi][j] (a lane writes consecutive entries over time); out[2 k] = the
+// distance.
+template <class Args>
+__device__ __forceinline__ void pd_forward(const Args& A) {
+    constexpr bool kTrace = std::is_same<Args, PaArgs>::value;
     const uint32_t wave = blockIdx.x * kPdWavesPerBlock + (threadIdx.x >> 6);
     if (wave >= A.n_waves) return;   // whole waves leave: the shift below sees full waves
     const uint32_t lane = threadIdx.x & 63u;
@@ -168,20 +188,26 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs 
     const uint32_t G = W.G;
     const uint32_t g = lane / G, w = lane - g * G;
     bool active = g < W.count && (uint64_t)W.first + g < A.n_pairs;
+    bool nw = true;
+    if constexpr (!kTrace) nw = A.mode == DMX_PD_NW;
 
     uint32_t m = 1, n = 1, rc = 0, cap = 0, has_cap = 0;
-    uint64_t qoff = 0, toff = 0, soff = 0;
+    uint64_t qoff = 0, toff = 0, soff = 0, trace = 0;
     if (active) {
-        const PdPair P = A.pairs[W.first + g];
+        const auto P = A.pairs[W.first + g];
         if (DMX_BOUND(A.pk.bd, reads, P.q, kBufRead) && DMX_BOUND(A.pk.bd, reads, P.t, kBufRead)) {
             m = A.lens[P.q];
             n = A.lens[P.t];
             qoff = A.offs[P.q];
             toff = A.offs[P.t];
             rc = P.flags & DMX_PD_RC;
-            has_cap = P.flags & 0x100u;
-            cap = P.cap;
             soff = P.soff;
+            if constexpr (kTrace) {
+                trace = P.toff;
+            } else {
+                has_cap = P.flags & 0x100u;
+                cap = P.cap;
+            }
         } else {
             active = false;
         }
@@ -191,7 +217,7 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs 
     const uint32_t L = n + G;                    // steps per stripe (n + G - 1, one to spare)
 
     uint64_t peq[5] = {0, 0, 0, 0, 0};
-    uint64_t Pv = 0, Mv = 0;
+    uint64_t Pv = 0, Mv = 0, tbase = 0;
     uint32_t s = 0, ts = 0, pass = 0, codes = 0, nbits = 0, wi = 0, hb = 63;
     bool last = false, live = false;
     int score = 0, best = 0;
@@ -207,8 +233,11 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs 
             if (live) pd_masks(A.pk, qoff, m, wi, peq);
             Pv = ~0ull;
             Mv = 0ull;
-            hb = last ? ((m - 1u) & 63u) : 63u;
-            if (last) score = best = (int)m;
+            // the word's last row: the query's in its last word, so no padded row is ever read
+            const uint32_t r = min(m, 64u * (wi + 1u));
+            hb = (r - 1u) & 63u;
+            if (kTrace || last) score = best = (int)r;
+            if constexpr (kTrace) tbase = trace + (uint64_t)wi * n;
         }
         if (w == 0) {   // the group's first lane feeds the array: row 0's delta or the stripe
                         // above's, and the target symbol
@@ -218,7 +247,7 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs 
                 const uint32_t k = ts & 15u;
                 sym = ((nbits >> k) & 1u) ? 4u : ((codes >> (2u * k)) & 3u);
                 if (s == 0) {
-                    hin1 = A.mode == DMX_PD_NW ? 2u : 1u;   // D(0, j) = j, or 0 in HW
+                    hin1 = nw ? 2u : 1u;   // D(0, j) = j, or 0 in HW
                 } else {
                     const uint64_t si = soff + ts;
                     hin1 = bchk(A.pk.bd, (int64_t)si, 0, (int64_t)A.scratch_bytes, kBufPd)
@@ -245,124 +274,15 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs 
             Pv = Mh | ~(Xv | Ph);
             Mv = Ph & Xv;
             pass = (uint32_t)(hout + 1) | (sym << 2);
-            if (last) {
-                score += hout;
+            if (kTrace || last) score += hout;
+            if constexpr (kTrace) {
+                const uint64_t ti = tbase + j;
+                if (bchk(A.pk.bd, (int64_t)ti, 0, (int64_t)A.trace_steps, kBufPaTrace)) {
+                    A.pm[ti] = make_ulonglong2(Pv, Mv);
+                    A.sc[ti] = (uint16_t)score;
+                }
+            } else if (last) {
                 best = min(best, score);
-            } else if (w + 1u == G) {   // the stripe's last row: kept for the stripe below
-                const uint64_t si = soff + j;
-                if (bchk(A.pk.bd, (int64_t)si, 0, (int64_t)A.scratch_bytes, kBufPd))
-                    A.scratch[si] = (uint8_t)(hout + 1);
-            }
-        }
-        if (++ts == L) {
-            ts = 0;
-            if (++s == S) {
-                active = false;
-                if (last) {
-                    uint32_t d = (uint32_t)(A.mode == DMX_PD_NW ? score : best);
-                    if (has_cap && d > cap) d = cap + 1u;
-                    A.out[W.first + g] = d;
-                }
-            } else {
-                __threadfence();   // the scratch row is read back by the group's first lane
-            }
-        }
-    }
-}
-
-// dmx_pairalign's forward pass: pairdist_kernel's NW scheme (same groups, stripes, scratch row
-// and target fetch), with every live lane also following D(r, j) of its word's last row
-// r = min(64 (wi + 1), m) and leaving Pv, Mv and that score of every column in the pair's trace
-// at [wi][j] (a lane writes consecutive entries over time).  out[2 k] = the distance.
-__global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairalign_kernel(PaArgs A) {
-    const uint32_t wave = blockIdx.x * kPdWavesPerBlock + (threadIdx.x >> 6);
-    if (wave >= A.n_waves) return;   // whole waves leave: the shift below sees full waves
-    const uint32_t lane = threadIdx.x & 63u;
-    const PdWave W = A.waves[wave];
-    const uint32_t G = W.G;
-    const uint32_t g = lane / G, w = lane - g * G;
-    bool active = g < W.count && (uint64_t)W.first + g < A.n_pairs;
-
-    uint32_t m = 1, n = 1, rc = 0;
-    uint64_t qoff = 0, toff = 0, soff = 0, trace = 0;
-    if (active) {
-        const PaPair P = A.pairs[W.first + g];
-        if (DMX_BOUND(A.pk.bd, reads, P.q, kBufRead) && DMX_BOUND(A.pk.bd, reads, P.t, kBufRead)) {
-            m = A.lens[P.q];
-            n = A.lens[P.t];
-            qoff = A.offs[P.q];
-            toff = A.offs[P.t];
-            rc = P.flags & DMX_PD_RC;
-            soff = P.soff;
-            trace = P.toff;
-        } else {
-            active = false;
-        }
-    }
-    const uint32_t mw = (m + 63u) >> 6;          // words of the query
-    const uint32_t S = (mw + G - 1u) / G;        // stripes
-    const uint32_t L = n + G;                    // steps per stripe (n + G - 1, one to spare)
-
-    uint64_t peq[5] = {0, 0, 0, 0, 0};
-    uint64_t Pv = 0, Mv = 0, tbase = 0;
-    uint32_t s = 0, ts = 0, pass = 0, codes = 0, nbits = 0, wi = 0, hb = 63;
-    bool last = false, live = false;
-    int score = 0;
-
-    for (uint32_t step = 0; step < W.steps; ++step) {
-        uint32_t recv = (uint32_t)__shfl_up((int)pass, 1);
-        if (!active) continue;
-        if (ts == 0) {   // a stripe starts: this lane's word, D(i, 0) = i
-            wi = s * G + w;
-            live = wi < mw;
-            last = wi + 1u == mw;
-            if (live) pd_masks(A.pk, qoff, m, wi, peq);
-            Pv = ~0ull;
-            Mv = 0ull;
-            const uint32_t r = min(m, 64u * (wi + 1u));   // the word's last row
-            hb = (r - 1u) & 63u;
-            score = (int)r;
-            tbase = trace + (uint64_t)wi * n;
-        }
-        if (w == 0) {   // the group's first lane feeds the array (pairdist_kernel, NW)
-            uint32_t sym = 0, hin1 = 1;
-            if (ts < n) {
-                if ((ts & 15u) == 0u) fetch16(A.pk, toff, n, rc, 0u, ts, codes, nbits);
-                const uint32_t k = ts & 15u;
-                sym = ((nbits >> k) & 1u) ? 4u : ((codes >> (2u * k)) & 3u);
-                if (s == 0) {
-                    hin1 = 2u;   // D(0, j) = j
-                } else {
-                    const uint64_t si = soff + ts;
-                    hin1 = bchk(A.pk.bd, (int64_t)si, 0, (int64_t)A.scratch_bytes, kBufPd)
-                               ? A.scratch[si] : 1u;
-                }
-            }
-            recv = hin1 | (sym << 2);
-        }
-        const uint32_t j = ts - w;   // wraps above n for ts < w
-        if (live && j < n) {
-            const uint32_t sym = recv >> 2;
-            const int hin = (int)(recv & 3u) - 1;
-            uint64_t Eq = sym == 0 ? peq[0] : sym == 1 ? peq[1] : sym == 2 ? peq[2]
-                        : sym == 3 ? peq[3] : peq[4];
-            const uint64_t hneg = hin < 0 ? 1ull : 0ull, hpos = hin > 0 ? 1ull : 0ull;
-            const uint64_t Xv = Eq | Mv;
-            Eq |= hneg;
-            const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-            uint64_t Ph = Mv | ~(Xh | Pv);
-            uint64_t Mh = Pv & Xh;
-            const int hout = (int)((Ph >> hb) & 1ull) - (int)((Mh >> hb) & 1ull);
-            Ph = (Ph << 1) | hpos;
-            Mh = (Mh << 1) | hneg;
-            Pv = Mh | ~(Xv | Ph);
-            Mv = Ph & Xv;
-            pass = (uint32_t)(hout + 1) | (sym << 2);
-            score += hout;
-            const uint64_t ti = tbase + j;
-            if (bchk(A.pk.bd, (int64_t)ti, 0, (int64_t)A.trace_steps, kBufPaTrace)) {
-                A.pm[ti] = make_ulonglong2(Pv, Mv);
-                A.sc[ti] = (uint16_t)score;
             }
             if (!last && w + 1u == G) {   // the stripe's last row: kept for the stripe below
                 const uint64_t si = soff + j;
@@ -374,13 +294,24 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairalign_kernel(PaArgs
             ts = 0;
             if (++s == S) {
                 active = false;
-                if (last) A.out[2u * (W.first + g)] = (uint32_t)score;
+                if (last) {
+                    if constexpr (kTrace) {
+                        A.out[2u * (W.first + g)] = (uint32_t)score;
+                    } else {
+                        uint32_t d = (uint32_t)(nw ? score : best);
+                        if (has_cap && d > cap) d = cap + 1u;
+                        A.out[W.first + g] = d;
+                    }
+                }
             } else {
                 __threadfence();   // the scratch row is read back by the group's first lane
             }
         }
     }
 }
+
+__global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs A) { pd_forward(A); }
+__global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairalign_kernel(PaArgs A) { pd_forward(A); }
 
 // dmx_pairalign's traceback: one lane per pair walks back from (m, n), preferring up (INSERT),
 // then left (DELETE), then the diagonal (include/dmx.h).  Bit b of a word's Pv / Mv at column j
@@ -459,22 +390,25 @@ using namespace dmx;
 
 namespace {
 
-#define PD_CK(call)                                                                          \
+// `who` is the entry point's name: it opens every message.
+#define PD_CK(who, call)                                                                     \
     do {                                                                                     \
         hipError_t e_ = (call);                                                              \
         if (e_ != hipSuccess) {                                                              \
-            c->err = std::string("dmx_pairdist: ") + #call + ": " + hipGetErrorString(e_);   \
+            c->err = std::string(who) + ": " + #call + ": " + hipGetErrorString(e_);         \
             return DMX_E_HIP;                                                                \
         }                                                                                    \
     } while (0)
 
-template <typename T>
-hipError_t pd_realloc(T** p, size_t count) {
-    if (*p) {
-        hipFree(*p);
-        *p = nullptr;
-    }
-    return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
+constexpr size_t kPaTraceEntry = sizeof(ulonglong2) + sizeof(uint16_t);   // bytes per word-step
+constexpr size_t kPaTraceMbDefault = 1024;                                // DMX_PA_TRACE_MB
+constexpr size_t kPdNoBudget = ~(size_t)0;                                // no trace: no budget
+
+// A number from the environment: `dflt` when unset or 0, `most` at most.
+size_t pd_env(const char* name, size_t dflt, size_t most) {
+    const char* e = std::getenv(name);
+    const size_t v = e ? (size_t)std::strtoull(e, nullptr, 10) : 0;
+    return std::min(v ? v : dflt, most);
 }
 
 int pd_group_size(uint32_t m) {
@@ -485,29 +419,46 @@ int pd_group_size(uint32_t m) {
 }
 
 // Arguments every form checks the same way.  0, or the code with *err set.
-int pd_validate(int mode, const uint32_t* lens, size_t n_reads, const uint32_t* q,
+int pd_validate(const char* who, int mode, const uint32_t* lens, size_t n_reads, const uint32_t* q,
                 const uint32_t* t, const uint8_t* flags, size_t n_pairs, std::string* err) {
+    const std::string name = std::string(who) + ": ";
     if (mode != DMX_PD_NW && mode != DMX_PD_HW) {
-        *err = "dmx_pairdist: mode must be DMX_PD_NW or DMX_PD_HW";
+        *err = name + "mode must be DMX_PD_NW or DMX_PD_HW";
         return DMX_E_INVALID;
     }
     for (size_t i = 0; i < n_pairs; ++i) {
         if (q[i] >= n_reads || t[i] >= n_reads) {
-            *err = "dmx_pairdist: pair " + std::to_string(i) + " names a read outside the batch";
+            *err = name + "pair " + std::to_string(i) + " names a read outside the batch";
             return DMX_E_INVALID;
         }
         if (flags && (flags[i] & ~DMX_PD_RC)) {
-            *err = "dmx_pairdist: pair " + std::to_string(i) + " has an unknown flag";
+            *err = name + "pair " + std::to_string(i) + " has an unknown flag";
             return DMX_E_INVALID;
         }
     }
     for (size_t i = 0; i < n_pairs; ++i) {
         const uint32_t m = lens[q[i]], n = lens[t[i]];
         if (m < 1 || n < 1 || m > DMX_PD_MAX_LEN || n > DMX_PD_MAX_LEN) {
-            *err = "dmx_pairdist: pair " + std::to_string(i) + ": reads of 1.." +
+            *err = name + "pair " + std::to_string(i) + ": reads of 1.." +
                    std::to_string(DMX_PD_MAX_LEN) + " nt supported";
             return DMX_E_UNSUPPORTED;
         }
+    }
+    return DMX_OK;
+}
+
+// pd_validate for dmx_pairalign (NW), and the room the paths may need.
+int pa_validate(const uint32_t* lens, size_t n_reads, const uint32_t* q, const uint32_t* t,
+                const uint8_t* flags, size_t n_pairs, size_t ops_cap, std::string* err) {
+    if (const int rc = pd_validate("dmx_pairalign", DMX_PD_NW, lens, n_reads, q, t, flags, n_pairs,
+                                   err))
+        return rc;
+    size_t need = 0;
+    for (size_t i = 0; i < n_pairs; ++i) need += (size_t)lens[q[i]] + lens[t[i]];
+    if (ops_cap < need) {
+        *err = "dmx_pairalign: ops_cap " + std::to_string(ops_cap) + " is below the " +
+               std::to_string(need) + " bytes the paths may take (sum of both lengths)";
+        return DMX_E_INVALID;
     }
     return DMX_OK;
 }
@@ -546,212 +497,6 @@ uint32_t pd_dp(int mode, const std::vector<uint8_t>& a, const std::vector<uint8_
     return *std::min_element(row.begin(), row.end());
 }
 
-}  // namespace
-
-extern "C" int dmx_pairdist_group_sizes(int* out, int cap) {
-    for (int k = 0; k < kPdNSizes && k < cap && out; ++k) out[k] = kPdSizes[k];
-    return kPdNSizes;
-}
-
-extern "C" float dmx_pairdist_ms(dmx_ctx* c) { return c && c->pd ? c->pd->ms : 0.f; }
-
-extern "C" int dmx_pairdist_host(int mode, const uint32_t* seq2b, const uint32_t* nmask,
-                                 const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
-                                 const uint32_t* q, const uint32_t* t, const uint8_t* flags,
-                                 const uint32_t* caps, size_t n_pairs, uint32_t* out,
-                                 int n_threads) {
-    if (n_pairs && (!q || !t || !out || !seq2b || !nmask || !offsets || !lens)) return DMX_E_INVALID;
-    std::string err;
-    if (const int rc = pd_validate(mode, lens, n_reads, q, t, flags, n_pairs, &err)) {
-        set_process_error(err);
-        return rc;
-    }
-    const size_t nth = std::max<size_t>(1, std::min<size_t>((size_t)std::max(n_threads, 1),
-                                                            std::max<size_t>(n_pairs, 1)));
-    auto work = [&](size_t k) {
-        std::vector<uint8_t> a, b;
-        std::vector<uint32_t> row;
-        for (size_t i = k; i < n_pairs; i += nth) {   // interleaved: similar work per thread
-            pd_decode(seq2b, nmask, offsets[q[i]], lens[q[i]], false, a);
-            pd_decode(seq2b, nmask, offsets[t[i]], lens[t[i]], flags && (flags[i] & DMX_PD_RC), b);
-            uint32_t d = pd_dp(mode, a, b, row);
-            if (caps && d > caps[i]) d = caps[i] + 1u;
-            out[i] = d;
-        }
-    };
-    if (nth == 1) {
-        work(0);
-    } else {
-        std::vector<std::thread> th;
-        for (size_t k = 0; k < nth; ++k) th.emplace_back(work, k);
-        for (auto& x : th) x.join();
-    }
-    return DMX_OK;
-}
-
-extern "C" int dmx_pairdist(dmx_ctx* c, int mode, const uint32_t* q, const uint32_t* t,
-                            const uint8_t* flags, const uint32_t* caps, size_t n_pairs,
-                            uint32_t* out) {
-    if (!c) return DMX_E_INVALID;
-    if (n_pairs && (!q || !t || !out)) {
-        c->err = "dmx_pairdist: null pair list or output";
-        return DMX_E_INVALID;
-    }
-    if (c->pd) c->pd->ms = 0.f;
-    const size_t n_reads = c->d_seq ? c->n_reads : 0;
-    // everything is validated on the host before anything is launched: the lengths come back
-    // from the resident batch (a copy, no kernel)
-    std::vector<uint32_t> lens(n_reads);
-    if (n_reads && n_pairs) {
-        PD_CK(hipSetDevice(c->device));
-        PD_CK(hipMemcpy(lens.data(), c->d_lens, n_reads * 4, hipMemcpyDeviceToHost));
-    }
-    if (const int rc = pd_validate(mode, lens.data(), n_reads, q, t, flags, n_pairs, &c->err))
-        return rc;
-    if (!n_pairs) return DMX_OK;
-    if (!c->pd) {
-        c->pd = new PdState();
-        for (auto& e : c->pd->ev) PD_CK(hipEventCreate(&e));
-    }
-    PdState* s = c->pd;
-    hipStream_t st = c->stream;
-    size_t chunk = kPdChunkDefault;
-    if (const char* e = std::getenv("DMX_PD_CHUNK")) {
-        const size_t v = (size_t)std::strtoull(e, nullptr, 10);
-        if (v) chunk = v;
-    }
-    chunk = std::min<size_t>(chunk, 1u << 24);
-
-    std::vector<uint64_t> keys;
-    std::vector<PdPair> pairs;
-    std::vector<PdWave> waves;
-    std::vector<uint32_t> res;
-    float total_ms = 0.f;
-    for (size_t lo = 0; lo < n_pairs;) {
-        // the chunk: up to `chunk` pairs, fewer when their scratch rows fill the bound
-        size_t hi = lo, scratch = 0;
-        keys.clear();
-        while (hi < n_pairs && hi - lo < chunk) {
-            const uint32_t m = lens[q[hi]], n = lens[t[hi]];
-            const size_t need = m > 64u * 64u ? n : 0;
-            if (hi > lo && scratch + need > kPdScratchMax) break;
-            scratch += need;
-            // sort key: group size, then target length (similar step counts share a wave),
-            // longest first; the low bits are the pair's place in the chunk
-            keys.push_back(((uint64_t)pd_group_size(m) << 48) | ((uint64_t)n << 24) |
-                           (uint64_t)(hi - lo));
-            ++hi;
-        }
-        const size_t np = hi - lo;
-        std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
-        pairs.resize(np);
-        waves.clear();
-        size_t soff = 0;
-        for (size_t k = 0; k < np;) {
-            const uint32_t G = (uint32_t)(keys[k] >> 48);
-            const uint32_t per = 64u / G;
-            PdWave W{(uint32_t)k, 0, G, 0};
-            while (k < np && W.count < per && (uint32_t)(keys[k] >> 48) == G) {
-                const size_t i = lo + (size_t)(keys[k] & 0xFFFFFFu);
-                const uint32_t m = lens[q[i]], n = lens[t[i]];
-                const uint32_t mw = (m + 63u) / 64u, S = (mw + G - 1u) / G;
-                PdPair& P = pairs[k];
-                P.q = q[i];
-                P.t = t[i];
-                P.cap = caps ? caps[i] : 0u;
-                P.flags = (flags ? (flags[i] & DMX_PD_RC) : 0u) | (caps ? 0x100u : 0u);
-                P.soff = soff;
-                if (S > 1) soff += n;
-                W.steps = std::max(W.steps, S * (n + G));
-                ++W.count;
-                ++k;
-            }
-            waves.push_back(W);
-        }
-        if (s->pair_cap < np || !s->d_pairs) {
-            PD_CK(pd_realloc(&s->d_pairs, np));
-            PD_CK(pd_realloc(&s->d_out, np));
-            s->pair_cap = np;
-        }
-        if (s->wave_cap < waves.size() || !s->d_waves) {
-            PD_CK(pd_realloc(&s->d_waves, waves.size()));
-            s->wave_cap = waves.size();
-        }
-        if (s->scratch_cap < soff || !s->d_scratch) {
-            PD_CK(pd_realloc(&s->d_scratch, soff));
-            s->scratch_cap = std::max<size_t>(soff, 1);
-        }
-        PD_CK(hipMemcpyAsync(s->d_pairs, pairs.data(), np * sizeof(PdPair), hipMemcpyHostToDevice,
-                             st));
-        PD_CK(hipMemcpyAsync(s->d_waves, waves.data(), waves.size() * sizeof(PdWave),
-                             hipMemcpyHostToDevice, st));
-        PD_CK(bounds_reset(c, st));
-        PdArgs A;
-        A.pk.seq = c->d_seq;
-        A.pk.nmask = c->d_nmask;
-        A.pk.bd = make_bounds(c, kKerPairdist);
-        A.offs = c->d_offs;
-        A.lens = c->d_lens;
-        A.pairs = s->d_pairs;
-        A.waves = s->d_waves;
-        A.n_waves = (uint32_t)waves.size();
-        A.n_pairs = (uint32_t)np;
-        A.mode = mode;
-        A.scratch = s->d_scratch;
-        A.scratch_bytes = s->scratch_cap;
-        A.out = s->d_out;
-        const uint32_t nb = (A.n_waves + kPdWavesPerBlock - 1u) / kPdWavesPerBlock;
-        PD_CK(hipEventRecord(s->ev[0], st));
-        hipLaunchKernelGGL(pairdist_kernel, dim3(nb), dim3(64 * kPdWavesPerBlock), 0, st, A);
-        PD_CK(hipGetLastError());
-        PD_CK(hipEventRecord(s->ev[1], st));
-        res.resize(np);
-        PD_CK(hipMemcpyAsync(res.data(), s->d_out, np * 4, hipMemcpyDeviceToHost, st));
-        PD_CK(hipStreamSynchronize(st));
-        if (const int brc = bounds_check(c, "dmx_pairdist")) return brc;
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-        total_ms += ms;
-        for (size_t k = 0; k < np; ++k) out[lo + (size_t)(keys[k] & 0xFFFFFFu)] = res[k];
-        lo = hi;
-    }
-    s->ms = total_ms;
-    return DMX_OK;
-}
-
-// ---- dmx_pairalign: the NW distance and the edit path (include/dmx.h; DESIGN.md §8f) -----------
-
-namespace {
-
-#define PA_CK(call)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            c->err = std::string("dmx_pairalign: ") + #call + ": " + hipGetErrorString(e_);  \
-            return DMX_E_HIP;                                                                \
-        }                                                                                    \
-    } while (0)
-
-constexpr size_t kPaTraceEntry = sizeof(ulonglong2) + sizeof(uint16_t);   // bytes per word-step
-constexpr size_t kPaTraceMbDefault = 1024;                                // DMX_PA_TRACE_MB
-
-// pd_validate with dmx_pairalign's name in the message, and the room the paths may need.
-int pa_validate(const uint32_t* lens, size_t n_reads, const uint32_t* q, const uint32_t* t,
-                const uint8_t* flags, size_t n_pairs, size_t ops_cap, std::string* err) {
-    if (const int rc = pd_validate(DMX_PD_NW, lens, n_reads, q, t, flags, n_pairs, err)) {
-        if (err->rfind("dmx_pairdist", 0) == 0) err->replace(0, 12, "dmx_pairalign");
-        return rc;
-    }
-    size_t need = 0;
-    for (size_t i = 0; i < n_pairs; ++i) need += (size_t)lens[q[i]] + lens[t[i]];
-    if (ops_cap < need) {
-        *err = "dmx_pairalign: ops_cap " + std::to_string(ops_cap) + " is below the " +
-               std::to_string(need) + " bytes the paths may take (sum of both lengths)";
-        return DMX_E_INVALID;
-    }
-    return DMX_OK;
-}
-
 // The whole (m + 1) x (n + 1) matrix, then the walk back from (m, n) by the contract's rule:
 // up (INSERT) before left (DELETE) before the diagonal.  The ops come out last first in `rev`.
 uint32_t pa_dp_path(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b,
@@ -787,7 +532,229 @@ uint32_t pa_dp_path(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b
     return D[m * W + n];
 }
 
+// work(k, nth) for k = 0 .. nth - 1 on nth <= n_threads threads; worker k takes pairs k, k + nth,
+// ... (interleaved: similar work per thread).
+template <class F>
+void pd_parallel(size_t n_pairs, int n_threads, F work) {
+    const size_t nth = std::min<size_t>((size_t)std::max(n_threads, 1), std::max<size_t>(n_pairs, 1));
+    if (nth == 1) return work(0, 1);
+    std::vector<std::thread> th;
+    for (size_t k = 0; k < nth; ++k) th.emplace_back(work, k, nth);
+    for (auto& x : th) x.join();
+}
+
+// The lengths of the resident batch, for the validation on the host before anything is
+// launched (a copy, no kernel).
+int pd_fetch_lens(Ctx* c, const char* who, size_t n_pairs, std::vector<uint32_t>& lens) {
+    lens.resize(c->d_seq ? c->n_reads : 0);
+    if (!lens.empty() && n_pairs) {
+        PD_CK(who, hipSetDevice(c->device));
+        PD_CK(who, hipMemcpy(lens.data(), c->d_lens, lens.size() * 4, hipMemcpyDeviceToHost));
+    }
+    return DMX_OK;
+}
+
+// The context's state of one form, made by the form's first call.
+template <class State>
+int pd_state(Ctx* c, const char* who, State*& s) {
+    if (!s) {
+        s = new State();
+        for (auto& e : s->ev) PD_CK(who, hipEventCreate(&e));
+    }
+    return DMX_OK;
+}
+
+// One launch: the pairs of a chunk in the order they run, cut into waves.
+template <class Pair>
+struct PdPlan {
+    std::vector<uint64_t> keys;   // sorted: (G, target length, place in the chunk), see place()
+    std::vector<Pair> pairs;
+    std::vector<PdWave> waves;
+    size_t scratch = 0, trace = 0, ops = 0;   // totals: scratch bytes, trace entries, op bytes
+    size_t place(size_t k) const { return (size_t)(keys[k] & 0xFFFFFFu); }   // of sorted pair k
+};
+
+// Plans the chunk that starts at pair `lo` and returns its end: up to max_pairs pairs, fewer
+// when their scratch rows fill kPdScratchMax or their traces (kPaTraceEntry bytes per word and
+// column) the budget; one pair at least.  The pairs are sorted by group size, then target
+// length (similar step counts share a wave), longest first, and packed into waves of one group
+// size, 64 / G groups at most.
+template <class Pair>
+size_t pd_plan(PdPlan<Pair>& pl, const uint32_t* lens, const uint32_t* q, const uint32_t* t,
+               const uint8_t* flags, const uint32_t* caps, size_t n_pairs, size_t lo,
+               size_t max_pairs, size_t trace_budget) {
+    size_t hi = lo, scratch = 0, trace = 0;
+    pl.keys.clear();
+    while (hi < n_pairs && hi - lo < max_pairs) {
+        const uint32_t m = lens[q[hi]], n = lens[t[hi]];
+        const size_t need = m > 64u * 64u ? n : 0;
+        const size_t steps = (size_t)((m + 63u) / 64u) * n;
+        if (hi > lo && (scratch + need > kPdScratchMax ||
+                        (trace + steps) * kPaTraceEntry > trace_budget))
+            break;
+        scratch += need;
+        trace += steps;
+        pl.keys.push_back(((uint64_t)pd_group_size(m) << 48) | ((uint64_t)n << 24) |
+                          (uint64_t)(hi - lo));
+        ++hi;
+    }
+    const size_t np = hi - lo;
+    std::sort(pl.keys.begin(), pl.keys.end(), std::greater<uint64_t>());
+    pl.pairs.resize(np);
+    pl.waves.clear();
+    pl.scratch = pl.trace = pl.ops = 0;
+    for (size_t k = 0; k < np;) {
+        const uint32_t G = (uint32_t)(pl.keys[k] >> 48);
+        const uint32_t per = 64u / G;
+        PdWave W{(uint32_t)k, 0, G, 0};
+        while (k < np && W.count < per && (uint32_t)(pl.keys[k] >> 48) == G) {
+            const size_t i = lo + pl.place(k);
+            const uint32_t m = lens[q[i]], n = lens[t[i]];
+            const uint32_t mw = (m + 63u) / 64u, S = (mw + G - 1u) / G;
+            Pair& P = pl.pairs[k];
+            P.q = q[i];
+            P.t = t[i];
+            P.cap = caps ? caps[i] : 0u;
+            P.flags = (flags ? (flags[i] & DMX_PD_RC) : 0u) | (caps ? 0x100u : 0u);
+            P.soff = pl.scratch;
+            if constexpr (std::is_same<Pair, PaPair>::value) {
+                P.toff = pl.trace;
+                P.roff = pl.ops;
+            }
+            if (S > 1) pl.scratch += n;
+            pl.trace += (size_t)mw * n;
+            pl.ops += (size_t)m + n;
+            W.steps = std::max(W.steps, S * (n + G));
+            ++W.count;
+            ++k;
+        }
+        pl.waves.push_back(W);
+    }
+    return hi;
+}
+
+// Stages a planned launch: room for its pairs, waves, scratch rows and out_words of output, the
+// upload, the bounds record's reset, and the arguments both forms' kernels take.
+template <class Pair>
+int pd_stage(Ctx* c, const char* who, PdBufs<Pair>& b, const PdPlan<Pair>& pl, size_t out_words,
+             int kid, PdHead<Pair>& A) {
+    const size_t np = pl.pairs.size(), nw = pl.waves.size();
+    hipStream_t st = c->stream;
+    PD_CK(who, b.pairs.reserve(np));
+    PD_CK(who, b.out.reserve(out_words));
+    PD_CK(who, b.waves.reserve(nw));
+    PD_CK(who, b.scratch.reserve(pl.scratch));
+    PD_CK(who, hipMemcpyAsync(b.pairs.p, pl.pairs.data(), np * sizeof(Pair), hipMemcpyHostToDevice,
+                              st));
+    PD_CK(who, hipMemcpyAsync(b.waves.p, pl.waves.data(), nw * sizeof(PdWave),
+                              hipMemcpyHostToDevice, st));
+    PD_CK(who, bounds_reset(c, st));
+    A.pk.seq = c->d_seq;
+    A.pk.nmask = c->d_nmask;
+    A.pk.bd = make_bounds(c, kid);
+    A.offs = c->d_offs;
+    A.lens = c->d_lens;
+    A.pairs = b.pairs.p;
+    A.waves = b.waves.p;
+    A.n_waves = (uint32_t)nw;
+    A.n_pairs = (uint32_t)np;
+    A.scratch = b.scratch.p;
+    A.scratch_bytes = b.scratch.cap;
+    return DMX_OK;
+}
+
+template <class Args>
+void pd_launch_forward(void (*kernel)(Args), const Args& A, hipStream_t st) {
+    const uint32_t nb = (A.n_waves + kPdWavesPerBlock - 1u) / kPdWavesPerBlock;
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(64 * kPdWavesPerBlock), 0, st, A);
+}
+
 }  // namespace
+
+extern "C" int dmx_pairdist_group_sizes(int* out, int cap) {
+    for (int k = 0; k < kPdNSizes && k < cap && out; ++k) out[k] = kPdSizes[k];
+    return kPdNSizes;
+}
+
+extern "C" float dmx_pairdist_ms(dmx_ctx* c) { return c && c->pd ? c->pd->ms : 0.f; }
+
+extern "C" int dmx_pairdist_host(int mode, const uint32_t* seq2b, const uint32_t* nmask,
+                                 const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
+                                 const uint32_t* q, const uint32_t* t, const uint8_t* flags,
+                                 const uint32_t* caps, size_t n_pairs, uint32_t* out,
+                                 int n_threads) {
+    if (n_pairs && (!q || !t || !out || !seq2b || !nmask || !offsets || !lens)) return DMX_E_INVALID;
+    std::string err;
+    if (const int rc = pd_validate("dmx_pairdist", mode, lens, n_reads, q, t, flags, n_pairs, &err)) {
+        set_process_error(err);
+        return rc;
+    }
+    pd_parallel(n_pairs, n_threads, [&](size_t k, size_t nth) {
+        std::vector<uint8_t> a, b;
+        std::vector<uint32_t> row;
+        for (size_t i = k; i < n_pairs; i += nth) {
+            pd_decode(seq2b, nmask, offsets[q[i]], lens[q[i]], false, a);
+            pd_decode(seq2b, nmask, offsets[t[i]], lens[t[i]], flags && (flags[i] & DMX_PD_RC), b);
+            uint32_t d = pd_dp(mode, a, b, row);
+            if (caps && d > caps[i]) d = caps[i] + 1u;
+            out[i] = d;
+        }
+    });
+    return DMX_OK;
+}
+
+extern "C" int dmx_pairdist(dmx_ctx* c, int mode, const uint32_t* q, const uint32_t* t,
+                            const uint8_t* flags, const uint32_t* caps, size_t n_pairs,
+                            uint32_t* out) {
+    const char* const who = "dmx_pairdist";
+    if (!c) return DMX_E_INVALID;
+    if (n_pairs && (!q || !t || !out)) {
+        c->err = "dmx_pairdist: null pair list or output";
+        return DMX_E_INVALID;
+    }
+    if (c->pd) c->pd->ms = 0.f;
+    std::vector<uint32_t> lens;
+    if (const int rc = pd_fetch_lens(c, who, n_pairs, lens)) return rc;
+    if (const int rc = pd_validate(who, mode, lens.data(), lens.size(), q, t, flags, n_pairs,
+                                   &c->err))
+        return rc;
+    if (!n_pairs) return DMX_OK;
+    if (const int rc = pd_state(c, who, c->pd)) return rc;
+    PdState* s = c->pd;
+    hipStream_t st = c->stream;
+    // the place in the chunk has 24 bits of the sort key
+    const size_t chunk = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+
+    PdPlan<PdPair> pl;
+    std::vector<uint32_t> res;
+    float total_ms = 0.f;
+    for (size_t lo = 0; lo < n_pairs;) {
+        const size_t hi = pd_plan(pl, lens.data(), q, t, flags, caps, n_pairs, lo, chunk,
+                                  kPdNoBudget);
+        const size_t np = hi - lo;
+        PdArgs A;
+        if (const int rc = pd_stage(c, who, *s, pl, np, kKerPairdist, A)) return rc;
+        A.mode = mode;
+        A.out = s->out.p;
+        PD_CK(who, hipEventRecord(s->ev[0], st));
+        pd_launch_forward(pairdist_kernel, A, st);
+        PD_CK(who, hipGetLastError());
+        PD_CK(who, hipEventRecord(s->ev[1], st));
+        res.resize(np);
+        PD_CK(who, hipMemcpyAsync(res.data(), A.out, np * 4, hipMemcpyDeviceToHost, st));
+        PD_CK(who, hipStreamSynchronize(st));
+        if (const int brc = bounds_check(c, who)) return brc;
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+        total_ms += ms;
+        for (size_t k = 0; k < np; ++k) out[lo + pl.place(k)] = res[k];
+        lo = hi;
+    }
+    s->ms = total_ms;
+    return DMX_OK;
+}
+
+// ---- dmx_pairalign: the NW distance and the edit path (include/dmx.h; DESIGN.md §8f) -----------
 
 extern "C" float dmx_pairalign_ms(dmx_ctx* c) {
     return c && c->pa ? c->pa->ms[0] + c->pa->ms[1] : 0.f;
@@ -818,9 +785,7 @@ extern "C" int dmx_pairalign_host(const uint32_t* seq2b, const uint32_t* nmask,
     std::vector<uint64_t> roff(n_pairs + 1, 0);
     for (size_t i = 0; i < n_pairs; ++i) roff[i + 1] = roff[i] + lens[q[i]] + lens[t[i]];
     std::vector<uint32_t> plen(n_pairs, 0);
-    const size_t nth = std::max<size_t>(1, std::min<size_t>((size_t)std::max(n_threads, 1),
-                                                            std::max<size_t>(n_pairs, 1)));
-    auto work = [&](size_t k) {
+    pd_parallel(n_pairs, n_threads, [&](size_t k, size_t nth) {
         std::vector<uint8_t> a, b, rev;
         std::vector<uint16_t> D;
         for (size_t i = k; i < n_pairs; i += nth) {
@@ -830,14 +795,7 @@ extern "C" int dmx_pairalign_host(const uint32_t* seq2b, const uint32_t* nmask,
             plen[i] = (uint32_t)rev.size();
             std::reverse_copy(rev.begin(), rev.end(), ops + roff[i + 1] - rev.size());
         }
-    };
-    if (nth == 1) {
-        work(0);
-    } else {
-        std::vector<std::thread> th;
-        for (size_t k = 0; k < nth; ++k) th.emplace_back(work, k);
-        for (auto& x : th) x.join();
-    }
+    });
     uint64_t at = 0;
     for (size_t i = 0; i < n_pairs; ++i) {
         op_off[i] = at;
@@ -851,6 +809,7 @@ extern "C" int dmx_pairalign_host(const uint32_t* seq2b, const uint32_t* nmask,
 extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, const uint8_t* flags,
                              size_t n_pairs, uint32_t* dist, uint64_t* op_off, uint8_t* ops,
                              size_t ops_cap) {
+    const char* const who = "dmx_pairalign";
     if (!c) return DMX_E_INVALID;
     if (!op_off || (n_pairs && (!q || !t || !dist || !ops))) {
         c->err = "dmx_pairalign: null pair list or output";
@@ -860,146 +819,52 @@ extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, c
         c->pa->ms[0] = c->pa->ms[1] = 0.f;
         c->pa->launches = 0;
     }
-    const size_t n_reads = c->d_seq ? c->n_reads : 0;
-    // everything is validated on the host before anything is launched (dmx_pairdist)
-    std::vector<uint32_t> lens(n_reads);
-    if (n_reads && n_pairs) {
-        PA_CK(hipSetDevice(c->device));
-        PA_CK(hipMemcpy(lens.data(), c->d_lens, n_reads * 4, hipMemcpyDeviceToHost));
-    }
-    if (const int rc = pa_validate(lens.data(), n_reads, q, t, flags, n_pairs, ops_cap, &c->err))
+    std::vector<uint32_t> lens;
+    if (const int rc = pd_fetch_lens(c, who, n_pairs, lens)) return rc;
+    if (const int rc = pa_validate(lens.data(), lens.size(), q, t, flags, n_pairs, ops_cap, &c->err))
         return rc;
     op_off[0] = 0;
     if (!n_pairs) return DMX_OK;
-    if (!c->pa) {
-        c->pa = new PaState();
-        for (auto& e : c->pa->ev) PA_CK(hipEventCreate(&e));
-    }
+    if (const int rc = pd_state(c, who, c->pa)) return rc;
     PaState* s = c->pa;
     hipStream_t st = c->stream;
-    size_t budget = kPaTraceMbDefault;
-    if (const char* e = std::getenv("DMX_PA_TRACE_MB")) {
-        const size_t v = (size_t)std::strtoull(e, nullptr, 10);
-        if (v) budget = v;
-    }
-    budget = std::min<size_t>(budget, (size_t)1 << 20) << 20;   // bytes
+    const size_t budget = pd_env("DMX_PA_TRACE_MB", kPaTraceMbDefault, (size_t)1 << 20) << 20;   // bytes
 
-    std::vector<uint64_t> keys;
-    std::vector<PaPair> pairs;
-    std::vector<PdWave> waves;
+    PdPlan<PaPair> pl;
     std::vector<uint32_t> res, place;
     std::vector<uint8_t> region;
     float ms_fwd = 0.f, ms_tb = 0.f;
     uint64_t at = 0;   // bytes of `ops` filled
     for (size_t lo = 0; lo < n_pairs;) {
-        // the chunk: pairs while their traces fit the budget and their scratch rows the bound,
-        // one pair at least
-        size_t hi = lo, scratch = 0, trace = 0;
-        keys.clear();
-        while (hi < n_pairs && hi - lo < kPdChunkDefault) {
-            const uint32_t m = lens[q[hi]], n = lens[t[hi]];
-            const size_t need = m > 64u * 64u ? n : 0;
-            const size_t steps = (size_t)((m + 63u) / 64u) * n;
-            if (hi > lo && (scratch + need > kPdScratchMax ||
-                            (trace + steps) * kPaTraceEntry > budget))
-                break;
-            scratch += need;
-            trace += steps;
-            keys.push_back(((uint64_t)pd_group_size(m) << 48) | ((uint64_t)n << 24) |
-                           (uint64_t)(hi - lo));
-            ++hi;
-        }
+        const size_t hi = pd_plan(pl, lens.data(), q, t, flags, nullptr, n_pairs, lo,
+                                  kPdChunkDefault, budget);
         const size_t np = hi - lo;
-        std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
-        pairs.resize(np);
-        waves.clear();
-        size_t soff = 0, toff = 0, roff = 0;
-        for (size_t k = 0; k < np;) {
-            const uint32_t G = (uint32_t)(keys[k] >> 48);
-            const uint32_t per = 64u / G;
-            PdWave W{(uint32_t)k, 0, G, 0};
-            while (k < np && W.count < per && (uint32_t)(keys[k] >> 48) == G) {
-                const size_t i = lo + (size_t)(keys[k] & 0xFFFFFFu);
-                const uint32_t m = lens[q[i]], n = lens[t[i]];
-                const uint32_t mw = (m + 63u) / 64u, S = (mw + G - 1u) / G;
-                PaPair& P = pairs[k];
-                P.q = q[i];
-                P.t = t[i];
-                P.flags = flags ? (flags[i] & DMX_PD_RC) : 0u;
-                P.pad = 0;
-                P.soff = soff;
-                P.toff = toff;
-                P.roff = roff;
-                if (S > 1) soff += n;
-                toff += (size_t)mw * n;
-                roff += (size_t)m + n;
-                W.steps = std::max(W.steps, S * (n + G));
-                ++W.count;
-                ++k;
-            }
-            waves.push_back(W);
-        }
-        if (s->pair_cap < np || !s->d_pairs) {
-            PA_CK(pd_realloc(&s->d_pairs, np));
-            PA_CK(pd_realloc(&s->d_out, 2 * np));
-            s->pair_cap = np;
-        }
-        if (s->wave_cap < waves.size() || !s->d_waves) {
-            PA_CK(pd_realloc(&s->d_waves, waves.size()));
-            s->wave_cap = waves.size();
-        }
-        if (s->scratch_cap < soff || !s->d_scratch) {
-            PA_CK(pd_realloc(&s->d_scratch, soff));
-            s->scratch_cap = std::max<size_t>(soff, 1);
-        }
-        if (s->trace_cap < toff || !s->d_pm) {
-            PA_CK(pd_realloc(&s->d_pm, toff));
-            PA_CK(pd_realloc(&s->d_sc, toff));
-            s->trace_cap = std::max<size_t>(toff, 1);
-        }
-        if (s->ops_cap < roff || !s->d_ops) {
-            PA_CK(pd_realloc(&s->d_ops, roff));
-            s->ops_cap = std::max<size_t>(roff, 1);
-        }
-        PA_CK(hipMemcpyAsync(s->d_pairs, pairs.data(), np * sizeof(PaPair), hipMemcpyHostToDevice,
-                             st));
-        PA_CK(hipMemcpyAsync(s->d_waves, waves.data(), waves.size() * sizeof(PdWave),
-                             hipMemcpyHostToDevice, st));
-        PA_CK(bounds_reset(c, st));
         PaArgs A;
-        A.pk.seq = c->d_seq;
-        A.pk.nmask = c->d_nmask;
-        A.pk.bd = make_bounds(c, kKerPairalign);
-        A.offs = c->d_offs;
-        A.lens = c->d_lens;
-        A.pairs = s->d_pairs;
-        A.waves = s->d_waves;
-        A.n_waves = (uint32_t)waves.size();
-        A.n_pairs = (uint32_t)np;
-        A.scratch = s->d_scratch;
-        A.scratch_bytes = s->scratch_cap;
-        A.pm = s->d_pm;
-        A.sc = s->d_sc;
-        A.trace_steps = s->trace_cap;
-        A.ops = s->d_ops;
-        A.ops_bytes = s->ops_cap;
-        A.out = s->d_out;
-        const uint32_t nb = (A.n_waves + kPdWavesPerBlock - 1u) / kPdWavesPerBlock;
-        PA_CK(hipEventRecord(s->ev[0], st));
-        hipLaunchKernelGGL(pairalign_kernel, dim3(nb), dim3(64 * kPdWavesPerBlock), 0, st, A);
-        PA_CK(hipGetLastError());
-        PA_CK(hipEventRecord(s->ev[1], st));
+        if (const int rc = pd_stage(c, who, *s, pl, 2 * np, kKerPairalign, A)) return rc;
+        PD_CK(who, s->pm.reserve(pl.trace));
+        PD_CK(who, s->sc.reserve(pl.trace));
+        PD_CK(who, s->ops.reserve(pl.ops));
+        A.pm = s->pm.p;
+        A.sc = s->sc.p;
+        A.trace_steps = std::min(s->pm.cap, s->sc.cap);
+        A.ops = s->ops.p;
+        A.ops_bytes = s->ops.cap;
+        A.out = s->out.p;
+        PD_CK(who, hipEventRecord(s->ev[0], st));
+        pd_launch_forward(pairalign_kernel, A, st);
+        PD_CK(who, hipGetLastError());
+        PD_CK(who, hipEventRecord(s->ev[1], st));
         set_kid(A.pk.bd, kKerPairalignTb);
         hipLaunchKernelGGL(pairalign_traceback_kernel, dim3((A.n_pairs + kPaTbLanes - 1u) / kPaTbLanes),
                            dim3(kPaTbLanes), 0, st, A);
-        PA_CK(hipGetLastError());
-        PA_CK(hipEventRecord(s->ev[2], st));
+        PD_CK(who, hipGetLastError());
+        PD_CK(who, hipEventRecord(s->ev[2], st));
         res.resize(2 * np);
-        region.resize(roff);
-        PA_CK(hipMemcpyAsync(res.data(), s->d_out, 2 * np * 4, hipMemcpyDeviceToHost, st));
-        PA_CK(hipMemcpyAsync(region.data(), s->d_ops, roff, hipMemcpyDeviceToHost, st));
-        PA_CK(hipStreamSynchronize(st));
-        if (const int brc = bounds_check(c, "dmx_pairalign")) return brc;
+        region.resize(pl.ops);
+        PD_CK(who, hipMemcpyAsync(res.data(), A.out, 2 * np * 4, hipMemcpyDeviceToHost, st));
+        PD_CK(who, hipMemcpyAsync(region.data(), A.ops, pl.ops, hipMemcpyDeviceToHost, st));
+        PD_CK(who, hipStreamSynchronize(st));
+        if (const int brc = bounds_check(c, who)) return brc;
         float ms = 0.f;
         hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
         ms_fwd += ms;
@@ -1008,7 +873,7 @@ extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, c
         ++s->launches;
         // the chunk's paths in the caller's pair order: pair lo + x ran at sorted place[x]
         place.resize(np);
-        for (size_t k = 0; k < np; ++k) place[(size_t)(keys[k] & 0xFFFFFFu)] = (uint32_t)k;
+        for (size_t k = 0; k < np; ++k) place[pl.place(k)] = (uint32_t)k;
         for (size_t x = 0; x < np; ++x) {
             const size_t k = place[x];
             const uint32_t m = lens[q[lo + x]], n = lens[t[lo + x]];
@@ -1021,7 +886,7 @@ extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, c
             }
             dist[lo + x] = res[2 * k];
             op_off[lo + x] = at;
-            std::memcpy(ops + at, region.data() + pairs[k].roff + (m + n - len), len);
+            std::memcpy(ops + at, region.data() + pl.pairs[k].roff + (m + n - len), len);
             at += len;
         }
         lo = hi;

@@ -104,6 +104,9 @@ def test_boundary_lengths_both_ways_round(ctx, boundary):
         assert len(d) == 0, (int(p.lengths[q[i]]), int(p.lengths[t[i]]), int(flags[i]),
                              "first differing op", int(d[0]), "of", len(a))
     same(got, host)
+    # the distance form of the one forward pass agrees with the trace form at every group size,
+    # at the stripe boundaries and under RC
+    np.testing.assert_array_equal(ctx.pairdist(q, t, lib.PD_NW, flags), got[0])
     # counts of 0 and 1, repeated and unordered pairs
     d, off, ops = ctx.pairalign([], [])
     assert len(d) == 0 and off.tolist() == [0] and len(ops) == 0
