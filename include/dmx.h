@@ -304,7 +304,8 @@ int dmx_chop_stats(dmx_ctx* ctx, float* ms, int n_ms);
  * calls it for every pair process_list() makes (mode 'NW', repeated on the reverse complement
  * when the forward identity is below 0.5), and the 'HW' comparisons of finetune() (:840-852).
  * edlib is not vendored; edit distance has one right answer, so parity is pinned by a
- * full-matrix DP (dmx_pairdist_host).  Clustering and consensus building are not replaced.
+ * full-matrix DP (dmx_pairdist_host).  Clustering is not replaced; the alignments of consensus
+ * building are dmx_groupalign's, below.
  * Runs on the batch made resident by dmx_load.  Symbols: A, C, G, T and the no-match mask as a
  * fifth symbol (edlib compares bytes, so N equals N and nothing else).
  * DMX_PD_NW: Levenshtein distance of the two whole reads.  DMX_PD_HW: the least edit distance
@@ -339,9 +340,10 @@ int dmx_pairdist_group_sizes(int* out, int cap);
 /* ---- Global alignment with the edit path ----------------------------------------
  * The GPU counterpart of edlib.align(q, t, mode='NW', task='path'), which create_alignment()
  * of amplicon_sorter.py (:333-339) runs for every read of every group it builds a consensus
- * of.  The consensus loop itself is NOT replaced (its alignments are sequential and their
- * targets carry gaps: DESIGN.md §8f).  Alphabet, equality, DMX_PD_RC, the length limits and
- * the argument checks are dmx_pairdist's; additionalEqualities is not supported.
+ * of.  This entry point aligns resident reads against resident reads; the loop itself, whose
+ * alignments are sequential within a group and whose targets carry gaps, is dmx_groupalign
+ * below.  Alphabet, equality, DMX_PD_RC, the length limits and the argument checks are
+ * dmx_pairdist's; additionalEqualities is not supported here (dmx_groupalign's masks carry it).
  * The query is the rows, the target the columns (edlib's orientation); ops carry edlib's
  * numbering.  An INSERT is a step up (a gap in the target), a DELETE a step left (a gap in
  * the query).  The distance has one right answer, a path has not, so the tie rule is part of
@@ -374,6 +376,58 @@ float dmx_pairalign_ms(dmx_ctx* ctx);  /* device time of both kernels, last dmx_
 /* ms[0] = the forward pass, ms[1] = the traceback of the last dmx_pairalign (first n_ms
  * written); returns the number of launches the pair list was cut into. */
 int dmx_pairalign_stats(dmx_ctx* ctx, float* ms, int n_ms);
+
+/* ---- Progressive alignment of read groups ---------------------------------------
+ * The loop of create_alignment() (amplicon_sorter.py:324-356) as create_consensus() (:358-441)
+ * runs it: row 0 of a group is a consensus, member k is aligned (NW, path, the tie rule above)
+ * against row 0 as it stands, and every column the member inserts becomes a '-' column of row 0
+ * and of every earlier row.  The caller only ever reads per-column symbol counts (:372-384), so
+ * no rows are kept: per column of the final row 0, the result is its mask, how many members
+ * showed each symbol there, and which member did first.
+ * A row is one mask byte per column: bit c (0..4 = A, C, G, T, masked/N) is set iff the column
+ * equals query symbol c; bits 5..7 must be 0.  '-' is 0 (it equals nothing, and stepping over
+ * it costs 1 like any edit), A/C/G/T/N are single bits, and the additionalEqualities of
+ * :334-339 are R = A|G, Y = C|T, M = A|C, K = G|T, S = G|C, W = A|T.
+ * Group g: its seed row is seed_masks[seed_off[g] .. seed_off[g + 1]), its members the resident
+ * reads members[member_off[g] .. member_off[g + 1]) in alignment order (a read may be a member
+ * of several groups; a group may have none, its seed row then comes back with zero counts).
+ * max_cols caps any row's length (0 = DMX_PD_MAX_LEN).  Out, per group g, columns
+ * col_off[g] .. col_off[g + 1) of the final row: mask[col], count[5 col + c] (members showing
+ * symbol c; row 0's own symbol is not counted) and first[5 col + c] (the 1-based place in the
+ * group of the first member that showed c, 0 = none).  cols_cap (entries of mask; count and
+ * first hold 5 per column) must be at least the sum over the groups of
+ * min(max_cols, seed length + member lengths).  dist[member_off[g] + k - member_off[0]] is the
+ * distance of member k's alignment.  ops may be NULL; otherwise member x's path against the
+ * row it met is ops[op_off[x] .. op_off[x + 1]) in member order, and ops_cap must be at least
+ * the sum over the members of the bound of the row they leave behind (DMX_E_INVALID otherwise).
+ * Runs in lock-step rounds: round k aligns member k of every group that has one (forward pass,
+ * traceback, merge into the group's next row), as many launches per round as keep the trace
+ * under DMX_PA_TRACE_MB; the results do not depend on the split.  Everything is checked on the
+ * host before anything is launched, naming the group: DMX_E_INVALID for a null argument, a
+ * member outside the batch, a mask byte with bits 5..7 set or too small an output;
+ * DMX_E_UNSUPPORTED for a member of 0 or more than DMX_PD_MAX_LEN nt, a seed outside
+ * 1..max_cols columns, max_cols above DMX_PD_MAX_LEN, more than 65535 members, and, during
+ * the run, a row that would grow past max_cols (naming group and round; the outputs are then
+ * undefined and the context stays usable).  Synchronous. */
+int dmx_groupalign(dmx_ctx* ctx, size_t n_groups, const uint8_t* seed_masks,
+                   const uint64_t* seed_off, const uint32_t* members, const uint64_t* member_off,
+                   uint32_t max_cols, uint64_t* col_off, uint8_t* mask, uint16_t* count,
+                   uint16_t* first, size_t cols_cap, uint32_t* dist, uint64_t* op_off,
+                   uint8_t* ops, size_t ops_cap);
+/* Host only (no GPU; tests, CPU baseline): the same contract on a dmx_pack layout, group after
+ * group and member after member: a full-matrix DP with the equality (mask[j] >> symbol) & 1,
+ * the tie rule applied literally, the merge in plain loops.  Errors: dmx_last_error(NULL). */
+int dmx_groupalign_host(const uint32_t* seq2b, const uint32_t* nmask, const uint64_t* offsets,
+                        const uint32_t* lens, size_t n_reads, size_t n_groups,
+                        const uint8_t* seed_masks, const uint64_t* seed_off,
+                        const uint32_t* members, const uint64_t* member_off, uint32_t max_cols,
+                        uint64_t* col_off, uint8_t* mask, uint16_t* count, uint16_t* first,
+                        size_t cols_cap, uint32_t* dist, uint64_t* op_off, uint8_t* ops,
+                        size_t ops_cap, int n_threads);
+/* ms[0] = the forward passes, ms[1] = the tracebacks, ms[2] = the merges of the last
+ * dmx_groupalign (first n_ms written); *rounds (may be NULL) = its lock-step rounds; returns
+ * the number of launches of each kernel. */
+int dmx_groupalign_stats(dmx_ctx* ctx, float* ms, int n_ms, int* rounds);
 
 #ifdef __cplusplus
 }

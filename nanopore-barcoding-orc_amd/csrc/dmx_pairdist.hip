@@ -16,11 +16,19 @@
 // last-row score per column, and a second kernel that walks the edit path back through it
 // (pairalign_traceback_kernel).
 //
-// Both forms share one forward pass (pd_forward: pairdist_kernel and pairalign_kernel are its two
-// instantiations, told apart at compile time by their argument struct) and one host path: the
-// chunk planner (pd_plan: chunk limits, sort, wave packing, pair records), the staging of a
-// launch (pd_stage: buffers, upload, the arguments both kernels take) and the buffers themselves
-// (PdBufs).  A change to the block step, the stripes or the planner is made once.
+// dmx_groupalign (the loop of create_alignment, :324-356, as create_consensus
+// runs it for every group) aligns member k of every group against the group's current row 0 in
+// lock-step rounds.  Row 0 is not a read but a row of equality masks (one byte per column, bit c
+// = the column equals query symbol c, 0 = a gap); the forward pass and the traceback are the
+// trace form's, and a third kernel (groupalign_merge_kernel) lays the path over the row: the new
+// row's masks and, per column, how many members showed each symbol and which member did first.
+//
+// All forms share one forward pass (pd_forward: pairdist_kernel, pairalign_kernel and
+// groupalign_kernel are its instantiations, told apart at compile time by their argument
+// struct), one traceback (pa_traceback) and one host path: the chunk planner (pd_plan: chunk
+// limits, sort, wave packing, pair records), the staging of a launch (pd_stage: buffers, upload,
+// the arguments every kernel takes) and the buffers themselves (PdBufs).  A change to the block
+// step, the stripes or the planner is made once.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +58,15 @@ struct PaPair : PdPair {
     uint64_t toff;               // its trace: word-step (wi, j) is entry toff + wi * n + j
     uint64_t roff;               // its (m + n)-byte op region
 };
+// dmx_groupalign's record: the target is a row of masks, `n` columns long now, at mask[row ..);
+// the merge writes the group's next row at mask[dst ..).  PdPair::t is the group, PdPair::cap
+// the most columns a row may have (a longer path is left unmerged and refused by the host).
+struct GaPair : PaPair {
+    uint64_t row, dst;           // columns: an index into mask, times 5 into count / first
+    uint32_t n;                  // the row's length in this round
+    uint32_t ord;                // the member's 1-based place in its group
+};
+static_assert(sizeof(GaPair) == 64, "the group form uploads 64 bytes per pair");
 struct PdWave {
     uint32_t first, count, G, steps;   // pairs[first .. first + count), one group of G lanes each
 };
@@ -80,6 +97,21 @@ struct PaArgs : PdHead<PaPair> {
     uint64_t trace_steps;        // entries of pm / sc
     uint8_t* ops;
     uint64_t ops_bytes;
+    uint32_t* out;               // per pair: distance, path length
+};
+
+// dmx_groupalign: the trace form's arguments, and the column arrays of every group's row in both
+// halves of the ping-pong (a round reads a group's row at P.row and writes the next at P.dst).
+struct GaArgs : PdHead<GaPair> {
+    ulonglong2* pm;
+    uint16_t* sc;
+    uint64_t trace_steps;
+    uint8_t* ops;
+    uint64_t ops_bytes;
+    uint8_t* mask;               // per column: the equality mask (bit c: equals query symbol c)
+    uint16_t* count;             // [column][5]: members that showed symbol c in the column
+    uint16_t* first;             // [column][5]: the first such member's place, 0 = none
+    uint64_t cols;               // columns of mask (count and first have 5 entries per column)
     uint32_t* out;               // per pair: distance, path length
 };
 
@@ -129,12 +161,27 @@ struct PaState : PdBufs<PaPair> {
     float ms[2] = {0.f, 0.f};    // forward pass, traceback
     int launches = 0;            // chunks of the last call
 };
+struct GaState : PdBufs<GaPair> {
+    DevBuf<ulonglong2> pm;
+    DevBuf<uint16_t> sc;
+    DevBuf<uint8_t> ops;
+    DevBuf<uint8_t> mask;        // both halves of every group's row
+    DevBuf<uint16_t> count, first;
+    hipEvent_t ev_merge = nullptr;   // after the merge (ev[0..2] as in the trace form)
+    float ms[3] = {0.f, 0.f, 0.f};   // forward pass, traceback, merge
+    int launches = 0, rounds = 0;
+    ~GaState() {
+        if (ev_merge) hipEventDestroy(ev_merge);
+    }
+};
 
 void pd_release(Ctx* c) {
     delete c->pd;
     delete c->pa;
+    delete c->ga;
     c->pd = nullptr;
     c->pa = nullptr;
+    c->ga = nullptr;
 }
 
 // The five match masks (A, C, G, T, N) of query rows 64 wi .. 64 wi + 63, built in registers
@@ -171,16 +218,42 @@ __device__ __forceinline__ void pd_masks(const Packed& pk, uint64_t qoff, uint32
     peq[4] = nb;
 }
 
-// The forward pass of both forms, told apart at compile time by the argument struct.
+// Where a pair's target lies: a read of the batch, or for dmx_groupalign the group's row.
+template <class Pair>
+__device__ __forceinline__ bool pd_target_ok(const Bounds& bd, const Pair& P) {
+    if constexpr (std::is_same<Pair, GaPair>::value) return true;   // P.t is a group, not a read
+    else return DMX_BOUND(bd, reads, P.t, kBufRead);
+}
+template <class Pair>
+__device__ __forceinline__ uint32_t pd_target_len(const uint32_t* lens, const Pair& P) {
+    if constexpr (std::is_same<Pair, GaPair>::value) return P.n;
+    else return lens[P.t];
+}
+template <class Pair>
+__device__ __forceinline__ uint64_t pd_target_off(const uint64_t* offs, const Pair& P) {
+    if constexpr (std::is_same<Pair, GaPair>::value) return P.row;
+    else return offs[P.t];
+}
+
+// The forward pass of every form, told apart at compile time by the argument struct.
 // PdArgs, the distance: NW or HW (A.mode); only the lane of the query's last word follows the
 // score (and, for HW, its minimum over the columns); out[k] = the distance, clamped by the cap.
 // PaArgs, the trace (dmx_pairalign's forward pass): NW; every live lane follows D(r, j) of its
 // word's last row r = min(64 (wi + 1), m) and leaves Pv, Mv and that score of every column in
 // the pair's trace at [wi][j] (a lane writes consecutive entries over time); out[2 k] = the
 // distance.
+// GaArgs, the trace against a row of masks (dmx_groupalign's forward pass): as PaArgs, but the
+// target is P.n mask bytes at A.mask[P.row ..), the group's first lane loads 16 of them per 16
+// columns, and the value that travels down the lanes carries the mask, not a symbol; Eq is the
+// OR of the peq[c] whose bit is set (a gap column, mask 0, equals nothing).
+// Every branch on the form is `if constexpr`: an instantiation holds no instruction of another.
+// That is a constraint, not a style: pairdist_kernel and pairalign_kernel are sensitive to where
+// their loop lands in the code, so a new form must leave their instructions as
+// they are (compare the assembly of both before and after).
 template <class Args>
 __device__ __forceinline__ void pd_forward(const Args& A) {
-    constexpr bool kTrace = std::is_same<Args, PaArgs>::value;
+    constexpr bool kRow = std::is_same<Args, GaArgs>::value;
+    constexpr bool kTrace = std::is_same<Args, PaArgs>::value || kRow;
     const uint32_t wave = blockIdx.x * kPdWavesPerBlock + (threadIdx.x >> 6);
     if (wave >= A.n_waves) return;   // whole waves leave: the shift below sees full waves
     const uint32_t lane = threadIdx.x & 63u;
@@ -195,11 +268,11 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
     uint64_t qoff = 0, toff = 0, soff = 0, trace = 0;
     if (active) {
         const auto P = A.pairs[W.first + g];
-        if (DMX_BOUND(A.pk.bd, reads, P.q, kBufRead) && DMX_BOUND(A.pk.bd, reads, P.t, kBufRead)) {
+        if (DMX_BOUND(A.pk.bd, reads, P.q, kBufRead) && pd_target_ok(A.pk.bd, P)) {
             m = A.lens[P.q];
-            n = A.lens[P.t];
+            n = pd_target_len(A.lens, P);
             qoff = A.offs[P.q];
-            toff = A.offs[P.t];
+            toff = pd_target_off(A.offs, P);
             rc = P.flags & DMX_PD_RC;
             soff = P.soff;
             if constexpr (kTrace) {
@@ -219,6 +292,7 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
     uint64_t peq[5] = {0, 0, 0, 0, 0};
     uint64_t Pv = 0, Mv = 0, tbase = 0;
     uint32_t s = 0, ts = 0, pass = 0, codes = 0, nbits = 0, wi = 0, hb = 63;
+    uint32_t row2 = 0, row3 = 0;   // kRow: mask bytes 8..15 of the 16 in flight (codes, nbits: 0..7)
     bool last = false, live = false;
     int score = 0, best = 0;
 
@@ -243,9 +317,21 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
                         // above's, and the target symbol
             uint32_t sym = 0, hin1 = 1;
             if (ts < n) {
-                if ((ts & 15u) == 0u) fetch16(A.pk, toff, n, rc, 0u, ts, codes, nbits);
                 const uint32_t k = ts & 15u;
-                sym = ((nbits >> k) & 1u) ? 4u : ((codes >> (2u * k)) & 3u);
+                if constexpr (kRow) {
+                    if (k == 0u) {   // rows start at multiples of 16 columns and are padded to one
+                        const uint64_t ri = toff + ts;
+                        uint4 v = make_uint4(0, 0, 0, 0);
+                        if (bchk(A.pk.bd, (int64_t)ri + 15, 15, (int64_t)A.cols, kBufGaCols))
+                            v = *reinterpret_cast<const uint4*>(A.mask + ri);
+                        codes = v.x, nbits = v.y, row2 = v.z, row3 = v.w;
+                    }
+                    const uint32_t wd = k < 4u ? codes : k < 8u ? nbits : k < 12u ? row2 : row3;
+                    sym = (wd >> (8u * (k & 3u))) & 31u;
+                } else {
+                    if (k == 0u) fetch16(A.pk, toff, n, rc, 0u, ts, codes, nbits);
+                    sym = ((nbits >> k) & 1u) ? 4u : ((codes >> (2u * k)) & 3u);
+                }
                 if (s == 0) {
                     hin1 = nw ? 2u : 1u;   // D(0, j) = j, or 0 in HW
                 } else {
@@ -260,8 +346,15 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
         if (live && j < n) {
             const uint32_t sym = recv >> 2;
             const int hin = (int)(recv & 3u) - 1;
-            uint64_t Eq = sym == 0 ? peq[0] : sym == 1 ? peq[1] : sym == 2 ? peq[2]
-                        : sym == 3 ? peq[3] : peq[4];
+            uint64_t Eq;
+            if constexpr (kRow) {
+                Eq = ((sym & 1u) ? peq[0] : 0ull) | ((sym & 2u) ? peq[1] : 0ull) |
+                     ((sym & 4u) ? peq[2] : 0ull) | ((sym & 8u) ? peq[3] : 0ull) |
+                     ((sym & 16u) ? peq[4] : 0ull);
+            } else {
+                Eq = sym == 0 ? peq[0] : sym == 1 ? peq[1] : sym == 2 ? peq[2]
+                   : sym == 3 ? peq[3] : peq[4];
+            }
             const uint64_t hneg = hin < 0 ? 1ull : 0ull, hpos = hin > 0 ? 1ull : 0ull;
             const uint64_t Xv = Eq | Mv;
             Eq |= hneg;
@@ -312,6 +405,7 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
 
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs A) { pd_forward(A); }
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairalign_kernel(PaArgs A) { pd_forward(A); }
+__global__ __launch_bounds__(64 * kPdWavesPerBlock) void groupalign_kernel(GaArgs A) { pd_forward(A); }
 
 // dmx_pairalign's traceback: one lane per pair walks back from (m, n), preferring up (INSERT),
 // then left (DELETE), then the diagonal (include/dmx.h).  Bit b of a word's Pv / Mv at column j
@@ -319,14 +413,16 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairalign_kernel(PaArgs
 // the word's score at column j - 1 minus the vertical deltas of the rows below i.  Column j of
 // the matrix is trace column j - 1; D(i, 0) = i needs no trace.  Op k goes to
 // region[m + n - 1 - k]: the path ends up in forward order at the region's tail.
+// The walk reads no sequence: m, n, the trace and the distance are all it needs, so the group
+// form (GaArgs) differs only in where n comes from (the record, not a read's length).
 constexpr uint32_t kPaTbLanes = 64;
-__global__ __launch_bounds__(kPaTbLanes) void pairalign_traceback_kernel(PaArgs A) {
+template <class Args>
+__device__ __forceinline__ void pa_traceback(const Args& A) {
     const uint32_t k = blockIdx.x * kPaTbLanes + threadIdx.x;
     if (k >= A.n_pairs) return;
-    const PaPair P = A.pairs[k];
-    if (!(DMX_BOUND(A.pk.bd, reads, P.q, kBufRead) && DMX_BOUND(A.pk.bd, reads, P.t, kBufRead)))
-        return;
-    const uint32_t m = A.lens[P.q], n = A.lens[P.t];
+    const auto P = A.pairs[k];
+    if (!(DMX_BOUND(A.pk.bd, reads, P.q, kBufRead) && pd_target_ok(A.pk.bd, P))) return;
+    const uint32_t m = A.lens[P.q], n = pd_target_len(A.lens, P);
     uint32_t i = m, j = n, len = 0;
     int d = (int)A.out[2u * k];
     uint64_t pos = P.roff + m + n;
@@ -382,6 +478,78 @@ __global__ __launch_bounds__(kPaTbLanes) void pairalign_traceback_kernel(PaArgs 
         ++len;
     }
     A.out[2u * k + 1u] = len;
+}
+__global__ __launch_bounds__(kPaTbLanes) void pairalign_traceback_kernel(PaArgs A) { pa_traceback(A); }
+__global__ __launch_bounds__(kPaTbLanes) void groupalign_traceback_kernel(GaArgs A) { pa_traceback(A); }
+
+// dmx_groupalign's merge: one wave per pair lays the pair's forward path over the group's row.
+// The path is taken 64 ops at a time, one op per lane; the column an op reads in the old row and
+// the query symbol it shows are its ranks among the ops that consume the target / the query: a
+// ballot, a popcount of the lanes below, and a base that runs over the chunks.  Column `col` of
+// the new row is written by the lane of op `col` alone (plain stores, no atomics: the result
+// does not depend on the order the lanes or the waves run in):
+//   mask:  the old column's for M / X / D, 0 (a gap: equals nothing) for I
+//   count: the old column's (0 for I), + 1 at the query's symbol for M / X / I
+//   first: the old column's; the member's place where its symbol's count was 0
+// A path longer than the row may become (P.cap) is left unmerged: the host refuses the call.
+constexpr uint32_t kGaMergeWaves = 4;
+__global__ __launch_bounds__(64 * kGaMergeWaves) void groupalign_merge_kernel(GaArgs A) {
+    const uint32_t k = blockIdx.x * kGaMergeWaves + (threadIdx.x >> 6);
+    if (k >= A.n_pairs) return;   // whole waves leave: the ballots below see full waves
+    const uint32_t lane = threadIdx.x & 63u;
+    const GaPair P = A.pairs[k];
+    if (!DMX_BOUND(A.pk.bd, reads, P.q, kBufRead)) return;
+    const uint32_t m = A.lens[P.q], n = P.n, len = A.out[2u * k + 1u];
+    if (len > P.cap || len > m + n || len < max(m, n)) return;
+    const uint64_t qoff = A.offs[P.q];
+    const uint64_t start = P.roff + (m + n - len);
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t tbase = 0, qbase = 0;
+    for (uint32_t c0 = 0; c0 < len; c0 += 64u) {
+        const uint32_t col = c0 + lane;
+        const bool in = col < len;
+        uint32_t op = DMX_PA_DELETE;
+        if (in && bchk(A.pk.bd, (int64_t)(start + col), 0, (int64_t)A.ops_bytes, kBufPaOps))
+            op = A.ops[start + col];
+        const bool takes_t = in && op != DMX_PA_INSERT, takes_q = in && op != DMX_PA_DELETE;
+        const uint64_t bt = __ballot(takes_t), bq = __ballot(takes_q);
+        if (in) {
+            uint32_t mk = 0;
+            uint16_t cnt[5] = {0, 0, 0, 0, 0}, fst[5] = {0, 0, 0, 0, 0};
+            if (takes_t) {
+                const uint64_t src = P.row + tbase + (uint32_t)__popcll(bt & below);
+                if (bchk(A.pk.bd, (int64_t)src, 0, (int64_t)A.cols, kBufGaCols)) {
+                    mk = A.mask[src];
+#pragma unroll
+                    for (int c = 0; c < 5; ++c) {
+                        cnt[c] = A.count[5u * src + c];
+                        fst[c] = A.first[5u * src + c];
+                    }
+                }
+            }
+            if (takes_q) {
+                const int64_t g = (int64_t)qoff + qbase + (uint32_t)__popcll(bq & below);
+                const uint32_t sym = (mask32(A.pk, g) & 1u) ? 4u : (code32(A.pk, g) & 3u);
+#pragma unroll
+                for (int c = 0; c < 5; ++c)
+                    if (sym == (uint32_t)c) {
+                        if (cnt[c] == 0) fst[c] = (uint16_t)P.ord;
+                        ++cnt[c];
+                    }
+            }
+            const uint64_t dst = P.dst + col;
+            if (bchk(A.pk.bd, (int64_t)dst, 0, (int64_t)A.cols, kBufGaCols)) {
+                A.mask[dst] = (uint8_t)mk;
+#pragma unroll
+                for (int c = 0; c < 5; ++c) {
+                    A.count[5u * dst + c] = cnt[c];
+                    A.first[5u * dst + c] = fst[c];
+                }
+            }
+        }
+        tbase += (uint32_t)__popcll(bt);
+        qbase += (uint32_t)__popcll(bq);
+    }
 }
 
 }  // namespace dmx
@@ -499,8 +667,10 @@ uint32_t pd_dp(int mode, const std::vector<uint8_t>& a, const std::vector<uint8_
 
 // The whole (m + 1) x (n + 1) matrix, then the walk back from (m, n) by the contract's rule:
 // up (INSERT) before left (DELETE) before the diagonal.  The ops come out last first in `rev`.
+// eq(x, y): does query symbol x equal target entry y (a symbol, or dmx_groupalign's mask)?
+template <class Eq>
 uint32_t pa_dp_path(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b,
-                    std::vector<uint16_t>& D, std::vector<uint8_t>& rev) {
+                    std::vector<uint16_t>& D, std::vector<uint8_t>& rev, Eq eq) {
     const size_t m = a.size(), n = b.size(), W = n + 1;
     D.resize((m + 1) * W);
     for (size_t j = 0; j <= n; ++j) D[j] = (uint16_t)j;
@@ -510,7 +680,7 @@ uint32_t pa_dp_path(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b
         row[0] = (uint16_t)i;
         const uint8_t ai = a[i - 1];
         for (size_t j = 1; j <= n; ++j) {
-            const uint32_t sub = up[j - 1] + (ai == b[j - 1] ? 0u : 1u);
+            const uint32_t sub = up[j - 1] + (eq(ai, b[j - 1]) ? 0u : 1u);
             row[j] = (uint16_t)std::min<uint32_t>(sub, std::min<uint32_t>(up[j], row[j - 1]) + 1u);
         }
     }
@@ -526,7 +696,7 @@ uint32_t pa_dp_path(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b
         } else if (D[i * W + j - 1] + 1u == D[i * W + j]) {
             rev.push_back(DMX_PA_DELETE), --j;
         } else {
-            rev.push_back(a[i - 1] == b[j - 1] ? DMX_PA_MATCH : DMX_PA_MISMATCH), --i, --j;
+            rev.push_back(eq(a[i - 1], b[j - 1]) ? DMX_PA_MATCH : DMX_PA_MISMATCH), --i, --j;
         }
     }
     return D[m * W + n];
@@ -578,15 +748,16 @@ struct PdPlan {
 // when their scratch rows fill kPdScratchMax or their traces (kPaTraceEntry bytes per word and
 // column) the budget; one pair at least.  The pairs are sorted by group size, then target
 // length (similar step counts share a wave), longest first, and packed into waves of one group
-// size, 64 / G groups at most.
+// size, 64 / G groups at most.  tn (dmx_groupalign): pair i's target is not read t[i] but a row
+// of tn[i] columns (t[i] is then the pair's group, and the caller fills in where the row lies).
 template <class Pair>
 size_t pd_plan(PdPlan<Pair>& pl, const uint32_t* lens, const uint32_t* q, const uint32_t* t,
                const uint8_t* flags, const uint32_t* caps, size_t n_pairs, size_t lo,
-               size_t max_pairs, size_t trace_budget) {
+               size_t max_pairs, size_t trace_budget, const uint32_t* tn = nullptr) {
     size_t hi = lo, scratch = 0, trace = 0;
     pl.keys.clear();
     while (hi < n_pairs && hi - lo < max_pairs) {
-        const uint32_t m = lens[q[hi]], n = lens[t[hi]];
+        const uint32_t m = lens[q[hi]], n = tn ? tn[hi] : lens[t[hi]];
         const size_t need = m > 64u * 64u ? n : 0;
         const size_t steps = (size_t)((m + 63u) / 64u) * n;
         if (hi > lo && (scratch + need > kPdScratchMax ||
@@ -609,7 +780,7 @@ size_t pd_plan(PdPlan<Pair>& pl, const uint32_t* lens, const uint32_t* q, const 
         PdWave W{(uint32_t)k, 0, G, 0};
         while (k < np && W.count < per && (uint32_t)(pl.keys[k] >> 48) == G) {
             const size_t i = lo + pl.place(k);
-            const uint32_t m = lens[q[i]], n = lens[t[i]];
+            const uint32_t m = lens[q[i]], n = tn ? tn[i] : lens[t[i]];
             const uint32_t mw = (m + 63u) / 64u, S = (mw + G - 1u) / G;
             Pair& P = pl.pairs[k];
             P.q = q[i];
@@ -617,10 +788,11 @@ size_t pd_plan(PdPlan<Pair>& pl, const uint32_t* lens, const uint32_t* q, const 
             P.cap = caps ? caps[i] : 0u;
             P.flags = (flags ? (flags[i] & DMX_PD_RC) : 0u) | (caps ? 0x100u : 0u);
             P.soff = pl.scratch;
-            if constexpr (std::is_same<Pair, PaPair>::value) {
+            if constexpr (std::is_base_of<PaPair, Pair>::value) {
                 P.toff = pl.trace;
                 P.roff = pl.ops;
             }
+            if constexpr (std::is_same<Pair, GaPair>::value) P.n = n;
             if (S > 1) pl.scratch += n;
             pl.trace += (size_t)mw * n;
             pl.ops += (size_t)m + n;
@@ -634,7 +806,7 @@ size_t pd_plan(PdPlan<Pair>& pl, const uint32_t* lens, const uint32_t* q, const 
 }
 
 // Stages a planned launch: room for its pairs, waves, scratch rows and out_words of output, the
-// upload, the bounds record's reset, and the arguments both forms' kernels take.
+// upload, the bounds record's reset, and the arguments every form's kernels take.
 template <class Pair>
 int pd_stage(Ctx* c, const char* who, PdBufs<Pair>& b, const PdPlan<Pair>& pl, size_t out_words,
              int kid, PdHead<Pair>& A) {
@@ -791,7 +963,7 @@ extern "C" int dmx_pairalign_host(const uint32_t* seq2b, const uint32_t* nmask,
         for (size_t i = k; i < n_pairs; i += nth) {
             pd_decode(seq2b, nmask, offsets[q[i]], lens[q[i]], false, a);
             pd_decode(seq2b, nmask, offsets[t[i]], lens[t[i]], flags && (flags[i] & DMX_PD_RC), b);
-            dist[i] = pa_dp_path(a, b, D, rev);
+            dist[i] = pa_dp_path(a, b, D, rev, [](uint8_t x, uint8_t y) { return x == y; });
             plen[i] = (uint32_t)rev.size();
             std::reverse_copy(rev.begin(), rev.end(), ops + roff[i + 1] - rev.size());
         }
@@ -894,5 +1066,393 @@ extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, c
     op_off[n_pairs] = at;
     s->ms[0] = ms_fwd;
     s->ms[1] = ms_tb;
+    return DMX_OK;
+}
+
+// ---- dmx_groupalign: progressive alignment of read groups (include/dmx.h) --------
+
+namespace {
+
+constexpr size_t kGaMaxMembers = 65535;   // count and first are 16 bits wide
+
+// What the checked arguments come to: the cap on a row, the columns a group's row may grow to
+// (its seed and every member inserted whole, the cap at most) and the sums the outputs must hold.
+struct GaShape {
+    uint32_t max_cols = 0;
+    std::vector<uint32_t> bound;   // per group
+    size_t cols = 0;               // sum of the bounds
+    size_t ops = 0;                // sum over the members of the bound of the row they leave
+    size_t members = 0, rounds = 0;
+};
+
+// Every argument check of both entry points, naming the group.  0, or the code with *err set.
+int ga_validate(const char* who, const uint32_t* lens, size_t n_reads, size_t n_groups,
+                const uint8_t* seed_masks, const uint64_t* seed_off, const uint32_t* members,
+                const uint64_t* member_off, uint32_t max_cols, size_t cols_cap, bool want_ops,
+                size_t ops_cap, GaShape& sh, std::string* err) {
+    const std::string name = std::string(who) + ": ";
+    if (max_cols > DMX_PD_MAX_LEN) {
+        *err = name + "max_cols " + std::to_string(max_cols) + " is above " +
+               std::to_string(DMX_PD_MAX_LEN);
+        return DMX_E_UNSUPPORTED;
+    }
+    sh.max_cols = max_cols ? max_cols : DMX_PD_MAX_LEN;
+    sh.bound.assign(n_groups, 0);
+    for (size_t g = 0; g < n_groups; ++g) {
+        const std::string grp = name + "group " + std::to_string(g) + ": ";
+        if (seed_off[g + 1] < seed_off[g] || member_off[g + 1] < member_off[g]) {
+            *err = grp + "offsets must not decrease";
+            return DMX_E_INVALID;
+        }
+        const uint64_t sl = seed_off[g + 1] - seed_off[g], nm = member_off[g + 1] - member_off[g];
+        if (sl < 1 || sl > sh.max_cols) {
+            *err = grp + "a seed row of " + std::to_string(sl) + " columns (1.." +
+                   std::to_string(sh.max_cols) + " supported)";
+            return DMX_E_UNSUPPORTED;
+        }
+        if (nm > kGaMaxMembers) {
+            *err = grp + std::to_string(nm) + " members (" + std::to_string(kGaMaxMembers) +
+                   " at most)";
+            return DMX_E_UNSUPPORTED;
+        }
+        for (uint64_t x = seed_off[g]; x < seed_off[g + 1]; ++x)
+            if (seed_masks[x] & 0xE0u) {
+                *err = grp + "seed column " + std::to_string(x - seed_off[g]) +
+                       " has a mask bit above the five symbols";
+                return DMX_E_INVALID;
+            }
+        uint64_t grow = sl;
+        for (uint64_t x = member_off[g]; x < member_off[g + 1]; ++x) {
+            if (members[x] >= n_reads) {
+                *err = grp + "member " + std::to_string(x - member_off[g]) +
+                       " names a read outside the batch";
+                return DMX_E_INVALID;
+            }
+            const uint32_t m = lens[members[x]];
+            if (m < 1 || m > DMX_PD_MAX_LEN) {
+                *err = grp + "member " + std::to_string(x - member_off[g]) + ": reads of 1.." +
+                       std::to_string(DMX_PD_MAX_LEN) + " nt supported";
+                return DMX_E_UNSUPPORTED;
+            }
+            grow = std::min<uint64_t>(grow + m, sh.max_cols);
+            sh.ops += grow;
+        }
+        sh.bound[g] = (uint32_t)grow;
+        sh.cols += grow;
+        sh.members += nm;
+        sh.rounds = std::max<size_t>(sh.rounds, nm);
+    }
+    if (cols_cap < sh.cols) {
+        *err = name + "cols_cap " + std::to_string(cols_cap) + " is below the " +
+               std::to_string(sh.cols) + " columns the rows may take (per group: seed and " +
+               "member lengths, max_cols at most)";
+        return DMX_E_INVALID;
+    }
+    if (want_ops && ops_cap < sh.ops) {
+        *err = name + "ops_cap " + std::to_string(ops_cap) + " is below the " +
+               std::to_string(sh.ops) + " bytes the paths may take";
+        return DMX_E_INVALID;
+    }
+    return DMX_OK;
+}
+
+std::string ga_overflow(const char* who, size_t g, size_t round, uint32_t len, uint32_t max_cols) {
+    return std::string(who) + ": group " + std::to_string(g) + ", round " + std::to_string(round) +
+           ": the row would grow to " + std::to_string(len) + " columns, above max_cols " +
+           std::to_string(max_cols);
+}
+
+// The members' paths in the caller's order, closed up.
+void ga_emit_paths(const std::vector<std::vector<uint8_t>>& paths, uint64_t* op_off, uint8_t* ops) {
+    uint64_t at = 0;
+    for (size_t x = 0; x < paths.size(); ++x) {
+        op_off[x] = at;
+        if (!paths[x].empty()) std::memcpy(ops + at, paths[x].data(), paths[x].size());
+        at += paths[x].size();
+    }
+    op_off[paths.size()] = at;
+}
+
+}  // namespace
+
+extern "C" int dmx_groupalign_stats(dmx_ctx* c, float* ms, int n_ms, int* rounds) {
+    if (!c) return DMX_E_INVALID;
+    for (int k = 0; k < n_ms && k < 3 && ms; ++k) ms[k] = c->ga ? c->ga->ms[k] : 0.f;
+    if (rounds) *rounds = c->ga ? c->ga->rounds : 0;
+    return c->ga ? c->ga->launches : 0;
+}
+
+extern "C" int dmx_groupalign_host(const uint32_t* seq2b, const uint32_t* nmask,
+                                   const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
+                                   size_t n_groups, const uint8_t* seed_masks,
+                                   const uint64_t* seed_off, const uint32_t* members,
+                                   const uint64_t* member_off, uint32_t max_cols, uint64_t* col_off,
+                                   uint8_t* mask, uint16_t* count, uint16_t* first, size_t cols_cap,
+                                   uint32_t* dist, uint64_t* op_off, uint8_t* ops, size_t ops_cap,
+                                   int n_threads) {
+    const char* const who = "dmx_groupalign_host";
+    const bool some = n_groups && member_off && member_off[n_groups] > member_off[0];
+    if (!seed_off || !member_off || !col_off || (ops && !op_off) ||
+        (n_groups && (!seed_masks || !mask || !count || !first)) ||
+        (some && (!members || !dist || !seq2b || !nmask || !offsets || !lens))) {
+        set_process_error(std::string(who) + ": null argument");
+        return DMX_E_INVALID;
+    }
+    GaShape sh;
+    std::string err;
+    if (const int rc = ga_validate(who, lens, n_reads, n_groups, seed_masks, seed_off, members,
+                                   member_off, max_cols, cols_cap, ops != nullptr, ops_cap, sh,
+                                   &err)) {
+        set_process_error(err);
+        return rc;
+    }
+    struct Cols {
+        std::vector<uint8_t> mask;
+        std::vector<uint16_t> count, first;
+    };
+    std::vector<Cols> rows(n_groups);
+    std::vector<std::vector<uint8_t>> paths(ops ? sh.members : 0);
+    std::vector<std::string> errs(n_groups);
+    const uint64_t m0 = n_groups ? member_off[0] : 0;
+    pd_parallel(n_groups, n_threads, [&](size_t k, size_t nth) {
+        std::vector<uint8_t> a, rev;
+        std::vector<uint16_t> D;
+        for (size_t g = k; g < n_groups; g += nth) {
+            Cols cur, nxt;
+            cur.mask.assign(seed_masks + seed_off[g], seed_masks + seed_off[g + 1]);
+            cur.count.assign(5 * cur.mask.size(), 0);
+            cur.first.assign(5 * cur.mask.size(), 0);
+            for (uint64_t x = member_off[g]; x < member_off[g + 1]; ++x) {
+                const size_t r = (size_t)(x - member_off[g]);
+                pd_decode(seq2b, nmask, offsets[members[x]], lens[members[x]], false, a);
+                const uint32_t d = pa_dp_path(a, cur.mask, D, rev, [](uint8_t sym, uint8_t mk) {
+                    return ((mk >> sym) & 1u) != 0;
+                });
+                const size_t len = rev.size();
+                if (len > sh.max_cols) {
+                    errs[g] = ga_overflow(who, g, r, (uint32_t)len, sh.max_cols);
+                    break;
+                }
+                dist[x - m0] = d;
+                nxt.mask.assign(len, 0);
+                nxt.count.assign(5 * len, 0);
+                nxt.first.assign(5 * len, 0);
+                size_t tj = 0, qi = 0;
+                for (size_t col = 0; col < len; ++col) {
+                    const uint8_t op = rev[len - 1 - col];
+                    if (op != DMX_PA_INSERT) {   // the old column moves here
+                        nxt.mask[col] = cur.mask[tj];
+                        for (int s = 0; s < 5; ++s) {
+                            nxt.count[5 * col + s] = cur.count[5 * tj + s];
+                            nxt.first[5 * col + s] = cur.first[5 * tj + s];
+                        }
+                        ++tj;
+                    }
+                    if (op != DMX_PA_DELETE) {   // the member shows a symbol here
+                        const uint8_t sym = a[qi++];
+                        if (nxt.count[5 * col + sym]++ == 0) nxt.first[5 * col + sym] = (uint16_t)(r + 1);
+                    }
+                }
+                if (ops) paths[x - m0].assign(rev.rbegin(), rev.rend());
+                std::swap(cur, nxt);
+            }
+            rows[g] = std::move(cur);
+        }
+    });
+    for (size_t g = 0; g < n_groups; ++g)
+        if (!errs[g].empty()) {
+            set_process_error(errs[g]);
+            return DMX_E_UNSUPPORTED;
+        }
+    uint64_t at = 0;
+    for (size_t g = 0; g < n_groups; ++g) {
+        const size_t len = rows[g].mask.size();
+        col_off[g] = at;
+        std::memcpy(mask + at, rows[g].mask.data(), len);
+        std::memcpy(count + 5 * at, rows[g].count.data(), 10 * len);
+        std::memcpy(first + 5 * at, rows[g].first.data(), 10 * len);
+        at += len;
+    }
+    col_off[n_groups] = at;
+    if (ops) ga_emit_paths(paths, op_off, ops);
+    return DMX_OK;
+}
+
+extern "C" int dmx_groupalign(dmx_ctx* c, size_t n_groups, const uint8_t* seed_masks,
+                              const uint64_t* seed_off, const uint32_t* members,
+                              const uint64_t* member_off, uint32_t max_cols, uint64_t* col_off,
+                              uint8_t* mask, uint16_t* count, uint16_t* first, size_t cols_cap,
+                              uint32_t* dist, uint64_t* op_off, uint8_t* ops, size_t ops_cap) {
+    const char* const who = "dmx_groupalign";
+    if (!c) return DMX_E_INVALID;
+    if (c->ga) {
+        c->ga->ms[0] = c->ga->ms[1] = c->ga->ms[2] = 0.f;
+        c->ga->launches = c->ga->rounds = 0;
+    }
+    const bool some = n_groups && member_off && member_off[n_groups] > member_off[0];
+    if (!seed_off || !member_off || !col_off || (ops && !op_off) ||
+        (n_groups && (!seed_masks || !mask || !count || !first)) || (some && (!members || !dist))) {
+        c->err = "dmx_groupalign: null argument";
+        return DMX_E_INVALID;
+    }
+    std::vector<uint32_t> lens;
+    if (const int rc = pd_fetch_lens(c, who, some ? 1 : 0, lens)) return rc;
+    GaShape sh;
+    if (const int rc = ga_validate(who, lens.data(), lens.size(), n_groups, seed_masks, seed_off,
+                                   members, member_off, max_cols, cols_cap, ops != nullptr, ops_cap,
+                                   sh, &c->err))
+        return rc;
+    col_off[0] = 0;
+    if (ops) op_off[0] = 0;
+    if (!n_groups) return DMX_OK;
+    if (const int rc = pd_state(c, who, c->ga)) return rc;
+    GaState* s = c->ga;
+    if (!s->ev_merge) PD_CK(who, hipEventCreate(&s->ev_merge));
+    hipStream_t st = c->stream;
+    PD_CK(who, hipSetDevice(c->device));
+    const size_t budget = pd_env("DMX_PA_TRACE_MB", kPaTraceMbDefault, (size_t)1 << 20) << 20;
+    const uint64_t m0 = member_off[0];
+
+    // every group's row has a region of its bound, padded to 16 columns (the forward pass loads
+    // 16 mask bytes at a time), at the same place in both halves of the column arrays
+    std::vector<uint64_t> goff(n_groups);
+    uint64_t total = 0;
+    for (size_t g = 0; g < n_groups; ++g) {
+        goff[g] = total;
+        total += ((uint64_t)sh.bound[g] + 15u) & ~(uint64_t)15u;
+    }
+    PD_CK(who, s->mask.reserve(2 * total));
+    PD_CK(who, s->count.reserve(10 * total));
+    PD_CK(who, s->first.reserve(10 * total));
+    std::vector<uint8_t> seed(total, 0);
+    std::vector<uint32_t> cur(n_groups), half(n_groups, 0);
+    for (size_t g = 0; g < n_groups; ++g) {
+        cur[g] = (uint32_t)(seed_off[g + 1] - seed_off[g]);
+        std::memcpy(seed.data() + goff[g], seed_masks + seed_off[g], cur[g]);
+    }
+    PD_CK(who, hipMemcpyAsync(s->mask.p, seed.data(), total, hipMemcpyHostToDevice, st));
+    PD_CK(who, hipMemsetAsync(s->count.p, 0, 5 * total * sizeof(uint16_t), st));
+    PD_CK(who, hipMemsetAsync(s->first.p, 0, 5 * total * sizeof(uint16_t), st));
+    PD_CK(who, hipStreamSynchronize(st));   // `seed` is pageable
+
+    PdPlan<GaPair> pl;
+    std::vector<uint32_t> rq, rg, rn, res;
+    std::vector<uint8_t> region;
+    std::vector<std::vector<uint8_t>> paths(ops ? sh.members : 0);
+    float ms3[3] = {0.f, 0.f, 0.f};
+    for (size_t round = 0; round < sh.rounds; ++round) {
+        // member `round` of every group that has one, against the group's row as it stands
+        rq.clear(), rg.clear(), rn.clear();
+        for (size_t g = 0; g < n_groups; ++g)
+            if (member_off[g + 1] - member_off[g] > round) {
+                rq.push_back(members[member_off[g] + round]);
+                rg.push_back((uint32_t)g);
+                rn.push_back(cur[g]);
+            }
+        const size_t n_pairs = rq.size();
+        for (size_t lo = 0; lo < n_pairs;) {
+            const size_t hi = pd_plan(pl, lens.data(), rq.data(), rg.data(), nullptr, nullptr,
+                                      n_pairs, lo, kPdChunkDefault, budget, rn.data());
+            const size_t np = hi - lo;
+            for (GaPair& P : pl.pairs) {
+                const size_t g = P.t;
+                P.row = half[g] * total + goff[g];
+                P.dst = (1u - half[g]) * total + goff[g];
+                P.ord = (uint32_t)round + 1u;
+                P.cap = sh.max_cols;
+            }
+            GaArgs A;
+            if (const int rc = pd_stage(c, who, *s, pl, 2 * np, kKerGroupalign, A)) return rc;
+            PD_CK(who, s->pm.reserve(pl.trace));
+            PD_CK(who, s->sc.reserve(pl.trace));
+            PD_CK(who, s->ops.reserve(pl.ops));
+            A.pm = s->pm.p;
+            A.sc = s->sc.p;
+            A.trace_steps = std::min(s->pm.cap, s->sc.cap);
+            A.ops = s->ops.p;
+            A.ops_bytes = s->ops.cap;
+            A.mask = s->mask.p;
+            A.count = s->count.p;
+            A.first = s->first.p;
+            A.cols = std::min(s->mask.cap, std::min(s->count.cap, s->first.cap) / 5);
+            A.out = s->out.p;
+            // a pair the kernels skip must not leave a stale length behind
+            PD_CK(who, hipMemsetAsync(A.out, 0, 2 * np * 4, st));
+            PD_CK(who, hipEventRecord(s->ev[0], st));
+            pd_launch_forward(groupalign_kernel, A, st);
+            PD_CK(who, hipGetLastError());
+            PD_CK(who, hipEventRecord(s->ev[1], st));
+            set_kid(A.pk.bd, kKerGroupalignTb);
+            hipLaunchKernelGGL(groupalign_traceback_kernel,
+                               dim3((A.n_pairs + kPaTbLanes - 1u) / kPaTbLanes), dim3(kPaTbLanes), 0,
+                               st, A);
+            PD_CK(who, hipGetLastError());
+            PD_CK(who, hipEventRecord(s->ev[2], st));
+            set_kid(A.pk.bd, kKerGroupalignMerge);
+            hipLaunchKernelGGL(groupalign_merge_kernel,
+                               dim3((A.n_pairs + kGaMergeWaves - 1u) / kGaMergeWaves),
+                               dim3(64 * kGaMergeWaves), 0, st, A);
+            PD_CK(who, hipGetLastError());
+            PD_CK(who, hipEventRecord(s->ev_merge, st));
+            res.resize(2 * np);
+            PD_CK(who, hipMemcpyAsync(res.data(), A.out, 2 * np * 4, hipMemcpyDeviceToHost, st));
+            if (ops) {
+                region.resize(pl.ops);
+                PD_CK(who, hipMemcpyAsync(region.data(), A.ops, pl.ops, hipMemcpyDeviceToHost, st));
+            }
+            PD_CK(who, hipStreamSynchronize(st));
+            if (const int brc = bounds_check(c, who)) return brc;
+            float ms = 0.f;
+            hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+            ms3[0] += ms;
+            hipEventElapsedTime(&ms, s->ev[1], s->ev[2]);
+            ms3[1] += ms;
+            hipEventElapsedTime(&ms, s->ev[2], s->ev_merge);
+            ms3[2] += ms;
+            ++s->launches;
+            for (size_t k = 0; k < np; ++k) {
+                const GaPair& P = pl.pairs[k];
+                const size_t g = P.t;
+                const uint32_t m = lens[P.q], n = P.n, len = res[2 * k + 1];
+                if (len > m + n || len < std::max(m, n)) {
+                    c->err = "dmx_groupalign: group " + std::to_string(g) + ", round " +
+                             std::to_string(round) + ": path of " + std::to_string(len) +
+                             " ops for a read of " + std::to_string(m) + " nt and a row of " +
+                             std::to_string(n) + " columns";
+                    return DMX_E_STATE;
+                }
+                if (len > sh.max_cols) {
+                    c->err = ga_overflow(who, g, round, len, sh.max_cols);
+                    return DMX_E_UNSUPPORTED;
+                }
+                const uint64_t x = member_off[g] + round - m0;
+                dist[x] = res[2 * k];
+                if (ops)
+                    paths[x].assign(region.begin() + P.roff + (m + n - len),
+                                    region.begin() + P.roff + (m + n));
+                cur[g] = len;      // the group's row of the next round: the other half
+                half[g] ^= 1u;
+            }
+            lo = hi;
+        }
+    }
+    s->rounds = (int)sh.rounds;
+    s->ms[0] = ms3[0], s->ms[1] = ms3[1], s->ms[2] = ms3[2];
+
+    uint64_t at = 0;
+    for (size_t g = 0; g < n_groups; ++g) {
+        const uint64_t src = half[g] * total + goff[g];
+        const size_t len = cur[g];
+        col_off[g] = at;
+        PD_CK(who, hipMemcpyAsync(mask + at, s->mask.p + src, len, hipMemcpyDeviceToHost, st));
+        PD_CK(who, hipMemcpyAsync(count + 5 * at, s->count.p + 5 * src, 10 * len,
+                                  hipMemcpyDeviceToHost, st));
+        PD_CK(who, hipMemcpyAsync(first + 5 * at, s->first.p + 5 * src, 10 * len,
+                                  hipMemcpyDeviceToHost, st));
+        at += len;
+    }
+    col_off[n_groups] = at;
+    PD_CK(who, hipStreamSynchronize(st));
+    if (ops) ga_emit_paths(paths, op_off, ops);
     return DMX_OK;
 }

@@ -42,7 +42,7 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_mask_exceptions", "dmx_host_register", "dmx_host_unregister", "dmx_panel_reach",
            "dmx_debug_bounds_selftest", "dmx_panel_pieces", "dmx_pairdist", "dmx_pairdist_host",
            "dmx_pairdist_group_sizes", "dmx_pairalign", "dmx_pairalign_host",
-           "dmx_pairalign_stats"]
+           "dmx_pairalign_stats", "dmx_groupalign", "dmx_groupalign_host", "dmx_groupalign_stats"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -158,6 +158,13 @@ def load() -> ctypes.CDLL:
         L.dmx_pairalign_ms.argtypes = [P]
         L.dmx_pairalign_ms.restype = ctypes.c_float
         L.dmx_pairalign_stats.argtypes = [P, ctypes.POINTER(ctypes.c_float), c_int]
+    if hasattr(L, "dmx_groupalign"):
+        ga = [c_size, P, c_u64p, P, c_u64p, ctypes.c_uint32, c_u64p, P, P, P, c_size, P, c_u64p, P,
+              c_size]
+        L.dmx_groupalign.argtypes = [P] + ga
+        L.dmx_groupalign_host.argtypes = [P, P, c_u64p, P, c_size] + ga + [c_int]
+        L.dmx_groupalign_stats.argtypes = [P, ctypes.POINTER(ctypes.c_float), c_int,
+                                           ctypes.POINTER(c_int)]
     # DMX_ALLOW_ABI=1: load an older in-tree build for a regression A/B (tools/replay_sweep.py)
     if L.dmx_abi_version() != ABI_VERSION and os.environ.get("DMX_ALLOW_ABI") != "1":
         raise DmxError("libdmx ABI mismatch")
@@ -430,6 +437,29 @@ class Context:
         n = self._check(self._L.dmx_pairalign_stats(self._h, ms, 2), "dmx_pairalign_stats")
         return {"forward": float(ms[0]), "traceback": float(ms[1]), "launches": int(n)}
 
+    # ---- progressive alignment of read groups (include/dmx.h dmx_groupalign) ----
+    def groupalign(self, seeds, groups, max_cols: int = 0, paths: bool = False) -> dict:
+        """create_alignment's loop for many groups at once: seeds[g] is group g's row 0 (str or
+        bytes over A/C/G/T/N/-/IUPAC, or a uint8 array of masks as mask_row makes them),
+        groups[g] its members (resident read indices, in alignment order).  Returns a dict:
+        col_off (uint64, n + 1), mask (uint8 per column), count and first (uint16, columns x 5:
+        members showing A/C/G/T/N in the column, and the 1-based place of the first that did),
+        dist (uint32 per member, group after group) and, with paths, op_off / ops as
+        pairalign's, one path per member against the row it met."""
+        a = _groupalign_args(getattr(self, "_lengths", None), seeds, groups, max_cols, paths)
+        self._check(self._L.dmx_groupalign(self._h, *a.call), "dmx_groupalign")
+        return a.result()
+
+    def groupalign_stats(self) -> dict:
+        """Device time (ms) of the last groupalign call by pass, its lock-step rounds and the
+        launches (of each of the three kernels) they were cut into."""
+        ms = (ctypes.c_float * 3)()
+        rounds = ctypes.c_int(0)
+        n = self._check(self._L.dmx_groupalign_stats(self._h, ms, 3, ctypes.byref(rounds)),
+                        "dmx_groupalign_stats")
+        return {"forward": float(ms[0]), "traceback": float(ms[1]), "merge": float(ms[2]),
+                "rounds": int(rounds.value), "launches": int(n)}
+
     def n_counts(self) -> int:
         a1 = 0 if self.mode == MODE_SINGLE else self.panel_sizes[1]
         return (self.panel_sizes[0] + 1) * (a1 + 1) + 2
@@ -548,6 +578,112 @@ def pairalign_host(p: "Packed", q, t, flags=None, n_threads: int = 1, ops_cap=No
         msg = L.dmx_last_error(None)
         raise DmxError(f"dmx_pairalign_host failed ({rc}): {msg.decode() if msg else ''}")
     return dist, off, ops[:int(off[-1])]
+
+
+# dmx_groupalign's row alphabet: bit c of a mask = the column equals query symbol c (A, C, G, T,
+# masked/N); '-' equals nothing; the IUPAC pairs are create_alignment's additionalEqualities
+_MASK_OF = {"-": 0, "A": 1, "C": 2, "G": 4, "T": 8, "N": 16, "R": 1 | 4, "Y": 2 | 8, "M": 1 | 2,
+            "K": 4 | 8, "S": 4 | 2, "W": 1 | 8}
+_MASK_LUT = np.full(256, 255, dtype=np.uint8)
+for _ch, _m in _MASK_OF.items():
+    _MASK_LUT[ord(_ch)] = _MASK_LUT[ord(_ch.lower())] = _m
+_SYM_LUT = np.zeros(32, dtype=np.uint8)
+for _ch in "-ACGTN":
+    _SYM_LUT[_MASK_OF[_ch]] = ord(_ch)
+
+
+def mask_row(seq) -> np.ndarray:
+    """A row of dmx_groupalign as mask bytes, from str or bytes over A/C/G/T/N, '-' and
+    R/Y/M/K/S/W (either case); anything else is refused."""
+    b = seq.encode("ascii", "replace") if isinstance(seq, str) else bytes(seq)
+    m = _MASK_LUT[np.frombuffer(b, dtype=np.uint8)]
+    bad = np.flatnonzero(m == 255)
+    if len(bad):
+        raise DmxError(f"mask_row: {chr(b[bad[0]])!r} at {int(bad[0])} is not one of "
+                       "A/C/G/T/N, '-' or R/Y/M/K/S/W")
+    return m
+
+
+def mask_symbols(mask) -> str:
+    """The row a mask array stands for, where that is one symbol per column: '-' and the
+    single-bit masks A/C/G/T/N (a mask of several bits is refused)."""
+    m = np.asarray(mask, dtype=np.uint8)
+    if m.ndim != 1 or (len(m) and int(m.max()) > 31):
+        raise DmxError("mask_symbols: a one-dimensional array of masks 0..31")
+    s = _SYM_LUT[m]
+    if (s == 0).any():
+        raise DmxError("mask_symbols: a mask of several symbols has no single letter")
+    return s.tobytes().decode()
+
+
+class _groupalign_args:
+    """The packed arguments and caller-sized outputs of dmx_groupalign(_host)."""
+
+    def __init__(self, lengths, seeds, groups, max_cols, paths, ops_cap=None, cols_cap=None):
+        if len(seeds) != len(groups):
+            raise DmxError("groupalign: one seed row per group")
+        rows = [np.ascontiguousarray(s, dtype=np.uint8) if isinstance(s, np.ndarray)
+                else mask_row(s) for s in seeds]
+        mem = [np.ascontiguousarray(g, dtype=np.uint32).reshape(-1) for g in groups]
+        n = len(rows)
+        self.seed_off = np.zeros(n + 1, dtype=np.uint64)
+        self.member_off = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            self.seed_off[1:] = np.cumsum([len(r) for r in rows])
+            self.member_off[1:] = np.cumsum([len(g) for g in mem])
+        self.seeds = np.concatenate(rows + [np.zeros(0, dtype=np.uint8)])
+        self.members = np.concatenate(mem + [np.zeros(0, dtype=np.uint32)])
+        # the library's bounds (include/dmx.h): a row grows by a member's length at most
+        nr = 0 if lengths is None else len(lengths)
+        ln = np.zeros(nr + 1, dtype=np.int64)
+        if nr:
+            ln[:nr] = lengths
+        lim = int(max_cols) if max_cols else PD_MAX_LEN
+        cols = ops = 0
+        for r, g in zip(rows, mem):
+            grow = np.minimum(len(r) + np.cumsum(ln[np.minimum(g, nr)]), lim)
+            cols += int(grow[-1]) if len(g) else min(len(r), lim)
+            ops += int(grow.sum())
+        cols = cols if cols_cap is None else int(cols_cap)
+        ops = ops if ops_cap is None else int(ops_cap)
+        self.col_off = np.zeros(n + 1, dtype=np.uint64)
+        self.mask = np.zeros(max(cols, 1), dtype=np.uint8)
+        self.count = np.zeros((max(cols, 1), 5), dtype=np.uint16)
+        self.first = np.zeros((max(cols, 1), 5), dtype=np.uint16)
+        self.dist = np.zeros(len(self.members), dtype=np.uint32)
+        self.op_off = np.zeros(len(self.members) + 1, dtype=np.uint64) if paths else None
+        self.ops = np.zeros(max(ops, 1), dtype=np.uint8) if paths else None
+        self.call = (n, self.seeds.ctypes.data, self.seed_off.ctypes.data,
+                     self.members.ctypes.data, self.member_off.ctypes.data, int(max_cols),
+                     self.col_off.ctypes.data, self.mask.ctypes.data, self.count.ctypes.data,
+                     self.first.ctypes.data, cols, self.dist.ctypes.data,
+                     self.op_off.ctypes.data if paths else None,
+                     self.ops.ctypes.data if paths else None, ops)
+
+    def result(self) -> dict:
+        n = int(self.col_off[-1])
+        out = {"col_off": self.col_off, "mask": self.mask[:n], "count": self.count[:n],
+               "first": self.first[:n], "dist": self.dist, "member_off": self.member_off}
+        if self.ops is not None:
+            out["op_off"] = self.op_off
+            out["ops"] = self.ops[:int(self.op_off[-1])]
+        return out
+
+
+def groupalign_host(p: "Packed", seeds, groups, max_cols: int = 0, paths: bool = False,
+                    n_threads: int = 1, ops_cap=None, cols_cap=None) -> dict:
+    """dmx_groupalign's contract on the host, group after group and member after member (no
+    GPU): the checker of the kernels and the CPU comparator of tools/bench_groupalign.py.
+    ops_cap, cols_cap: the room given to the library instead of its bounds (to see it refused).
+    Returns the dict of Context.groupalign."""
+    L = load()
+    a = _groupalign_args(p.lengths, seeds, groups, max_cols, paths, ops_cap, cols_cap)
+    rc = L.dmx_groupalign_host(p.seq2b.ctypes.data, p.nmask.ctypes.data, p.offsets.ctypes.data,
+                               p.lengths.ctypes.data, p.n_reads, *a.call, int(n_threads))
+    if rc < 0:
+        msg = L.dmx_last_error(None)
+        raise DmxError(f"dmx_groupalign_host failed ({rc}): {msg.decode() if msg else ''}")
+    return a.result()
 
 
 def cigar(ops, extended: bool = False) -> str:

@@ -3,17 +3,17 @@
 identity lines, restated from scripts/auxiliary_code/amplicon_sorter.py (:550-623 selection,
 :648-716 pairs, :225-235 + :777-808 identities) on top of dmx_pairdist (include/dmx.h).
 
-Clustering, species grouping and consensus building are NOT replaced: this module stops at the
-similarity lines (`i:j:iden`, `i:j:iden:reverse`) the reference's later steps read.  The random
-selection modes (-ra, -a) are out of scope.  Alphabet: A, C, G, T, N (a read with any other
-byte is refused; the reference would compare such bytes literally).
+Clustering and species grouping are NOT replaced: similarity() stops at the similarity lines
+(`i:j:iden`, `i:j:iden:reverse`) the reference's later steps read.  The random selection modes
+(-ra, -a) are out of scope.  Alphabet: A, C, G, T, N (a read with any other byte is refused;
+the reference would compare such bytes literally).
 
-gapped() restates one iteration of create_alignment (:340-355) on a path of dmx_pairalign: the
-two gapped rows a read and a fresh, ungapped consensus get.  The loop over the reads of a group
-is NOT restated: the reference aligns read k against a consensus list that has already
-received the '-' gaps of reads 0..k-1 (`z.insert(i, '-')` edits the target in place, it is
-alignlist[0]), so a group's alignments are sequential and their targets hold a symbol that is
-not in the packed batch.
+consensus() restates create_consensus (:358-428) for many groups at once on top of
+dmx_groupalign, which runs create_alignment's loop (:324-356) in lock-step
+over the groups and returns per-column symbol counts, all the consensus reads of an alignment.
+alignment_rows() rebuilds the gapped rows themselves from the returned paths (the -aln output,
+and the tests).  Out of scope: -amb (ambiguity, degenerate), the callers' random sampling and
+consensus_direction (the reads are taken as they come, already oriented).
 """
 from __future__ import annotations
 
@@ -108,7 +108,8 @@ def gapped(query, target, ops):
     and the read `query`, from the path `ops` of query against target (lib.pairalign): the
     consensus row with a '-' wherever the read inserts (I), and the read's row with a '-'
     wherever it deletes (D).  Both rows have len(ops) columns.  Returns (target_row,
-    query_row) as str."""
+    query_row) as str.  The loop over a group's reads, where read k meets a row that already
+    carries the gaps of reads 0..k-1, is alignment_rows() on the paths of lib.groupalign."""
     q = query.decode("ascii") if isinstance(query, (bytes, bytearray)) else str(query)
     t = target.decode("ascii") if isinstance(target, (bytes, bytearray)) else str(target)
     a = np.asarray(ops, dtype=np.uint8)
@@ -123,6 +124,148 @@ def gapped(query, target, ops):
     trow = np.where(takes_t, np.frombuffer((t or "-").encode(), dtype=np.uint8)[np.maximum(ti, 0)],
                     ord("-")).astype(np.uint8)
     return trow.tobytes().decode(), qrow.tobytes().decode()
+
+
+def alignment_rows(seed, reads, ops) -> list:
+    """The gapped rows of create_alignment (:324-356): row 0 is `seed` (str or bytes, '-' and
+    IUPAC allowed), row k + 1 is reads[k]; ops[k] is read k's path against row 0 as it stood
+    (a slice of groupalign's ops).  A DELETE puts '-' into the read's row; every INSERT column
+    becomes a '-' column of row 0 and of every earlier row.  Returns the rows as str, all of
+    the last path's length."""
+    def raw(x):
+        return np.frombuffer(x.encode("ascii") if isinstance(x, str) else bytes(x), dtype=np.uint8)
+    if len(reads) != len(ops):
+        raise DmxError("alignment_rows: one path per read")
+    rows = [raw(seed).copy()]
+    for r, path in zip(reads, ops):
+        a = np.asarray(path, dtype=np.uint8)
+        q = raw(r)
+        takes_q = a != lib.PA_DELETE
+        takes_t = a != lib.PA_INSERT
+        if int(takes_q.sum()) != len(q) or int(takes_t.sum()) != len(rows[0]):
+            raise DmxError("alignment_rows: a path does not span its read and the row it met")
+        for k, old in enumerate(rows):
+            new = np.full(len(a), ord("-"), dtype=np.uint8)
+            new[takes_t] = old
+            rows[k] = new
+        new = np.full(len(a), ord("-"), dtype=np.uint8)
+        new[takes_q] = q
+        rows.append(new)
+    return [x.tobytes().decode() for x in rows]
+
+
+THRESHOLDS = (0.45, 0.15, 0.5)   # create_consensus's three cycles (:365)
+_SYMS = "ACGTN"
+
+
+def _column_tops(res, g, n_rows):
+    """The kept columns of group g's alignment (:372-384): for every column whose most frequent
+    symbol is shown by more than 10 % of the rows, that symbol and its count (and the runner-up's,
+    which only -amb reads).  Row 0's own symbol counts, before any member's; ties go to the
+    symbol seen first down the rows (the reference's stable sort over dict insertion order)."""
+    lo, hi = int(res["col_off"][g]), int(res["col_off"][g + 1])
+    cnt = res["count"][lo:hi].astype(np.int64)
+    rank = res["first"][lo:hi].astype(np.int64)
+    rank[cnt == 0] = 1 << 30
+    mask = res["mask"][lo:hi]
+    for c in range(5):   # row 0 shows a symbol where its mask is that symbol's bit alone
+        own = mask == (1 << c)
+        cnt[own, c] += 1
+        rank[own, c] = 0
+    # falling count, then rising first occurrence (places are below 65536)
+    order = np.argsort(-cnt * 65536 + np.minimum(rank, 65535), axis=1, kind="stable")
+    top = order[:, 0]
+    top_n = np.take_along_axis(cnt, order[:, :1], axis=1)[:, 0]
+    keep = (top_n > 0) & (top_n > n_rows * 0.10)
+    return top[keep], top_n[keep]
+
+
+def _homopolymer_sort(top, top_n):
+    """homopolymersort (:244-257): within every run of columns with the same top symbol, the
+    columns by falling count (stable); the last run stays as it is, as in the reference."""
+    if not len(top):
+        raise DmxError("consensus: no column of the alignment is kept")
+    run = np.concatenate([[0], np.cumsum(top[1:] != top[:-1])])
+    key = np.where(run == run[-1], 0, -top_n)
+    order = np.lexsort((key, run))
+    return top[order], top_n[order]
+
+
+def _final_correction(top, top_n, c, treshold):
+    """The homopolymer correction of :394-428, literally (the entry before the first is the
+    last one; `treshold` is still the last cycle's)."""
+    out = []
+    b = 1
+    n_cols = len(top)
+    for n in range(n_cols):
+        sym, cnt = _SYMS[top[n]], int(top_n[n])
+        prev = (n - 1) % n_cols
+        if top[n] == top[prev]:
+            if sym in "AT":
+                if b >= 4:
+                    if cnt > c * 0.2:
+                        out.append(sym)
+                        b += 1
+                elif cnt > c * treshold:
+                    out.append(sym)
+                    b += 1
+            elif sym in "CG":
+                if b >= 3:
+                    if int(top_n[prev]) * 0.5 < cnt > c * 0.2:
+                        out.append(sym)
+                        b += 1
+                elif cnt > c * treshold:
+                    out.append(sym)
+                    b += 1
+        elif cnt > c * treshold:
+            out.append(sym)
+            b = 1
+    return "".join(out)
+
+
+def consensus(ctx, reads, groups, ambiguous: bool = False, n_threads: int = 16) -> list:
+    """create_consensus (:358-428) for many groups at once: `groups` are lists of indices into
+    `reads` (str or bytes over A/C/G/T/N, already oriented).  Per group: a stable sort by
+    falling length, the longest read seeds cycle 1 and the others are aligned against it;
+    cycles 2 and 3 align every read, the seed included, against the previous cycle's
+    consensus.  Every group of the call goes into each of the three groupalign calls.  ctx: a
+    Context, or None to run on the host reference (lib.groupalign_host, n_threads).  Returns
+    the consensus strings, one per group."""
+    if ambiguous:
+        raise DmxError("consensus: -amb (ambiguity, degenerate) is not supported")
+    seqs = _clean(reads)
+    ln = np.array([len(s) for s in seqs], dtype=np.int64)
+    if len(ln) and int(ln.max()) > lib.PD_MAX_LEN:
+        raise DmxError(f"a read is longer than {lib.PD_MAX_LEN} nt")
+    orders = []
+    for k, g in enumerate(groups):
+        g = np.asarray(g, dtype=np.int64).reshape(-1)
+        if not len(g):
+            raise DmxError(f"consensus: group {k} has no reads")
+        orders.append(g[np.argsort(-ln[g], kind="stable")])
+    if not orders:
+        return []
+    blob = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+    offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
+    p = lib.pack(blob, offs, ln.astype(np.uint32))
+    if ctx is not None:
+        ctx.load(p)
+    seeds = [seqs[o[0]] for o in orders]
+    members = [o[1:] for o in orders]
+    tops = []
+    for treshold in THRESHOLDS:
+        res = (ctx.groupalign(seeds, members) if ctx is not None
+               else lib.groupalign_host(p, seeds, members, n_threads=n_threads))
+        tops, seeds = [], []
+        for k, mem in enumerate(members):
+            c = len(mem) + 1
+            top, top_n = _homopolymer_sort(*_column_tops(res, k, c))
+            tops.append((top, top_n, c))
+            seeds.append("".join(_SYMS[x] for x in top[top_n > c * treshold]))
+            if not seeds[-1]:
+                raise DmxError(f"consensus: group {k}: no column passes the threshold")
+        members = orders   # the full list from the second cycle on
+    return [_final_correction(top, top_n, c, THRESHOLDS[-1]) for top, top_n, c in tops]
 
 
 def _clean(reads) -> list:

@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Device time of dmx_groupalign on the shape make_consensus feeds create_consensus
+(amplicon_sorter.py:1227-1240): synthetic families (dmx.synth.amplicon_bin, about 1,200 nt) cut
+into --groups groups of --per reads, cycle 1 only (the longest read of a group seeds it, the
+others are aligned against the growing row in lock-step rounds).  Reported: rounds, launches,
+the device time of the three passes (forward trace, traceback, merge) and which dominates,
+alignments per second, the final row lengths, and, rerun in the same session, dmx_pairalign on
+the same number of pairs of the same reads (every member against its group's seed read: the
+ungapped first round, tools/bench_pairalign.py's procedure) for the per-alignment time next to
+it.  The CPU comparator is dmx_groupalign_host (the project's sequential full-matrix DP, NOT
+edlib) on 16 threads over --cpu-groups groups; its columns are checked against the GPU's.
+Medians of --reps calls after --warmup.  Writes one JSON record."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                "nanopore-barcoding-orc_amd"))
+from dmx import lib, synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--groups", type=int, default=256)
+    ap.add_argument("--per", type=int, default=50)
+    ap.add_argument("--families", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--cpu-groups", type=int, default=16)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    reads, seeds, groups, seed_idx = [], [], [], []
+    gpf = (a.groups + a.families - 1) // a.families
+    for f in range(a.families):
+        fam = [r.encode() for r in synth.amplicon_bin(gpf * a.per, 1, (1150, 1250), (0.03, 0.12),
+                                                      0.0, seed=190 + f)]
+        for k in range(gpf):
+            if len(groups) == a.groups:
+                break
+            base = len(reads)
+            g = fam[k * a.per:(k + 1) * a.per]
+            order = np.argsort([-len(r) for r in g], kind="stable")
+            reads += g
+            seeds.append(g[order[0]])
+            seed_idx.append(base + int(order[0]))
+            groups.append([base + int(i) for i in order[1:]])
+    ln = np.array([len(r) for r in reads], dtype=np.int64)
+    blob = np.frombuffer(b"".join(reads), dtype=np.uint8)
+    offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
+    p = lib.pack(blob, offs, ln.astype(np.uint32))
+    n_align = sum(len(g) for g in groups)
+    # the same pairs for dmx_pairalign: every member against its group's seed read
+    pq = np.array([i for g in groups for i in g], dtype=np.uint32)
+    pt = np.repeat(np.array(seed_idx, dtype=np.uint32), [len(g) for g in groups])
+    rec = {"tool": "bench_groupalign", "groups": len(groups), "reads_per_group": a.per,
+           "families": a.families, "mean_len": float(ln.mean()), "alignments": int(n_align),
+           "cycle": "1 of 3 (seed = the group's longest read)"}
+    with lib.Context(a.device) as ctx:
+        ctx.load(p)
+        fwd, tb, mg, wall, pa, pf, pt_ms = [], [], [], [], [], [], []
+        for i in range(a.warmup + a.reps):
+            t0 = time.perf_counter()
+            res = ctx.groupalign(seeds, groups)
+            w = time.perf_counter() - t0
+            st = ctx.groupalign_stats()
+            ctx.pairalign(pq, pt)
+            ps = ctx.pairalign_stats()
+            if i >= a.warmup:
+                fwd.append(st["forward"])
+                tb.append(st["traceback"])
+                mg.append(st["merge"])
+                wall.append(w * 1e3)
+                pa.append(ctx.pairalign_ms())
+                pf.append(ps["forward"])
+                pt_ms.append(ps["traceback"])
+        passes = {"forward trace": float(np.median(fwd)), "traceback": float(np.median(tb)),
+                  "merge": float(np.median(mg))}
+        dev = sum(passes.values())
+        rows = np.diff(res["col_off"].astype(np.int64))
+        rec.update({"rounds": st["rounds"], "launches": st["launches"],
+                    "forward_ms_median": passes["forward trace"],
+                    "traceback_ms_median": passes["traceback"],
+                    "merge_ms_median": passes["merge"],
+                    "device_ms_median": dev,
+                    "device_ms_all": [float(x + y + z) for x, y, z in zip(fwd, tb, mg)],
+                    "dominant_pass": max(passes, key=passes.get),
+                    "call_ms_median": float(np.median(wall)),
+                    "alignments_per_s_device": n_align / (dev * 1e-3),
+                    "alignments_per_s_call": n_align / (float(np.median(wall)) * 1e-3),
+                    "us_per_alignment_device": dev * 1e3 / n_align,
+                    "pairs_per_round": len(groups),
+                    "final_row_len": {"min": int(rows.min()), "median": float(np.median(rows)),
+                                      "max": int(rows.max())},
+                    "pairalign_same_pairs": {
+                        "pairs": int(len(pq)), "launches": ps["launches"],
+                        "device_ms_median": float(np.median(pa)),
+                        "forward_ms_median": float(np.median(pf)),
+                        "traceback_ms_median": float(np.median(pt_ms)),
+                        "us_per_alignment_device": float(np.median(pa)) * 1e3 / len(pq)}})
+    k = min(a.cpu_groups, len(groups))
+    t0 = time.perf_counter()
+    host = lib.groupalign_host(p, seeds[:k], groups[:k], n_threads=16)
+    cpu = time.perf_counter() - t0
+    n = int(host["col_off"][-1])
+    same = bool(np.array_equal(host["col_off"], res["col_off"][:k + 1]) and
+                np.array_equal(host["mask"], res["mask"][:n]) and
+                np.array_equal(host["count"], res["count"][:n]) and
+                np.array_equal(host["first"], res["first"][:n]) and
+                np.array_equal(host["dist"], res["dist"][:len(host["dist"])]))
+    cpu_n = sum(len(g) for g in groups[:k])
+    rec.update({"cpu_comparator": "dmx_groupalign_host (the project's sequential full-matrix DP, "
+                                  "traceback and merge, not edlib), 16 threads, one group per "
+                                  "thread",
+                "cpu_groups": int(k), "cpu_alignments_per_s": cpu_n / cpu,
+                "cpu_sample_matches_gpu": same})
+    rec["speedup_vs_cpu_dp_call"] = rec["alignments_per_s_call"] / rec["cpu_alignments_per_s"]
+    print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(rec, indent=1) + "\n")
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
