@@ -429,6 +429,36 @@ int dmx_groupalign_host(const uint32_t* seq2b, const uint32_t* nmask, const uint
  * the number of launches of each kernel. */
 int dmx_groupalign_stats(dmx_ctx* ctx, float* ms, int n_ms, int* rounds);
 
+/* ---- Read distance against rows of masks ----------------------------------------
+ * The comparisons of process_consensuslist() / similarity_species() (amplicon_sorter.py
+ * :1628-1716): every read not yet in a group against the consensus of every group, which
+ * rest_reads() (:1962-2023) repeats pass after pass.  A consensus is not a read of the resident
+ * batch, so the targets are given per call, as rows of dmx_groupalign's masks: row g is
+ * masks[row_off[g] .. row_off[g + 1]) (row_off has n_rows + 1 entries), one byte per column,
+ * bit c (0..4 = A, C, G, T, masked/N) set iff the column equals query symbol c, 0 = a gap column
+ * that equals nothing, bits 5..7 must be 0.
+ * out[i] = the NW (whole read, whole row) edit distance of resident read q[i] against row r[i],
+ * min(d, caps[i] + 1) when caps is given (caps may be NULL).  There is no HW mode and no
+ * DMX_PD_RC here: a reversed target is a second row that the caller builds.  Pairs may repeat
+ * and come in any order; a row may serve any number of pairs.  The rows are uploaded with the
+ * call; lists above DMX_PD_CHUNK pairs run as several launches, as dmx_pairdist's do.
+ * Everything is checked on the host before anything is launched, naming the pair or the row:
+ * DMX_E_INVALID for a null pointer with n_pairs > 0, a read index outside the batch, a row
+ * index outside n_rows, decreasing offsets or a mask byte with bits 5..7 set;
+ * DMX_E_UNSUPPORTED for a read or a row of 0 or more than DMX_PD_MAX_LEN entries.  A refused
+ * call launches nothing and leaves the context usable.  Synchronous. */
+int dmx_rowdist(dmx_ctx* ctx, size_t n_rows, const uint8_t* masks, const uint64_t* row_off,
+                const uint32_t* q, const uint32_t* r, const uint32_t* caps, size_t n_pairs,
+                uint32_t* out);
+/* Host only (no GPU; tests, CPU baseline): the same contract on a dmx_pack layout, by a plain
+ * full-matrix DP with the equality (mask[j] >> symbol) & 1 (dmx_groupalign_host's; a different
+ * algorithm from the kernel's on purpose).  Errors: dmx_last_error(NULL). */
+int dmx_rowdist_host(const uint32_t* seq2b, const uint32_t* nmask, const uint64_t* offsets,
+                     const uint32_t* lens, size_t n_reads, size_t n_rows, const uint8_t* masks,
+                     const uint64_t* row_off, const uint32_t* q, const uint32_t* r,
+                     const uint32_t* caps, size_t n_pairs, uint32_t* out, int n_threads);
+float dmx_rowdist_ms(dmx_ctx* ctx);  /* device time of the last dmx_rowdist (HIP events) */
+
 #ifdef __cplusplus
 }
 #endif

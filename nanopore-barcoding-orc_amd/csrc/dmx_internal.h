@@ -16,6 +16,7 @@ struct ChopState;   // read reorientation (dmx_chop.hip)
 struct PdState;     // pairwise read distance (dmx_pairdist.hip)
 struct PaState;     // pairwise alignment with edit path (dmx_pairdist.hip)
 struct GaState;     // progressive alignment of read groups (dmx_pairdist.hip)
+struct RdState;     // read distance against rows of masks (dmx_pairdist.hip)
 
 // Reach of a panel's gathers around a view, in nt (panel_reach below).
 struct PanelReach {
@@ -146,6 +147,7 @@ struct Ctx {
     PdState* pd = nullptr;       // dmx_pairdist buffers, created by its first call
     PaState* pa = nullptr;       // dmx_pairalign buffers, created by its first call
     GaState* ga = nullptr;       // dmx_groupalign buffers, created by its first call
+    RdState* rd = nullptr;       // dmx_rowdist buffers, created by its first call
 
     // RCCL communicator for the per-bin count exchange (dmx_comm.cpp)
     ncclComm* comm = nullptr;

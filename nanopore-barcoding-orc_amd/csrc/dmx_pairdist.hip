@@ -23,9 +23,13 @@
 // trace form's, and a third kernel (groupalign_merge_kernel) lays the path over the row: the new
 // row's masks and, per column, how many members showed each symbol and which member did first.
 //
-// All forms share one forward pass (pd_forward: pairdist_kernel, pairalign_kernel and
-// groupalign_kernel are its instantiations, told apart at compile time by their argument
-// struct), one traceback (pa_traceback) and one host path: the chunk planner (pd_plan: chunk
+// dmx_rowdist (process_consensuslist / similarity_species, :1628-1716: every read
+// not yet in a group against every group's consensus) is the distance form against such rows:
+// NW, no trace, the rows given by the caller per call (rowdist_kernel).
+//
+// All forms share one forward pass (pd_forward: pairdist_kernel, pairalign_kernel,
+// groupalign_kernel and rowdist_kernel are its instantiations, told apart at compile time by
+// their argument struct), one traceback (pa_traceback) and one host path: the chunk planner (pd_plan: chunk
 // limits, sort, wave packing, pair records), the staging of a launch (pd_stage: buffers, upload,
 // the arguments every kernel takes) and the buffers themselves (PdBufs).  A change to the block
 // step, the stripes or the planner is made once.
@@ -67,6 +71,13 @@ struct GaPair : PaPair {
     uint32_t ord;                // the member's 1-based place in its group
 };
 static_assert(sizeof(GaPair) == 64, "the group form uploads 64 bytes per pair");
+// dmx_rowdist's record: the distance form's, with the target a row of `n` masks at mask[row ..).
+// PdPair::t is the row's index among the call's rows, not a read.
+struct RdPair : PdPair {
+    uint64_t row;                // first column of the row in the device mask array
+    uint32_t n;                  // the row's length
+};
+static_assert(sizeof(RdPair) == 40, "the row form uploads 40 bytes per pair");
 struct PdWave {
     uint32_t first, count, G, steps;   // pairs[first .. first + count), one group of G lanes each
 };
@@ -113,6 +124,13 @@ struct GaArgs : PdHead<GaPair> {
     uint16_t* first;             // [column][5]: the first such member's place, 0 = none
     uint64_t cols;               // columns of mask (count and first have 5 entries per column)
     uint32_t* out;               // per pair: distance, path length
+};
+
+// dmx_rowdist: the distance form's arguments (NW only, so no mode) and the call's rows.
+struct RdArgs : PdHead<RdPair> {
+    const uint8_t* mask;         // per column: the equality mask, every row padded to 16 columns
+    uint64_t cols;               // columns of mask
+    uint32_t* out;               // per pair: the distance
 };
 
 // A device buffer that grows on demand, never shrinks, and is freed with its owner.
@@ -175,13 +193,20 @@ struct GaState : PdBufs<GaPair> {
     }
 };
 
+struct RdState : PdBufs<RdPair> {
+    DevBuf<uint8_t> mask;        // the rows of the last call
+    float ms = 0.f;
+};
+
 void pd_release(Ctx* c) {
     delete c->pd;
     delete c->pa;
     delete c->ga;
+    delete c->rd;
     c->pd = nullptr;
     c->pa = nullptr;
     c->ga = nullptr;
+    c->rd = nullptr;
 }
 
 // The five match masks (A, C, G, T, N) of query rows 64 wi .. 64 wi + 63, built in registers
@@ -218,20 +243,23 @@ __device__ __forceinline__ void pd_masks(const Packed& pk, uint64_t qoff, uint32
     peq[4] = nb;
 }
 
-// Where a pair's target lies: a read of the batch, or for dmx_groupalign the group's row.
+// Where a pair's target lies: a read of the batch, or a row of masks (dmx_groupalign's group
+// row, dmx_rowdist's given row).
+template <class Pair>
+constexpr bool kPdRowPair = std::is_same<Pair, GaPair>::value || std::is_same<Pair, RdPair>::value;
 template <class Pair>
 __device__ __forceinline__ bool pd_target_ok(const Bounds& bd, const Pair& P) {
-    if constexpr (std::is_same<Pair, GaPair>::value) return true;   // P.t is a group, not a read
+    if constexpr (kPdRowPair<Pair>) return true;   // P.t is a group or a row, not a read
     else return DMX_BOUND(bd, reads, P.t, kBufRead);
 }
 template <class Pair>
 __device__ __forceinline__ uint32_t pd_target_len(const uint32_t* lens, const Pair& P) {
-    if constexpr (std::is_same<Pair, GaPair>::value) return P.n;
+    if constexpr (kPdRowPair<Pair>) return P.n;
     else return lens[P.t];
 }
 template <class Pair>
 __device__ __forceinline__ uint64_t pd_target_off(const uint64_t* offs, const Pair& P) {
-    if constexpr (std::is_same<Pair, GaPair>::value) return P.row;
+    if constexpr (kPdRowPair<Pair>) return P.row;
     else return offs[P.t];
 }
 
@@ -246,14 +274,19 @@ __device__ __forceinline__ uint64_t pd_target_off(const uint64_t* offs, const Pa
 // target is P.n mask bytes at A.mask[P.row ..), the group's first lane loads 16 of them per 16
 // columns, and the value that travels down the lanes carries the mask, not a symbol; Eq is the
 // OR of the peq[c] whose bit is set (a gap column, mask 0, equals nothing).
+// RdArgs, the distance against a row of masks (dmx_rowdist): the target and its fetch are
+// GaArgs's, the score handling PdArgs's in NW (there is no mode and no reversed target: the
+// caller gives a reversed row as a row of its own); out[k] = the distance, clamped by the cap.
 // Every branch on the form is `if constexpr`: an instantiation holds no instruction of another.
 // That is a constraint, not a style: pairdist_kernel and pairalign_kernel are sensitive to where
 // their loop lands in the code, so a new form must leave their instructions as
-// they are (compare the assembly of both before and after).
+// they are (compare the assembly of all of them before and after).
 template <class Args>
 __device__ __forceinline__ void pd_forward(const Args& A) {
-    constexpr bool kRow = std::is_same<Args, GaArgs>::value;
-    constexpr bool kTrace = std::is_same<Args, PaArgs>::value || kRow;
+    constexpr bool kRd = std::is_same<Args, RdArgs>::value;
+    constexpr bool kRow = std::is_same<Args, GaArgs>::value || kRd;
+    constexpr bool kTrace = std::is_same<Args, PaArgs>::value || std::is_same<Args, GaArgs>::value;
+    constexpr uint32_t kColsBuf = kRd ? kBufRdCols : kBufGaCols;
     const uint32_t wave = blockIdx.x * kPdWavesPerBlock + (threadIdx.x >> 6);
     if (wave >= A.n_waves) return;   // whole waves leave: the shift below sees full waves
     const uint32_t lane = threadIdx.x & 63u;
@@ -262,7 +295,7 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
     const uint32_t g = lane / G, w = lane - g * G;
     bool active = g < W.count && (uint64_t)W.first + g < A.n_pairs;
     bool nw = true;
-    if constexpr (!kTrace) nw = A.mode == DMX_PD_NW;
+    if constexpr (!kTrace && !kRd) nw = A.mode == DMX_PD_NW;
 
     uint32_t m = 1, n = 1, rc = 0, cap = 0, has_cap = 0;
     uint64_t qoff = 0, toff = 0, soff = 0, trace = 0;
@@ -322,7 +355,7 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
                     if (k == 0u) {   // rows start at multiples of 16 columns and are padded to one
                         const uint64_t ri = toff + ts;
                         uint4 v = make_uint4(0, 0, 0, 0);
-                        if (bchk(A.pk.bd, (int64_t)ri + 15, 15, (int64_t)A.cols, kBufGaCols))
+                        if (bchk(A.pk.bd, (int64_t)ri + 15, 15, (int64_t)A.cols, kColsBuf))
                             v = *reinterpret_cast<const uint4*>(A.mask + ri);
                         codes = v.x, nbits = v.y, row2 = v.z, row3 = v.w;
                     }
@@ -406,6 +439,7 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs A) { pd_forward(A); }
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairalign_kernel(PaArgs A) { pd_forward(A); }
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void groupalign_kernel(GaArgs A) { pd_forward(A); }
+__global__ __launch_bounds__(64 * kPdWavesPerBlock) void rowdist_kernel(RdArgs A) { pd_forward(A); }
 
 // dmx_pairalign's traceback: one lane per pair walks back from (m, n), preferring up (INSERT),
 // then left (DELETE), then the diagonal (include/dmx.h).  Bit b of a word's Pv / Mv at column j
@@ -665,12 +699,11 @@ uint32_t pd_dp(int mode, const std::vector<uint8_t>& a, const std::vector<uint8_
     return *std::min_element(row.begin(), row.end());
 }
 
-// The whole (m + 1) x (n + 1) matrix, then the walk back from (m, n) by the contract's rule:
-// up (INSERT) before left (DELETE) before the diagonal.  The ops come out last first in `rev`.
-// eq(x, y): does query symbol x equal target entry y (a symbol, or dmx_groupalign's mask)?
+// The whole (m + 1) x (n + 1) matrix of query a against target b; returns D(m, n).
+// eq(x, y): does query symbol x equal target entry y (a symbol, or a row's mask)?
 template <class Eq>
-uint32_t pa_dp_path(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b,
-                    std::vector<uint16_t>& D, std::vector<uint8_t>& rev, Eq eq) {
+uint32_t pa_dp_matrix(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b,
+                      std::vector<uint16_t>& D, Eq eq) {
     const size_t m = a.size(), n = b.size(), W = n + 1;
     D.resize((m + 1) * W);
     for (size_t j = 0; j <= n; ++j) D[j] = (uint16_t)j;
@@ -684,6 +717,16 @@ uint32_t pa_dp_path(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b
             row[j] = (uint16_t)std::min<uint32_t>(sub, std::min<uint32_t>(up[j], row[j - 1]) + 1u);
         }
     }
+    return D[m * W + n];
+}
+
+// That matrix, then the walk back from (m, n) by the contract's rule: up (INSERT) before left
+// (DELETE) before the diagonal.  The ops come out last first in `rev`.
+template <class Eq>
+uint32_t pa_dp_path(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b,
+                    std::vector<uint16_t>& D, std::vector<uint8_t>& rev, Eq eq) {
+    const size_t m = a.size(), n = b.size(), W = n + 1;
+    pa_dp_matrix(a, b, D, eq);
     rev.clear();
     size_t i = m, j = n;
     while (i > 0 || j > 0) {
@@ -748,8 +791,9 @@ struct PdPlan {
 // when their scratch rows fill kPdScratchMax or their traces (kPaTraceEntry bytes per word and
 // column) the budget; one pair at least.  The pairs are sorted by group size, then target
 // length (similar step counts share a wave), longest first, and packed into waves of one group
-// size, 64 / G groups at most.  tn (dmx_groupalign): pair i's target is not read t[i] but a row
-// of tn[i] columns (t[i] is then the pair's group, and the caller fills in where the row lies).
+// size, 64 / G groups at most.  tn (dmx_groupalign, dmx_rowdist): pair i's target is not read
+// t[i] but a row of tn[i] columns (t[i] is then the pair's group or row, and the caller fills in
+// where the row lies).
 template <class Pair>
 size_t pd_plan(PdPlan<Pair>& pl, const uint32_t* lens, const uint32_t* q, const uint32_t* t,
                const uint8_t* flags, const uint32_t* caps, size_t n_pairs, size_t lo,
@@ -792,7 +836,7 @@ size_t pd_plan(PdPlan<Pair>& pl, const uint32_t* lens, const uint32_t* q, const 
                 P.toff = pl.trace;
                 P.roff = pl.ops;
             }
-            if constexpr (std::is_same<Pair, GaPair>::value) P.n = n;
+            if constexpr (kPdRowPair<Pair>) P.n = n;
             if (S > 1) pl.scratch += n;
             pl.trace += (size_t)mw * n;
             pl.ops += (size_t)m + n;
@@ -1454,5 +1498,166 @@ extern "C" int dmx_groupalign(dmx_ctx* c, size_t n_groups, const uint8_t* seed_m
     col_off[n_groups] = at;
     PD_CK(who, hipStreamSynchronize(st));
     if (ops) ga_emit_paths(paths, op_off, ops);
+    return DMX_OK;
+}
+
+// ---- dmx_rowdist: resident reads against rows of masks (include/dmx.h) -----------
+
+namespace {
+
+// Every argument check of both entry points, naming the pair or the row; rn[i] becomes the length
+// of pair i's row.  0, or the code with *err set.
+int rd_validate(const char* who, const uint32_t* lens, size_t n_reads, size_t n_rows,
+                const uint8_t* masks, const uint64_t* row_off, const uint32_t* q, const uint32_t* r,
+                size_t n_pairs, std::vector<uint32_t>& rn, std::string* err) {
+    const std::string name = std::string(who) + ": ";
+    for (size_t g = 0; g < n_rows; ++g) {
+        if (row_off[g + 1] < row_off[g]) {
+            *err = name + "row " + std::to_string(g) + ": offsets must not decrease";
+            return DMX_E_INVALID;
+        }
+        for (uint64_t x = row_off[g]; x < row_off[g + 1]; ++x)
+            if (masks[x] & 0xE0u) {
+                *err = name + "row " + std::to_string(g) + ": column " +
+                       std::to_string(x - row_off[g]) + " has a mask bit above the five symbols";
+                return DMX_E_INVALID;
+            }
+    }
+    rn.resize(n_pairs);
+    for (size_t i = 0; i < n_pairs; ++i) {
+        if (q[i] >= n_reads) {
+            *err = name + "pair " + std::to_string(i) + " names a read outside the batch";
+            return DMX_E_INVALID;
+        }
+        if (r[i] >= n_rows) {
+            *err = name + "pair " + std::to_string(i) + " names a row outside the " +
+                   std::to_string(n_rows) + " given";
+            return DMX_E_INVALID;
+        }
+    }
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const uint32_t m = lens[q[i]];
+        const uint64_t n = row_off[r[i] + 1] - row_off[r[i]];
+        if (m < 1 || m > DMX_PD_MAX_LEN) {
+            *err = name + "pair " + std::to_string(i) + ": reads of 1.." +
+                   std::to_string(DMX_PD_MAX_LEN) + " nt supported";
+            return DMX_E_UNSUPPORTED;
+        }
+        if (n < 1 || n > DMX_PD_MAX_LEN) {
+            *err = name + "pair " + std::to_string(i) + ": row " + std::to_string(r[i]) + " has " +
+                   std::to_string(n) + " columns (1.." + std::to_string(DMX_PD_MAX_LEN) +
+                   " supported)";
+            return DMX_E_UNSUPPORTED;
+        }
+        rn[i] = (uint32_t)n;
+    }
+    return DMX_OK;
+}
+
+}  // namespace
+
+extern "C" float dmx_rowdist_ms(dmx_ctx* c) { return c && c->rd ? c->rd->ms : 0.f; }
+
+extern "C" int dmx_rowdist_host(const uint32_t* seq2b, const uint32_t* nmask,
+                                const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
+                                size_t n_rows, const uint8_t* masks, const uint64_t* row_off,
+                                const uint32_t* q, const uint32_t* r, const uint32_t* caps,
+                                size_t n_pairs, uint32_t* out, int n_threads) {
+    const char* const who = "dmx_rowdist_host";
+    if (!n_pairs) return DMX_OK;
+    if (!q || !r || !out || !masks || !row_off || !seq2b || !nmask || !offsets || !lens) {
+        set_process_error(std::string(who) + ": null argument");
+        return DMX_E_INVALID;
+    }
+    std::string err;
+    std::vector<uint32_t> rn;
+    if (const int rc = rd_validate(who, lens, n_reads, n_rows, masks, row_off, q, r, n_pairs, rn,
+                                   &err)) {
+        set_process_error(err);
+        return rc;
+    }
+    pd_parallel(n_pairs, n_threads, [&](size_t k, size_t nth) {
+        std::vector<uint8_t> a, b;
+        std::vector<uint16_t> D;
+        for (size_t i = k; i < n_pairs; i += nth) {
+            pd_decode(seq2b, nmask, offsets[q[i]], lens[q[i]], false, a);
+            b.assign(masks + row_off[r[i]], masks + row_off[r[i] + 1]);
+            uint32_t d = pa_dp_matrix(a, b, D, [](uint8_t sym, uint8_t mk) {
+                return ((mk >> sym) & 1u) != 0;
+            });
+            if (caps && d > caps[i]) d = caps[i] + 1u;
+            out[i] = d;
+        }
+    });
+    return DMX_OK;
+}
+
+extern "C" int dmx_rowdist(dmx_ctx* c, size_t n_rows, const uint8_t* masks, const uint64_t* row_off,
+                           const uint32_t* q, const uint32_t* r, const uint32_t* caps,
+                           size_t n_pairs, uint32_t* out) {
+    const char* const who = "dmx_rowdist";
+    if (!c) return DMX_E_INVALID;
+    if (c->rd) c->rd->ms = 0.f;
+    if (!n_pairs) return DMX_OK;
+    if (!q || !r || !out || !masks || !row_off) {
+        c->err = "dmx_rowdist: null rows, pair list or output";
+        return DMX_E_INVALID;
+    }
+    std::vector<uint32_t> lens, rn;
+    if (const int rc = pd_fetch_lens(c, who, n_pairs, lens)) return rc;
+    if (const int rc = rd_validate(who, lens.data(), lens.size(), n_rows, masks, row_off, q, r,
+                                   n_pairs, rn, &c->err))
+        return rc;
+    if (const int rc = pd_state(c, who, c->rd)) return rc;
+    RdState* s = c->rd;
+    hipStream_t st = c->stream;
+    PD_CK(who, hipSetDevice(c->device));
+    const size_t chunk = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+
+    // every row starts at a multiple of 16 columns and is padded to one with zeros (the forward
+    // pass loads 16 mask bytes at a time); rows no pair names are not uploaded
+    std::vector<uint64_t> goff(n_rows, ~(uint64_t)0);
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_pairs; ++i)
+        if (goff[r[i]] == ~(uint64_t)0) {
+            goff[r[i]] = total;
+            total += ((uint64_t)rn[i] + 15u) & ~(uint64_t)15u;
+        }
+    std::vector<uint8_t> rows(total, 0);
+    for (size_t g = 0; g < n_rows; ++g)
+        if (goff[g] != ~(uint64_t)0)
+            std::memcpy(rows.data() + goff[g], masks + row_off[g], row_off[g + 1] - row_off[g]);
+    PD_CK(who, s->mask.reserve(total));
+    PD_CK(who, hipMemcpyAsync(s->mask.p, rows.data(), total, hipMemcpyHostToDevice, st));
+    PD_CK(who, hipStreamSynchronize(st));   // `rows` is pageable
+
+    PdPlan<RdPair> pl;
+    std::vector<uint32_t> res;
+    float total_ms = 0.f;
+    for (size_t lo = 0; lo < n_pairs;) {
+        const size_t hi = pd_plan(pl, lens.data(), q, r, nullptr, caps, n_pairs, lo, chunk,
+                                  kPdNoBudget, rn.data());
+        const size_t np = hi - lo;
+        for (RdPair& P : pl.pairs) P.row = goff[P.t];
+        RdArgs A;
+        if (const int rc = pd_stage(c, who, *s, pl, np, kKerRowdist, A)) return rc;
+        A.mask = s->mask.p;
+        A.cols = s->mask.cap;
+        A.out = s->out.p;
+        PD_CK(who, hipEventRecord(s->ev[0], st));
+        pd_launch_forward(rowdist_kernel, A, st);
+        PD_CK(who, hipGetLastError());
+        PD_CK(who, hipEventRecord(s->ev[1], st));
+        res.resize(np);
+        PD_CK(who, hipMemcpyAsync(res.data(), A.out, np * 4, hipMemcpyDeviceToHost, st));
+        PD_CK(who, hipStreamSynchronize(st));
+        if (const int brc = bounds_check(c, who)) return brc;
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+        total_ms += ms;
+        for (size_t k = 0; k < np; ++k) out[lo + pl.place(k)] = res[k];
+        lo = hi;
+    }
+    s->ms = total_ms;
     return DMX_OK;
 }

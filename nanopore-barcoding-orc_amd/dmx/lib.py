@@ -42,7 +42,8 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_mask_exceptions", "dmx_host_register", "dmx_host_unregister", "dmx_panel_reach",
            "dmx_debug_bounds_selftest", "dmx_panel_pieces", "dmx_pairdist", "dmx_pairdist_host",
            "dmx_pairdist_group_sizes", "dmx_pairalign", "dmx_pairalign_host",
-           "dmx_pairalign_stats", "dmx_groupalign", "dmx_groupalign_host", "dmx_groupalign_stats"]
+           "dmx_pairalign_stats", "dmx_groupalign", "dmx_groupalign_host", "dmx_groupalign_stats",
+           "dmx_rowdist", "dmx_rowdist_host"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -165,6 +166,12 @@ def load() -> ctypes.CDLL:
         L.dmx_groupalign_host.argtypes = [P, P, c_u64p, P, c_size] + ga + [c_int]
         L.dmx_groupalign_stats.argtypes = [P, ctypes.POINTER(ctypes.c_float), c_int,
                                            ctypes.POINTER(c_int)]
+    if hasattr(L, "dmx_rowdist"):
+        L.dmx_rowdist.argtypes = [P, c_size, P, c_u64p, P, P, P, c_size, P]
+        L.dmx_rowdist_host.argtypes = [P, P, c_u64p, P, c_size, c_size, P, c_u64p, P, P, P, c_size,
+                                       P, c_int]
+        L.dmx_rowdist_ms.argtypes = [P]
+        L.dmx_rowdist_ms.restype = ctypes.c_float
     # DMX_ALLOW_ABI=1: load an older in-tree build for a regression A/B (tools/replay_sweep.py)
     if L.dmx_abi_version() != ABI_VERSION and os.environ.get("DMX_ALLOW_ABI") != "1":
         raise DmxError("libdmx ABI mismatch")
@@ -288,6 +295,7 @@ class Context:
                                     p.offsets.ctypes.data, p.lengths.ctypes.data, p.n_words,
                                     p.n_reads, out.ctypes.data), "dmx_run")
         self._n_loaded = p.n_reads
+        self._resident = None
         return out
 
     def run_sparse(self, p: Packed) -> np.ndarray:
@@ -299,6 +307,7 @@ class Context:
                                            p.lengths.ctypes.data, p.n_words, p.n_reads,
                                            out.ctypes.data), "dmx_run_sparse")
         self._n_loaded = p.n_reads
+        self._resident = None
         return out
 
     def load(self, p: Packed):
@@ -307,6 +316,7 @@ class Context:
                                      p.n_reads), "dmx_load")
         self._n_loaded = p.n_reads
         self._lengths = np.array(p.lengths, dtype=np.uint32)   # pairalign sizes its output by them
+        self._resident = None   # sorter.assign's tag of the list whose batch is loaded
 
     def exec(self):
         self._check(self._L.dmx_exec(self._h), "dmx_exec")
@@ -459,6 +469,24 @@ class Context:
                         "dmx_groupalign_stats")
         return {"forward": float(ms[0]), "traceback": float(ms[1]), "merge": float(ms[2]),
                 "rounds": int(rounds.value), "launches": int(n)}
+
+    # ---- read distance against rows of masks (include/dmx.h dmx_rowdist) --------
+    def rowdist(self, rows, q, r, caps=None) -> np.ndarray:
+        """NW edit distance of resident read q[i] against rows[r[i]]: a row is a str or bytes
+        over A/C/G/T/N/-/IUPAC or a uint8 array of masks as mask_row makes them (a consensus,
+        or mask_rc of one for the reverse complement).  caps: out[i] = min(d, caps[i] + 1).
+        Returns uint32."""
+        masks, off, qa, ra, ca = _rowdist_args(rows, q, r, caps)
+        out = np.zeros(len(qa), dtype=np.uint32)
+        self._check(self._L.dmx_rowdist(self._h, len(off) - 1, masks.ctypes.data, off.ctypes.data,
+                                        qa.ctypes.data, ra.ctypes.data,
+                                        ca.ctypes.data if ca is not None else None, len(qa),
+                                        out.ctypes.data), "dmx_rowdist")
+        return out
+
+    def rowdist_ms(self) -> float:
+        """Device time (ms) of the last rowdist call."""
+        return float(self._L.dmx_rowdist_ms(self._h))
 
     def n_counts(self) -> int:
         a1 = 0 if self.mode == MODE_SINGLE else self.panel_sizes[1]
@@ -684,6 +712,57 @@ def groupalign_host(p: "Packed", seeds, groups, max_cols: int = 0, paths: bool =
         msg = L.dmx_last_error(None)
         raise DmxError(f"dmx_groupalign_host failed ({rc}): {msg.decode() if msg else ''}")
     return a.result()
+
+
+# A <-> T and C <-> G of a mask's low four bits (bit order A, C, G, T: the nibble reversed); N
+# (bit 4) stays
+_MASK_COMP = np.array([(m & 16) | ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3)
+                       for m in range(32)], dtype=np.uint8)
+
+
+def mask_rc(mask) -> np.ndarray:
+    """The reverse complement of a row of masks: the columns backwards with bits A <-> T and
+    C <-> G swapped, N and gap columns unchanged (mask_rc(mask_row(s)) is mask_row of the
+    reverse complement of s, IUPAC pairs included)."""
+    m = np.asarray(mask, dtype=np.uint8)
+    if m.ndim != 1 or (len(m) and int(m.max()) > 31):
+        raise DmxError("mask_rc: a one-dimensional array of masks 0..31")
+    return np.ascontiguousarray(_MASK_COMP[m[::-1]])
+
+
+def _rowdist_args(rows, q, r, caps):
+    """(masks, row_off, q, r, caps) of dmx_rowdist(_host), the rows closed up."""
+    rr = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1) if isinstance(s, np.ndarray)
+          else mask_row(s) for s in rows]
+    off = np.zeros(len(rr) + 1, dtype=np.uint64)
+    if rr:
+        off[1:] = np.cumsum([len(x) for x in rr])
+    masks = np.concatenate(rr + [np.zeros(1, dtype=np.uint8)])   # never empty: a valid pointer
+    qa = np.ascontiguousarray(q, dtype=np.uint32)
+    ra = np.ascontiguousarray(r, dtype=np.uint32)
+    if qa.ndim != 1 or qa.shape != ra.shape:
+        raise DmxError("rowdist: q and r must be one-dimensional and of equal length")
+    ca = None if caps is None else np.ascontiguousarray(caps, dtype=np.uint32)
+    if ca is not None and ca.shape != qa.shape:
+        raise DmxError("rowdist: caps must have one entry per pair")
+    return masks, off, qa, ra, ca
+
+
+def rowdist_host(p: "Packed", rows, q, r, caps=None, n_threads: int = 1) -> np.ndarray:
+    """dmx_rowdist's contract on the host, by a plain full-matrix DP with the mask equality (no
+    GPU): the checker of the kernel and the CPU comparator of tools/bench_rowdist.py."""
+    L = load()
+    masks, off, qa, ra, ca = _rowdist_args(rows, q, r, caps)
+    out = np.zeros(len(qa), dtype=np.uint32)
+    rc = L.dmx_rowdist_host(p.seq2b.ctypes.data, p.nmask.ctypes.data, p.offsets.ctypes.data,
+                            p.lengths.ctypes.data, p.n_reads, len(off) - 1, masks.ctypes.data,
+                            off.ctypes.data, qa.ctypes.data, ra.ctypes.data,
+                            ca.ctypes.data if ca is not None else None, len(qa), out.ctypes.data,
+                            int(n_threads))
+    if rc < 0:
+        msg = L.dmx_last_error(None)
+        raise DmxError(f"dmx_rowdist_host failed ({rc}): {msg.decode() if msg else ''}")
+    return out
 
 
 def cigar(ops, extended: bool = False) -> str:

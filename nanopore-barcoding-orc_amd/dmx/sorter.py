@@ -268,13 +268,114 @@ def consensus(ctx, reads, groups, ambiguous: bool = False, n_threads: int = 16) 
     return [_final_correction(top, top_n, c, THRESHOLDS[-1]) for top, top_n, c in tops]
 
 
-def _clean(reads) -> list:
+def assign(ctx, reads, unassigned, consensuses, similar: float, n_threads: int = 16,
+           chunk: int = 2_000_000, max_chunks: int = 100):
+    """One pass of process_consensuslist (:1628-1691) + similarity_species (:1693-1716) + the
+    best-hit filter of update_groups (:1730-1755) on top of dmx_rowdist.
+    `reads` are the bin's reads (str or bytes over A/C/G/T/N), `unassigned` the indices of those
+    not yet in a group, `consensuses` the groups' consensus sequences (group = list index),
+    `similar` the pass's threshold as a fraction.  ctx: a Context, or None to run on the host
+    reference (lib.rowdist_host, n_threads).
+
+    Pairs: every read of `unassigned`, in the given order, against every consensus in index
+    order, except where len(a) * 1.05 < len(b) or len(b) * 1.05 < len(a) in double arithmetic
+    (:1664); generation stops after the read at whose end `max_chunks` full chunks of `chunk`
+    comparisons have been made (:1669-1676, tested once per read).
+    Lines: iden = round(1 - d / len(longer), 3); `read:group:iden` when iden >= similar - 0.01,
+    else, when iden < 0.5, the same line form with the identity against the reverse-complemented
+    consensus if that passes (no `:reverse` tag here, as in the reference).
+    Best hit: one survivor per read; a later line replaces the kept one iff its identity is >=
+    the kept one's, so among equal identities the last line wins.  The lines come in
+    pair-generation order, read-major and consensus ascending; the reference's own order is its
+    workers' interleaving, so its tie winner is whichever worker wrote last.
+
+    Returns (lines, best, added): best has one (read, group, iden) per read that has a line, in
+    first-appearance order; added are the entries of best with iden >= similar.  The outer
+    rest_reads loop, the sampling above 200 reads, finetune, compare_consensus and
+    consensus_direction are the caller's."""
+    seqs = _clean(reads)
+    cons = _clean(consensuses, "consensus")
+    for g, s in enumerate(cons):
+        if not s:
+            raise DmxError(f"assign: consensus {g} is empty")
+    un = np.asarray(unassigned, dtype=np.int64).reshape(-1)
+    if len(un) and (int(un.min()) < 0 or int(un.max()) >= len(seqs)):
+        raise DmxError("assign: an unassigned index is outside the reads")
+    ln = np.array([len(s) for s in seqs], dtype=np.int64)
+    lc = np.array([len(s) for s in cons], dtype=np.int64)
+    if (len(ln) and int(ln.max()) > lib.PD_MAX_LEN) or (len(lc) and int(lc.max()) > lib.PD_MAX_LEN):
+        raise DmxError(f"a read or a consensus is longer than {lib.PD_MAX_LEN} nt")
+    if not len(un) or not len(cons):
+        return [], [], []
+    # the pairs: the 5 % rule in both directions with the reference's double products, then the
+    # stop, tested after each read's consensuses as the reference does (k == 100, :1675)
+    la = ln[un].astype(np.float64)[:, None]
+    lb = lc.astype(np.float64)[None, :]
+    keep = ~((la * 1.05 < lb) | (lb * 1.05 < la))
+    full = np.cumsum(keep.sum(axis=1)) // int(chunk)   # todo files written by the end of a read
+    stop = np.flatnonzero(full == int(max_chunks))
+    if len(stop):
+        keep[stop[0] + 1:] = False
+    xi, g = np.nonzero(keep)            # row-major: read-major, consensus ascending
+    if not len(xi):
+        return [], [], []
+    q = un[xi]
+    lt = np.maximum(ln[q], lc[g])       # distance() divides by the longer one's length
+    thr = similar - 0.01
+    top = int(lt.max()) + 1
+    cap_half = np.full(top, -1, dtype=np.int64)
+    cap_thr = np.full(top, -1, dtype=np.int64)
+    for L in np.unique(lt):
+        cap_half[L] = identity_cap(int(L), 0.5)
+        cap_thr[L] = identity_cap(int(L), thr)
+    rows = [lib.mask_row(s) for s in cons]
+    p = None
+    if ctx is None or getattr(ctx, "_resident", None) is not reads:
+        blob = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+        offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
+        p = lib.pack(blob, offs, ln.astype(np.uint32))
+        if ctx is not None:
+            ctx.load(p)
+            ctx._resident = reads      # the next pass over the same list finds its batch loaded
+
+    def dist(rws, qq, rr, caps):
+        if ctx is not None:
+            return ctx.rowdist(rws, qq, rr, caps).astype(np.int64)
+        return lib.rowdist_host(p, rws, qq, rr, caps, n_threads=n_threads).astype(np.int64)
+
+    # the exact distance is needed wherever the identity is >= 0.5 or >= similar - 0.01
+    fcap = np.maximum(np.maximum(cap_half[lt], cap_thr[lt]), 0).astype(np.uint32)
+    df = dist(rows, q, g, fcap)
+    plain = df <= cap_thr[lt]
+    rcs = np.flatnonzero(~plain & (df > cap_half[lt]) & (cap_thr[lt] >= 0))
+    hit = np.zeros(len(q), dtype=bool)
+    d = df.copy()
+    if len(rcs):
+        # the reverse-complemented consensuses the second call needs, as rows of their own
+        gs, inv = np.unique(g[rcs], return_inverse=True)
+        dr = dist([lib.mask_rc(rows[k]) for k in gs], q[rcs], inv,
+                  cap_thr[lt[rcs]].astype(np.uint32))
+        ok = dr <= cap_thr[lt[rcs]]
+        hit[rcs[ok]] = True
+        d[rcs[ok]] = dr[ok]
+    lines, best = [], {}
+    for k in np.flatnonzero(plain | hit):
+        rd, grp = int(q[k]), int(g[k])
+        iden = identity(int(d[k]), int(lt[k]))
+        lines.append(f"{rd}:{grp}:{iden}")
+        if rd not in best or iden >= best[rd][2]:
+            best[rd] = (rd, grp, iden)
+    best = list(best.values())
+    return lines, best, [b for b in best if b[2] >= similar]
+
+
+def _clean(reads, what: str = "read") -> list:
     out = []
     for i, r in enumerate(reads):
         b = r.encode("ascii", "replace") if isinstance(r, str) else bytes(r)
         b = b.upper()
         if b.translate(None, b"ACGTN"):
-            raise DmxError(f"read {i} has a byte outside ACGTN (the similarity pass supports "
+            raise DmxError(f"{what} {i} has a byte outside ACGTN (the similarity pass supports "
                            "A, C, G, T and N only)")
         out.append(b)
     return out
