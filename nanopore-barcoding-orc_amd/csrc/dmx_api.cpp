@@ -94,12 +94,22 @@ int ensure_pipeline(Ctx* c) {
         int rc;
         for (int r = 0; r < 2; ++r) {
             if ((rc = dev_alloc(c, &c->d_winner[r], s))) return rc;
-            if ((rc = dev_alloc(c, &c->d_origin[r], s))) return rc;
             if ((rc = dev_alloc(c, &c->d_lb[r], s))) return rc;
         }
         if ((rc = dev_alloc(c, &c->d_linked, n))) return rc;
         c->slot_cap = s;
         c->cap_reads = n;
+    }
+    // per-slot origins: only for the rounds this mode runs in ring mode (a band round's winner
+    // key carries its origin), sized like the winner slots
+    for (int r = 0; r < 2; ++r) {
+        if ((r == 1 && c->mode == DMX_MODE_SINGLE) || band_round(c, r) ||
+            c->origin_cap[r] >= c->slot_cap)
+            continue;
+        c->origin_cap[r] = 0;
+        int rc;
+        if ((rc = dev_alloc(c, &c->d_origin[r], c->slot_cap))) return rc;
+        c->origin_cap[r] = c->slot_cap;
     }
     // The item list has its own capacity: a linked batch needs reads x pairs items, which can
     // exceed what an earlier two-round batch allocated (reads) while its winner slots (2 x
@@ -127,7 +137,6 @@ int ensure_pipeline(Ctx* c) {
         for (int r = 0; r < 2; ++r)
             for (int l = 0; l < 2; ++l) {
                 if ((rc = dev_alloc(c, &c->d_cand[r][l], want_cand))) return rc;
-                if ((rc = dev_alloc(c, &c->d_cand_out[r][l], want_cand))) return rc;
             }
         c->cand_cap = want_cand;
     }
@@ -195,7 +204,6 @@ int grow_cands(Ctx* c) {
     for (int r = 0; r < 2; ++r)
         for (int l = 0; l < 2; ++l) {
             if ((rc = dev_alloc(c, &c->d_cand[r][l], want))) return rc;
-            if ((rc = dev_alloc(c, &c->d_cand_out[r][l], want))) return rc;
         }
     c->cand_cap = want;
     return DMX_OK;
@@ -353,7 +361,6 @@ void dmx_close(dmx_ctx* c) {
     for (int r = 0; r < 2; ++r)
         for (int l = 0; l < 2; ++l) {
             if (c->d_cand[r][l]) hipFree(c->d_cand[r][l]);
-            if (c->d_cand_out[r][l]) hipFree(c->d_cand_out[r][l]);
         }
     void* alt[] = {c->alt.seq_alloc, c->alt.nmask_alloc, c->alt.offs, c->alt.lens, c->alt.res,
                    c->alt.exc, c->d_exc};

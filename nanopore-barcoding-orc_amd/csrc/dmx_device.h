@@ -276,10 +276,10 @@ struct Cand {
 };
 static_assert(sizeof(Cand) == 40 && offsetof(Cand, off) == 32, "Cand layout");
 
-struct Outcome {      // best cell found by the resolve lane of a cluster
+struct Outcome {      // best cell found by the resolve lane of a cluster (ring mode)
     uint64_t key;     // ~0 = none
     int32_t origin;
-    int32_t pad;      // band_cand_kernel: the cell's winner slot (read by select_cand_kernel)
+    int32_t pad;
 };
 
 // 64-bit ordering key, smaller = better, matching cutadapt's selection order:
@@ -298,6 +298,33 @@ __host__ __device__ inline int key_cost(uint64_t k) { return (int)((k >> 48) & 1
 __host__ __device__ inline int key_adapter(uint64_t k) { return (int)((k >> 40) & 255); }
 __host__ __device__ inline uint64_t key_t(uint64_t k) { return k & ((1ull << 40) - 1); }
 
+// Band-mode rounds carry the winning cell's origin in its key: the scan position
+// field holds t << 4 | (delta + 8), delta = origin - (j - iend) being the path's start diagonal
+// against the end cell's own.  An optimal path of cost c leaves its end cell's diagonal by at most
+// c (§3.5) and band mode has c <= kk <= 7, so |delta| <= 7 and the code is 1..15.  Two cells of a
+// slot that agree in every field down to t are the same cell and so have the same delta: the
+// minimum over the slot is the one make_key's order picks, and it delivers the origin with it.
+// Bit budget: t <= len + 1 + iend with a 32-bit len and iend <= 64, so t < 2^33 <= 2^36.
+constexpr int kKeyPosBits = 40;     // make_key's scan position field
+constexpr int kKeyDeltaBits = 4;
+constexpr int kKeyDeltaBias = 8;
+constexpr int kKeyDeltaMin = -kKeyDeltaBias;   // code 0: below every real cell's (bound keys)
+constexpr int kBandMaxCost = 7;                // largest kk of a band-mode panel
+static_assert(sizeof(uint32_t) * 8 + 1 <= kKeyPosBits - kKeyDeltaBits,
+              "t = len + 1 + iend < 2^33 must fit above the delta code");
+static_assert(kBandMaxCost < kKeyDeltaBias && kBandMaxCost + kKeyDeltaBias < (1 << kKeyDeltaBits),
+              "|delta| <= cost <= 7 must fit the delta code");
+__host__ __device__ inline uint64_t make_key_o(int score, int o, int cost, int a, uint64_t t,
+                                               int delta) {
+    return make_key(score, o, cost, a,
+                    (t << kKeyDeltaBits) |
+                        (uint64_t)((delta + kKeyDeltaBias) & ((1 << kKeyDeltaBits) - 1)));
+}
+__host__ __device__ inline uint64_t key_t_o(uint64_t k) { return key_t(k) >> kKeyDeltaBits; }
+__host__ __device__ inline int key_delta(uint64_t k) {
+    return (int)(k & ((1u << kKeyDeltaBits) - 1)) - kKeyDeltaBias;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Bounds of the device buffers.  Release builds: empty, every check is `true`.
 // DMX_DEBUG_BOUNDS builds (dmx/libdmx_bounds.so): every gather of the packed batch and every
@@ -313,7 +340,7 @@ enum BoundsBuf : uint32_t {
 };
 enum BoundsKernel : int32_t {
     kKerFilter = 1, kKerVerify, kKerScreen, kKerScreen4, kKerWscan, kKerScan, kKerBand0,
-    kKerBand1, kKerSelectCand, kKerResolve, kKerSelect, kKerFin0, kKerFin1, kKerFin0L, kKerFin1L,
+    kKerBand1, kKerResolve, kKerSelect, kKerFin0, kKerFin1, kKerFin0L, kKerFin1L,
     kKerFin2L, kKerChop, kKerChopBig, kKerChopStart, kKerSelfTest, kKerPieces, kKerPairdist,
     kKerPairalign, kKerPairalignTb, kKerGroupalign, kKerGroupalignTb, kKerGroupalignMerge,
     kKerRowdist

@@ -93,7 +93,8 @@ struct Ctx {
     // pipeline state
     dmx_result* d_res = nullptr;
     unsigned long long* d_winner[2] = {nullptr, nullptr};
-    int32_t* d_origin[2] = {nullptr, nullptr};
+    int32_t* d_origin[2] = {nullptr, nullptr};   // ring rounds only (band rounds: in the key)
+    size_t origin_cap[2] = {0, 0};
     int32_t* d_lb[2] = {nullptr, nullptr};
     bool ring_small[2] = {true, true};
     bool band_ok[2] = {true, true};
@@ -105,7 +106,6 @@ struct Ctx {
     Outcome* d_outc[2] = {nullptr, nullptr};
     size_t cl_cap = 0;
     Cand* d_cand[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    Outcome* d_cand_out[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     size_t cand_cap = 0;
     Window* d_win = nullptr;
     Window* d_win2 = nullptr;
@@ -165,6 +165,10 @@ int reset_counts(Ctx* c);      // size d_counts for the current panels/mode and 
 void set_process_error(const std::string& msg);
 std::string process_error();
 void chop_invalidate(Ctx* c);   // a new dmx_load makes the last dmx_chop_exec's results stale
+// Round `round` resolves its candidates with the band kernels (every adapter has kk <= 7 and
+// DMX_RESOLVE=ring is not set): its winner keys carry their origin (make_key_o), and nothing
+// reads or writes d_origin[round].
+inline bool band_round(const Ctx* c, int round) { return c->band_ok[round] && !c->force_ring; }
 int launch_round(Ctx* c, int round, hipStream_t st);
 int prepare_flat(Ctx* c, hipStream_t st);   // the flat piece scan's index (dmx_kernels.hip)
 int launch_finalize(Ctx* c, int round, hipStream_t st);

@@ -38,7 +38,7 @@ struct RoundArgs {
     uint32_t cl_cap;
     uint32_t* flags;             // bit0 cluster overflow, bit1 window violation
     unsigned long long* winner;  // per slot, ~0 = none
-    int32_t* origin;             // per slot
+    int32_t* origin;             // per slot (ring rounds; band rounds carry it in the key)
     int32_t* lb;                 // per slot: lower bound of the best accepted score (0 = none)
     Window* win;
     uint32_t* win_count;         // [kShards]: shard s at win + s * win_scap
@@ -49,7 +49,6 @@ struct RoundArgs {
     uint32_t* diag;              // [0] resolved clusters, [1] tracebacks
     int32_t band;                // 1: emit candidate cells (band kernels), 0: clusters (ring)
     Cand* cand[2];               // candidate lists: [0] cost <= 3 (band 7), [1] cost 4..7 (15)
-    Outcome* cand_out[2];
     uint32_t* cand_count;        // [2][kShards] x kShardStride: list l, shard s at cand[l] + s * cand_scap
     uint32_t cand_cap;
     uint32_t cand_scap;          // per-shard capacity
@@ -3864,7 +3863,8 @@ __device__ __forceinline__ void band_dp_cost(int wc, bool fast, const uint8_t* r
 // end.  A queue runs a DP pass whenever it holds 256 cells (and once more, partially, at the end),
 // so the DP waves are full whatever the prune rate; a pass first sorts its cells by cost, so each
 // wave runs the narrowest band its cells allow (band_dp_cost).  The slot's best is the minimum
-// key over all its candidates (key order = locate's / best_match's / ReverseComplementer's order).
+// key over all its candidates (key order = locate's / best_match's / ReverseComplementer's order);
+// the key carries the cell's origin (make_key_o), so the atomicMin is all a cell ever writes.
 #ifndef DMX_BAND_SPLIT   // list 1 in two launches, cost 4 then cost 5 (0: one launch)
 #define DMX_BAND_SPLIT 1
 #endif
@@ -3921,7 +3921,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
     sm.load(R.cand_count + list * kShards * kShardStride, R.cand_scap);   // (barrier: above too)
     const uint32_t total = sm.total();
     const Cand* cl = R.cand[list];
-    Outcome* outs = R.cand_out[list];
     const uint32_t wave = threadIdx.x >> 6;
     const bool fast = s_multi == 0;                  // (read after sm.load's barrier)
 
@@ -3987,16 +3986,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
                     band_dp_cost<CMIN == 0 ? 1 : CMIN, CMAX, true>(
                         wc, fast, s_rm + c.a, R.pk, tv, ad.front, iend, j, c2,
                         origin, score);
-                if (c2 != cst) atomicOr(R.flags, 2u);    // band / scan disagreement: bug
+                // the path's start diagonal against the end cell's: |delta| <= cost <= 7 (§3.5)
+                const int delta = origin - (j - iend);
+                // band / scan disagreement, or an origin the key cannot hold: bug
+                if (c2 != cst || abs(delta) > cst || cst > kBandMaxCost) atomicOr(R.flags, 2u);
                 const int lr = iend + (origin < 0 ? origin : 0);
-                if (slot_in && lr >= 0 && cst <= (int)acc[lr]) {
-                    Outcome out;
-                    out.key = make_key(score, c.o, cst, c.a, t);
-                    out.origin = origin;
-                    out.pad = (int32_t)slot;             // select_cand needs no Cand reload
-                    atomicMin(&R.winner[slot], (unsigned long long)out.key);
-                    outs[cj] = out;
-                }
+                if (slot_in && lr >= 0 && cst <= (int)acc[lr])
+                    atomicMin(&R.winner[slot],
+                              (unsigned long long)make_key_o(score, c.o, cst, c.a, t, delta));
             }
         }
         __syncthreads();
@@ -4007,8 +4004,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
         const uint32_t ci = ti < total ? sm.phys(ti) : 0u;
         Cand c{};
         if (ti < total) c = cl[ci];
-        // cmask != 0: this launch takes the list's cells whose cost has its bit set (the others'
-        // outcomes are written by the launch that takes them)
+        // cmask != 0: this launch takes the list's cells whose cost has its bit set (the others
+        // belong to the launch that takes their cost)
         if (ti < total && (cmask == 0 || ((cmask >> c.cost) & 1))) {
             const uint32_t slot = slot_of(R, c.item, c.sub);
             const bool slot_in = DMX_BOUND(R.pk.bd, slots, slot, kBufSlot);
@@ -4016,24 +4013,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
             const int j = (int)c.j;
             const uint64_t t = iend == (int)(s_amk[c.a] & 255u) ? (uint64_t)j
                                                                : (uint64_t)c.len + 1 + iend;
-            Outcome out;
-            out.key = ~0ull;
-            out.origin = 0;
-            out.pad = 0;
             const int lrmax = min(iend, j + cost);
             const int ub = lrmax - 2 * cost;
+            // (the bound key takes the smallest delta code: <= every real key of this cell)
             if (slot_in && viable_lb(R.lb[slot], lrmax, c.o, cost) &&
-                make_key(ub, c.o, cost, c.a, t) <= R.winner[slot]) {
+                make_key_o(ub, c.o, cost, c.a, t, kKeyDeltaMin) <= R.winner[slot]) {
                 if (cost == 0) {              // exact: the pointer chain is the pure diagonal
-                    const int origin = j - iend;
+                    const int origin = j - iend;   // (delta = 0)
                     const int score = j >= iend ? iend : j;
                     const int lr = iend + (origin < 0 ? origin : 0);
-                    if (lr >= 0 && 0 <= (int)s_bacc[72 * c.a + lr]) {
-                        out.key = make_key(score, c.o, 0, c.a, t);
-                        out.origin = origin;
-                        out.pad = (int32_t)slot;
-                        atomicMin(&R.winner[slot], (unsigned long long)out.key);
-                    }
+                    if (lr >= 0 && 0 <= (int)s_bacc[72 * c.a + lr])
+                        atomicMin(&R.winner[slot],
+                                  (unsigned long long)make_key_o(score, c.o, 0, c.a, t, 0));
                 } else {
                     const int dx = j - iend;
                     const int H = CMAX;       // the widest band this kernel may run
@@ -4043,7 +4034,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
                     s_qc[e][q] = (uint8_t)cost;
                 }
             }
-            outs[ci] = out;
         }
         __syncthreads();
         for (int e = 0; e < 2; ++e)                 // full passes (each queue ends below 256)
@@ -4055,25 +4045,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
     for (int e = 0; e < 2; ++e)
         if (s_nq[e]) dp_pass(e, s_nq[e]);
     if (threadIdx.x == 0 && s_n) atomicAdd(R.diag + 1, s_n);
-}
-
-__global__ void select_cand_kernel(RoundArgs R) {
-    __shared__ uint32_t s_spre[kShards + 1];
-    for (int list = 0; list < 2; ++list) {
-        ShardMap sm{s_spre, 0u};
-        __syncthreads();   // the previous list's map is no longer read
-        sm.load(R.cand_count + list * kShards * kShardStride, R.cand_scap);
-        const uint32_t total = sm.total();
-        for (uint32_t ti = blockIdx.x * blockDim.x + threadIdx.x; ti < total;
-             ti += gridDim.x * blockDim.x) {
-            const uint32_t ci = sm.phys(ti);
-            const Outcome o = R.cand_out[list][ci];
-            if (o.key == ~0ull) continue;
-            const uint32_t slot = (uint32_t)o.pad;   // band_cand_kernel stores the cell's slot
-            if (!DMX_BOUND(R.pk.bd, slots, slot, kBufSlot)) continue;
-            if (R.winner[slot] == o.key) R.origin[slot] = o.origin;
-        }
-    }
 }
 
 // select: the cluster whose outcome is the slot's winner publishes its origin.
@@ -4093,12 +4064,15 @@ __global__ void select_kernel(RoundArgs R) {
 // ---------------------------------------------------------------------------------------------
 // finalize
 // ---------------------------------------------------------------------------------------------
-// Decode a winning key into a cutadapt Match on a view of length vlen.
-__device__ __forceinline__ void decode_match(uint64_t key, int origin, uint32_t vlen,
-                                             const DevPanel* P, dmx_match& mt, int& a, int& o) {
+// Decode a winning key into a cutadapt Match on a view of length vlen.  okey: the round ran in
+// band mode, so the key carries its origin (make_key_o) and `origins` is not read; else the
+// origin is origins[slot] (ring mode: select_kernel wrote it).
+__device__ __forceinline__ void decode_match(uint64_t key, bool okey, const int32_t* origins,
+                                             size_t slot, uint32_t vlen, const DevPanel* P,
+                                             dmx_match& mt, int& a, int& o) {
     a = key_adapter(key);
     o = key_orient(key);
-    const uint64_t t = key_t(key);
+    const uint64_t t = okey ? key_t_o(key) : key_t(key);
     int refstop, qstop;
     if (t <= vlen) {
         qstop = (int)t;
@@ -4109,6 +4083,7 @@ __device__ __forceinline__ void decode_match(uint64_t key, int origin, uint32_t 
     }
     mt.rstop = qstop;
     mt.astop = (int16_t)refstop;
+    const int origin = okey ? qstop - refstop + key_delta(key) : origins[slot];
     if (origin >= 0) {
         mt.astart = 0;
         mt.rstart = origin;
@@ -4125,7 +4100,8 @@ struct FinalArgs {
     const DevPanel* p0;
     const DevPanel* p1;
     const unsigned long long* winner;
-    const int32_t* origin;
+    const int32_t* origin;      // ring rounds only (nullptr when every round is a band round)
+    int32_t okey;               // this round's keys carry their origin (band mode, make_key_o)
     dmx_result* res;
     ItemView* items;            // round-1 item list (out for finalize0, in for finalize1)
     uint32_t* n_items;
@@ -4137,6 +4113,7 @@ struct FinalArgs {
     // linked mode
     const unsigned long long* winner0;   // per (read, pair) front winners
     const int32_t* origin0;
+    int32_t okey0;                       // round 0's keys carry their origin
     unsigned long long* linked_best;     // per read: best pair key
     Bounds bd;                           // DMX_DEBUG_BOUNDS: extents of the buffers above
 };
@@ -4180,7 +4157,7 @@ __global__ __launch_bounds__(256) void finalize0_linked_kernel(FinalArgs F) {
             if (key == ~0ull) continue;
             dmx_match m;
             int aa, o;
-            decode_match(key, F.origin[(size_t)r * F.A0 + a], n, F.p0, m, aa, o);
+            decode_match(key, F.okey, F.origin, (size_t)r * F.A0 + a, n, F.p0, m, aa, o);
             ItemView v;
             v.read = r;
             v.strand = 0;
@@ -4229,9 +4206,9 @@ __global__ __launch_bounds__(256) void finalize2_linked_kernel(FinalArgs F) {
             const ItemView v = F.items[i];
             dmx_result& out = F.res[r];
             int aa, o;
-            decode_match(F.winner0[(size_t)r * F.A0 + a], F.origin0[(size_t)r * F.A0 + a],
-                         F.lens[r], F.p0, out.m1, aa, o);
-            decode_match(F.winner[i], F.origin[i], v.len, F.p1, out.m2, aa, o);
+            decode_match(F.winner0[(size_t)r * F.A0 + a], F.okey0, F.origin0,
+                         (size_t)r * F.A0 + a, F.lens[r], F.p0, out.m1, aa, o);
+            decode_match(F.winner[i], F.okey, F.origin, i, v.len, F.p1, out.m2, aa, o);
             out.bin1 = out.bin2 = (int16_t)a;
             b = a;
         }
@@ -4303,7 +4280,7 @@ __global__ __launch_bounds__(256) void finalize0_kernel(FinalArgs F) {
             if (key != ~0ull) {
                 int a;
                 const uint32_t n = F.lens[r];
-                decode_match(key, F.origin[ws], n, F.p0, out.m1, a, o);
+                decode_match(key, F.okey, F.origin, ws, n, F.p0, out.m1, a, o);
                 out.bin1 = (int16_t)a;
                 out.rc1 = (uint8_t)o;
                 if (F.mode == DMX_MODE_TWO_ROUND) {
@@ -4372,7 +4349,7 @@ __global__ __launch_bounds__(256) void finalize1_kernel(FinalArgs F) {
         out.rc2 = (uint8_t)o;
         if (key != ~0ull) {
             int a;
-            decode_match(key, F.origin[ws], v.len, F.p1, out.m2, a, o);
+            decode_match(key, F.okey, F.origin, ws, v.len, F.p1, out.m2, a, o);
             out.bin2 = (int16_t)a;
             b = a;
         }
@@ -4448,8 +4425,7 @@ int bounds_check(Ctx* c, const char* where) {
     static const char* const kKer[] = {
         "?", "filter_kernel", "verify_kernel", "iscreen_kernel", "iscreen4_kernel",
         "wscan_kernel", "scan_kernel", "band_cand_kernel<0,3>", "band_cand_kernel<4,5|7>",
-        "select_cand_kernel", "resolve_kernel", "select_kernel", "finalize0_kernel",
-        "finalize1_kernel", "finalize0_linked_kernel", "finalize1_linked_kernel",
+        "resolve_kernel", "select_kernel", "finalize0_kernel", "finalize1_kernel", "finalize0_linked_kernel", "finalize1_linked_kernel",
         "finalize2_linked_kernel", "chop_kernel", "chop_big_kernel", "chop_start",
         "bounds_selftest_kernel", "pscreen_kernel", "pairdist_kernel", "pairalign_kernel",
         "pairalign_traceback_kernel", "groupalign_kernel", "groupalign_traceback_kernel",
@@ -4649,11 +4625,10 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
     R.win2_count = c->d_shard + (kShWin2 + round) * kShards * kShardStride;
     R.win_cap = (uint32_t)c->win_cap;
     R.win_scap = (uint32_t)(c->win_cap / kShards);
-    const bool band = c->band_ok[round] && !c->force_ring;
+    const bool band = band_round(c, round);
     R.band = band ? 1 : 0;
     for (int l = 0; l < 2; ++l) {
         R.cand[l] = c->d_cand[round][l];
-        R.cand_out[l] = c->d_cand_out[round][l];
     }
     R.cand_count = c->d_shard + (kShCand + 2 * round) * kShards * kShardStride;
     R.cand_cap = (uint32_t)c->cand_cap;
@@ -4803,9 +4778,7 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
             hipLaunchKernelGGL((band_cand_kernel<4, 5>), dim3(256 * 4), dim3(256), 0, st, R, 1, 0);
         }
         DMX_DBG_SYNC("band_cand_kernel<4, 5|7>");
-        set_kid(R.pk.bd, kKerSelectCand);
-        hipLaunchKernelGGL(select_cand_kernel, dim3(1024), dim3(256), 0, st, R);
-        DMX_DBG_SYNC("select_cand_kernel");
+        // (no selection pass: the winning key carries its origin, make_key_o)
         hipEventRecord(c->ev[round * 3 + 2], st);
         return hipGetLastError() == hipSuccess ? DMX_OK : DMX_E_HIP;
     }
@@ -4866,6 +4839,7 @@ int launch_finalize(Ctx* c, int round, hipStream_t st) {
     F.p1 = c->d_panel[1];
     F.winner = c->d_winner[round];
     F.origin = c->d_origin[round];
+    F.okey = band_round(c, round) ? 1 : 0;
     F.res = c->d_res;
     F.items = c->d_items;
     F.n_items = c->d_counters + 2;
@@ -4877,6 +4851,7 @@ int launch_finalize(Ctx* c, int round, hipStream_t st) {
     F.counts = c->d_counts;
     F.winner0 = c->d_winner[0];
     F.origin0 = c->d_origin[0];
+    F.okey0 = band_round(c, 0) ? 1 : 0;
     F.linked_best = c->d_linked;
     F.bd = make_bounds(c, kKerFin0);
     if (c->mode == DMX_MODE_LINKED) {
