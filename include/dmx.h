@@ -304,8 +304,9 @@ int dmx_chop_stats(dmx_ctx* ctx, float* ms, int n_ms);
  * calls it for every pair process_list() makes (mode 'NW', repeated on the reverse complement
  * when the forward identity is below 0.5), and the 'HW' comparisons of finetune() (:840-852).
  * edlib is not vendored; edit distance has one right answer, so parity is pinned by a
- * full-matrix DP (dmx_pairdist_host).  Clustering is not replaced; the alignments of consensus
- * building are dmx_groupalign's, below.
+ * full-matrix DP (dmx_pairdist_host).  The best-hit filter and the gene groups that read these
+ * identities are dmx_pairhits / dmx_hitgroups, the alignments of consensus building
+ * dmx_groupalign's, both below.
  * Runs on the batch made resident by dmx_load.  Symbols: A, C, G, T and the no-match mask as a
  * fifth symbol (edlib compares bytes, so N equals N and nothing else).
  * DMX_PD_NW: Levenshtein distance of the two whole reads.  DMX_PD_HW: the least edit distance
@@ -458,6 +459,76 @@ int dmx_rowdist_host(const uint32_t* seq2b, const uint32_t* nmask, const uint64_
                      const uint64_t* row_off, const uint32_t* q, const uint32_t* r,
                      const uint32_t* caps, size_t n_pairs, uint32_t* out, int n_threads);
 float dmx_rowdist_ms(dmx_ctx* ctx);  /* device time of the last dmx_rowdist (HIP events) */
+
+/* ---- Gene groups: best-hit links and their connected components -----------------
+ * Replaces: what update_list() of amplicon_sorter.py does with the similarity lines (:983-1034:
+ * per longer read j the lines of the largest identity, ties kept; then greedy groups) and
+ * merge_groups() (:1058-1087: merged until nothing moves).  Every kept line i:j is an edge
+ * {i, j}, and the groups are the connected components of the edges.  Only a label per read
+ * leaves the device.  Not replaced: comp_consensus_groups (:1206, random sampling) onward, the
+ * species groups and the .group files. */
+#define DMX_LG_NONE 0xFFFFFFFFu  /* a node on no edge; a read with no hit; a pair with no outcome */
+#define DMX_LG_REV 0x80000000u   /* an outcome's reverse bit (the host twins' outcome words)      */
+#define DMX_LG_MAX_PAIRS 0x7FFFFFFFu /* pairs per dmx_pairhits, edges per dmx_edgegroups: places
+                                      * and counts are 32-bit on the device */
+/* Connected components of the undirected edges {a[e], b[e]} over nodes 0 .. n_nodes - 1:
+ * labels[v] = the smallest node of v's component, DMX_LG_NONE for a node on no edge (a node
+ * with only a self-loop is its own component).  Self-loops and repeated edges are allowed.  An
+ * endpoint >= n_nodes is DMX_E_INVALID (checked on the host before anything is launched), more
+ * than DMX_LG_MAX_PAIRS edges DMX_E_UNSUPPORTED.  Needs no resident batch.  Hooking by atomicMin
+ * on a parent array and pointer jumping, repeated until a round changes nothing; the result does
+ * not depend on the order the atomics land in.  Synchronous. */
+int dmx_edgegroups(dmx_ctx* ctx, const uint32_t* a, const uint32_t* b, size_t n_edges,
+                   uint32_t n_nodes, uint32_t* labels);
+/* Host only (no GPU; tests): the same contract by a sequential union-find.  Errors:
+ * dmx_last_error(NULL). */
+int dmx_edgegroups_host(const uint32_t* a, const uint32_t* b, size_t n_edges, uint32_t n_nodes,
+                        uint32_t* labels);
+/* The similarity pass over pairs of the resident batch with the hit decision on the device.
+ * cap_hit[i] / cap_half[i]: the largest distance whose identity is still >= the hit threshold /
+ * >= 0.5 for pair i's target length, -1 where there is none (a value below -1 is DMX_E_INVALID).
+ * Per pair: the forward NW distance df, capped at max(cap_hit, cap_half, 0); df <= cap_hit is a
+ * forward hit with d = df; otherwise, when cap_hit >= 0 and df > cap_half, the distance dr
+ * against the reverse-complemented target (DMX_PD_RC), capped at cap_hit, and dr <= cap_hit is a
+ * reverse hit with d = dr; otherwise the pair has no hit.  The outcomes stay on the device, in
+ * the context, until the next dmx_load, dmx_run, dmx_pairhits or dmx_close.  best[r] (one entry
+ * per read of the batch) = the least d over the hits whose target is r, DMX_LG_NONE where there
+ * is none; *n_hits = the number of hits.  The distances are dmx_pairdist's launches (the same
+ * kernel, chunks of DMX_PD_CHUNK pairs, same results whatever the chunk); per chunk only a
+ * bitmap of the pairs to retry comes back, and the retries run as launches of their own.
+ * Validation and the length limits are dmx_pairdist's; more than DMX_LG_MAX_PAIRS pairs is
+ * DMX_E_UNSUPPORTED.  Device memory: 20 bytes per pair beside dmx_pairdist's.  Synchronous. */
+int dmx_pairhits(dmx_ctx* ctx, const uint32_t* q, const uint32_t* t, const int32_t* cap_hit,
+                 const int32_t* cap_half, size_t n_pairs, uint32_t* best, uint64_t* n_hits);
+/* The hits of the last dmx_pairhits in ascending place in its pair list, compacted on the device
+ * (flag, prefix sum, scatter): pair[k] the place, d[k] the distance, rev[k] 1 for a reverse hit.
+ * *n = the number of hits, always; with cap below it nothing is written and the call is
+ * DMX_E_INVALID, as it is without valid dmx_pairhits outcomes. */
+int dmx_pairhits_fetch(dmx_ctx* ctx, uint32_t* pair, uint32_t* d, uint8_t* rev, size_t cap,
+                       size_t* n);
+/* The groups: the edges are the hits {q, t} of the last dmx_pairhits with d <= tie[t] (tie has
+ * one entry per read of the batch: the largest distance that still rounds to the identity of
+ * best[t], which the caller computes with the reference's own rounding; entries of reads
+ * without a hit are not read).  They are filtered by the compaction above and fed to
+ * dmx_edgegroups' kernels without leaving the device; labels as dmx_edgegroups', one per read.
+ * DMX_E_INVALID without valid dmx_pairhits outcomes. */
+int dmx_hitgroups(dmx_ctx* ctx, const uint32_t* tie, uint32_t* labels);
+/* Host only (no GPU; tests, ctx=None of dmx.sorter.gene_groups): dmx_pairhits on a dmx_pack
+ * layout, on dmx_pairdist_host; the state is the caller's: outcome[i] = d, d | DMX_LG_REV or
+ * DMX_LG_NONE for pair i.  Errors: dmx_last_error(NULL). */
+int dmx_pairhits_host(const uint32_t* seq2b, const uint32_t* nmask, const uint64_t* offsets,
+                      const uint32_t* lens, size_t n_reads, const uint32_t* q, const uint32_t* t,
+                      const int32_t* cap_hit, const int32_t* cap_half, size_t n_pairs,
+                      uint32_t* outcome, uint32_t* best, uint64_t* n_hits, int n_threads);
+/* Host only: dmx_hitgroups on the outcomes of dmx_pairhits_host and its pair list, by the
+ * sequential union-find. */
+int dmx_hitgroups_host(const uint32_t* q, const uint32_t* t, const uint32_t* outcome,
+                       size_t n_pairs, const uint32_t* tie, size_t n_reads, uint32_t* labels);
+/* Device time (ms, HIP events; first n_ms written): ms[0] the distance launches of the last
+ * dmx_pairhits, ms[1] the last compaction (dmx_pairhits_fetch, dmx_hitgroups), ms[2] the last
+ * components run (dmx_edgegroups, dmx_hitgroups; first kernel to last, the flag's trips to the
+ * host between the rounds included).  Returns that run's hooking rounds. */
+int dmx_hitgroups_stats(dmx_ctx* ctx, float* ms, int n_ms);
 
 #ifdef __cplusplus
 }

@@ -349,6 +349,7 @@ void dmx_close(dmx_ctx* c) {
     hipStreamSynchronize(c->stream);
     chop_release(c);
     pd_release(c);
+    lg_release(c);
     comm_release(c);
     void* bufs[] = {c->d_seq_alloc, c->d_nmask_alloc,     c->d_offs,     c->d_lens,      c->d_res,
                     c->d_winner[0], c->d_winner[1], c->d_origin[0], c->d_origin[1], c->d_lb[0], c->d_lb[1], c->d_cl[0],
@@ -912,6 +913,7 @@ int load_impl(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& mask, const uint
     c->executed = false;
     c->chunked = false;
     chop_invalidate(c);
+    lg_invalidate(c);
     return DMX_OK;
 }
 
@@ -1340,6 +1342,7 @@ int run_chunked(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& nmask,
     }
     c->n_reads = maxn;
     chop_invalidate(c);
+    lg_invalidate(c);
     c->chunked = false;
     std::vector<uint64_t> total, part;
     if ((rc = upload_chunk(c, ch[0], seq2b, nmask, offsets, lens))) return rc;

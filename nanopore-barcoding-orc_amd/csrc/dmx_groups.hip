@@ -1,0 +1,709 @@
+// dmx_groups.hip — gene groups on the device (include/dmx.h dmx_edgegroups, dmx_pairhits,
+// dmx_pairhits_fetch, dmx_hitgroups).  Replaces the best-hit filter and the
+// grouping of the amplicon-sorting stage (amplicon_sorter.py update_list :983-1034, merge_groups
+// :1058-1087): of the similarity pass only one label per read comes back.
+//
+// Three pieces:
+//   outcomes    what becomes of a launch of dmx_pairhits' distances (ph_decide_kernel): per input
+//               pair a distance and a reverse bit, or none; per read the least distance of the
+//               hits it is the target of (atomicMin); a bitmap of the pairs to try reversed.
+//   compaction  order-preserving: a flag per pair, the flags counted per block of 256
+//               (lg_count_kernel), the counts scanned by one block (lg_scan_kernel), and every
+//               kept pair written at its block's offset plus its rank in the block
+//               (lg_scatter_kernel).  It makes dmx_pairhits_fetch's hit list and dmx_hitgroups'
+//               edge list (the hits with d <= tie[t]).
+//   components  of an edge list over n nodes: parent[v] = v; rounds of hooking (every edge whose
+//               ends have different roots sets the larger root's parent to the smaller root,
+//               atomicMin) and pointer jumping (parent[v] = v's root), until a round hooks
+//               nothing; a last pass writes labels.  parent[v] <= v always holds, so there are no
+//               cycles, a root is the smallest node of its tree, and the result (the smallest
+//               node of the component) does not depend on the order the atomics land in.
+// The forward pass itself is dmx_pairdist's (dmx_pairdist.hip dmx_pairhits).
+#include <cstring>
+#include <numeric>
+
+#include "dmx_internal.h"
+
+namespace dmx {
+
+constexpr uint32_t kLgBlock = 256;                 // threads per block, one pair / edge / node each
+constexpr uint32_t kLgWaves = kLgBlock / 64;
+constexpr uint32_t kLgDist = ~(uint32_t)DMX_LG_REV;   // an outcome's distance bits
+
+struct LgState {
+    // the last dmx_pairhits: its pair list, and per pair the outcome (d | DMX_LG_REV, or
+    // DMX_LG_NONE); valid until the next dmx_load, dmx_pairhits or dmx_close
+    DevBuf<uint32_t> q, t, outc;
+    DevBuf<int32_t> cap_hit, cap_half;
+    DevBuf<uint32_t> best;           // per read of the batch
+    DevBuf<uint32_t> orig, need;     // per launch: sorted pair -> input pair; the retry bitmap
+    DevBuf<unsigned long long> cnt;  // hits
+    size_t n_pairs = 0, n_reads = 0;
+    uint64_t n_hits = 0;
+    bool valid = false;
+    // compaction: per-block counts / offsets, and what it writes (hits: pair, d, rev; edges: a, b)
+    DevBuf<uint32_t> blk, sel_a, sel_b;
+    DevBuf<uint8_t> sel_rev;
+    // components
+    DevBuf<uint32_t> parent, labels, tie, flag;
+    hipEvent_t ev[2] = {};
+    float ms[3] = {0.f, 0.f, 0.f};   // dmx_pairhits' forward launches, compaction, components
+    int rounds = 0;                  // hooking rounds of the last components run
+    ~LgState() {
+        for (auto& e : ev)
+            if (e) hipEventDestroy(e);
+    }
+};
+
+void lg_release(Ctx* c) {
+    delete c->lg;
+    c->lg = nullptr;
+}
+
+void lg_invalidate(Ctx* c) {
+    if (c->lg) c->lg->valid = false;   // the outcomes name reads of the previous resident batch
+}
+
+// ---- outcomes ----------------------------------------------------------------------------------
+
+struct PhDecide {
+    const uint32_t* dist;    // the launch's distances, min(d, cap + 1), in sorted order
+    const uint32_t* orig;    // sorted pair k is input pair orig[k]
+    uint32_t np, pass, lo;   // pass 0: forward, bit orig[k] - lo of need; pass 1: reverse
+    const int32_t* cap_hit;
+    const int32_t* cap_half;
+    const uint32_t* t;
+    uint32_t n_pairs, n_reads;
+    uint32_t* outc;
+    uint32_t* best;
+    uint32_t* need;
+    uint32_t need_words;
+    unsigned long long* cnt;
+};
+
+// The decisions of sorter.similarity on one launch's distances.  Forward: d <= cap_hit is a hit;
+// otherwise cap_hit >= 0 and d > cap_half asks for the reverse complement.  Reverse: d <= cap_hit
+// is a hit with the reverse bit.  The forward cap is max(cap_hit, cap_half, 0), so the clamped
+// distance compares against both caps as the exact one would.
+__global__ __launch_bounds__(kLgBlock) void ph_decide_kernel(PhDecide A) {
+    const uint32_t k = blockIdx.x * kLgBlock + threadIdx.x;
+    bool hit = false;
+    if (k < A.np) {
+        const uint32_t i = A.orig[k];
+        if (i < A.n_pairs) {
+            const int64_t d = A.dist[k], ch = A.cap_hit[i], chalf = A.cap_half[i];
+            hit = d <= ch;
+            if (A.pass == 0) {
+                A.outc[i] = hit ? (uint32_t)d : DMX_LG_NONE;
+                if (!hit && ch >= 0 && d > chalf) {
+                    const uint32_t b = i - A.lo;
+                    if ((b >> 5) < A.need_words) atomicOr(&A.need[b >> 5], 1u << (b & 31u));
+                }
+            } else if (hit) {
+                A.outc[i] = (uint32_t)d | DMX_LG_REV;
+            }
+            if (hit) {
+                const uint32_t r = A.t[i];
+                if (r < A.n_reads) atomicMin(&A.best[r], (uint32_t)d);
+            }
+        }
+    }
+    const uint64_t bal = __ballot(hit);   // every lane of the wave is here
+    if ((threadIdx.x & 63u) == 0 && bal) atomicAdd(A.cnt, (unsigned long long)__popcll(bal));
+}
+
+__global__ __launch_bounds__(kLgBlock) void lg_fill_kernel(uint32_t* p, uint32_t n, uint32_t v) {
+    const uint32_t i = blockIdx.x * kLgBlock + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// ---- compaction --------------------------------------------------------------------------------
+
+struct LgCompact {
+    const uint32_t* outc;
+    const uint32_t* q;
+    const uint32_t* t;
+    const uint32_t* tie;     // edges: per read, the largest distance kept
+    uint32_t n_pairs, n_reads;
+    uint32_t* blk;           // [block]: its count, then its offset; [n_blocks]: the total
+    uint32_t* out_a;         // hits: the pair's place in the input; edges: q
+    uint32_t* out_b;         // hits: d; edges: t
+    uint8_t* out_rev;        // hits: the reverse bit
+    uint32_t out_cap;
+};
+
+// Is pair i kept?  Hits: every pair with an outcome.  Edges: those with d <= tie[t].
+template <bool kEdges>
+__device__ __forceinline__ bool lg_keep(const LgCompact& A, uint32_t i) {
+    if (i >= A.n_pairs) return false;
+    const uint32_t o = A.outc[i];
+    if (o == DMX_LG_NONE) return false;
+    if constexpr (kEdges) {
+        const uint32_t r = A.t[i];
+        return r < A.n_reads && (o & kLgDist) <= A.tie[r];
+    } else {
+        return true;
+    }
+}
+
+// The flagged threads of the block before this one; *total: of the whole block.  Every thread of
+// the block calls it.
+__device__ __forceinline__ uint32_t lg_block_rank(bool f, uint32_t* total) {
+    __shared__ uint32_t wsum[kLgWaves];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint64_t bal = __ballot(f);
+    if (lane == 0) wsum[w] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t before = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kLgWaves; ++k) {
+        if (k < w) before += wsum[k];
+        tot += wsum[k];
+    }
+    *total = tot;
+    return before;
+}
+
+template <bool kEdges>
+__global__ __launch_bounds__(kLgBlock) void lg_count_kernel(LgCompact A) {
+    uint32_t tot;
+    lg_block_rank(lg_keep<kEdges>(A, blockIdx.x * kLgBlock + threadIdx.x), &tot);
+    if (threadIdx.x == 0) A.blk[blockIdx.x] = tot;
+}
+
+// One block: blk[b] becomes the sum of the counts before b, blk[nb] the total.
+__global__ __launch_bounds__(kLgBlock) void lg_scan_kernel(uint32_t* blk, uint32_t nb) {
+    __shared__ uint32_t wsum[kLgWaves];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nb; base += kLgBlock) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < nb ? blk[i] : 0u;
+        uint32_t x = v;   // the wave's inclusive scan
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)x, d);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63u) wsum[w] = x;
+        __syncthreads();
+        uint32_t off = 0, tot = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kLgWaves; ++k) {
+            if (k < w) off += wsum[k];
+            tot += wsum[k];
+        }
+        if (i < nb) blk[i] = carry + off + x - v;
+        carry += tot;
+        __syncthreads();   // wsum is written again in the next tile
+    }
+    if (threadIdx.x == 0) blk[nb] = carry;
+}
+
+template <bool kEdges>
+__global__ __launch_bounds__(kLgBlock) void lg_scatter_kernel(LgCompact A) {
+    const uint32_t i = blockIdx.x * kLgBlock + threadIdx.x;
+    const bool f = lg_keep<kEdges>(A, i);
+    uint32_t tot;
+    const uint32_t pos = A.blk[blockIdx.x] + lg_block_rank(f, &tot);
+    if (!f || pos >= A.out_cap) return;
+    if constexpr (kEdges) {
+        A.out_a[pos] = A.q[i];
+        A.out_b[pos] = A.t[i];
+    } else {
+        const uint32_t o = A.outc[i];
+        A.out_a[pos] = i;
+        A.out_b[pos] = o & kLgDist;
+        A.out_rev[pos] = (uint8_t)(o >> 31);
+    }
+}
+
+// ---- components --------------------------------------------------------------------------------
+
+// v's root.  parent[x] <= x for every x, so the walk only descends; a value another thread is
+// writing meanwhile is an ancestor either way.  n bounds the walk whatever the array holds.
+__device__ __forceinline__ uint32_t lg_root(const uint32_t* parent, uint32_t v, uint32_t n) {
+    for (uint32_t it = 0; it < n; ++it) {
+        const uint32_t p = parent[v];
+        if (p >= v) break;
+        v = p;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kLgBlock) void lg_init_kernel(uint32_t* parent, uint32_t* labels,
+                                                           uint32_t n) {
+    const uint32_t v = blockIdx.x * kLgBlock + threadIdx.x;
+    if (v >= n) return;
+    parent[v] = v;
+    labels[v] = DMX_LG_NONE;
+}
+
+// A node on an edge (a self-loop too) gets a label; which one, lg_flatten_kernel says.
+__global__ __launch_bounds__(kLgBlock) void lg_mark_kernel(const uint32_t* a, const uint32_t* b,
+                                                           uint32_t ne, uint32_t n,
+                                                           uint32_t* labels) {
+    const uint32_t e = blockIdx.x * kLgBlock + threadIdx.x;
+    if (e >= ne) return;
+    const uint32_t x = a[e], y = b[e];
+    if (x >= n || y >= n) return;
+    labels[x] = 0u;
+    labels[y] = 0u;
+}
+
+// Hooking.  The larger root's parent becomes at most the smaller root: were it lowered further by
+// another edge meanwhile, this edge's union is not recorded, but the flag is set and the next
+// round sees the edge again.  The first atomicMin of a round lands on a true root and lowers it,
+// so every round that sets the flag lowers some parent: the rounds end.
+__global__ __launch_bounds__(kLgBlock) void lg_hook_kernel(const uint32_t* a, const uint32_t* b,
+                                                           uint32_t ne, uint32_t n,
+                                                           uint32_t* parent, uint32_t* flag) {
+    const uint32_t e = blockIdx.x * kLgBlock + threadIdx.x;
+    if (e >= ne) return;
+    const uint32_t x = a[e], y = b[e];
+    if (x >= n || y >= n) return;
+    const uint32_t rx = lg_root(parent, x, n), ry = lg_root(parent, y, n);
+    if (rx == ry) return;
+    atomicMin(&parent[max(rx, ry)], min(rx, ry));
+    *flag = 1u;
+}
+
+// Pointer jumping, all the way: every tree becomes a star.
+__global__ __launch_bounds__(kLgBlock) void lg_jump_kernel(uint32_t* parent, uint32_t n) {
+    const uint32_t v = blockIdx.x * kLgBlock + threadIdx.x;
+    if (v >= n) return;
+    const uint32_t r = lg_root(parent, v, n);
+    if (r != parent[v]) parent[v] = r;
+}
+
+__global__ __launch_bounds__(kLgBlock) void lg_flatten_kernel(const uint32_t* parent,
+                                                              uint32_t* labels, uint32_t n) {
+    const uint32_t v = blockIdx.x * kLgBlock + threadIdx.x;
+    if (v >= n) return;
+    if (labels[v] != DMX_LG_NONE) labels[v] = lg_root(parent, v, n);
+}
+
+}  // namespace dmx
+
+using namespace dmx;
+
+namespace {
+
+#define LG_CK(who, call)                                                                     \
+    do {                                                                                     \
+        hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            c->err = std::string(who) + ": " + #call + ": " + hipGetErrorString(e_);         \
+            return DMX_E_HIP;                                                                \
+        }                                                                                    \
+    } while (0)
+
+inline uint32_t lg_blocks(size_t n) { return (uint32_t)((n + kLgBlock - 1) / kLgBlock); }
+
+int lg_state(Ctx* c, const char* who) {
+    LG_CK(who, hipSetDevice(c->device));
+    if (!c->lg) {
+        c->lg = new LgState();
+        for (auto& e : c->lg->ev) LG_CK(who, hipEventCreate(&e));
+    }
+    return DMX_OK;
+}
+
+// The compaction of the last dmx_pairhits' outcomes into sel_a / sel_b (/ sel_rev), room for
+// `cap` entries; *total = how many are kept.  Synchronises; ms[1] = its device time.
+template <bool kEdges>
+int lg_compact(Ctx* c, const char* who, size_t cap, uint32_t* total) {
+    LgState* s = c->lg;
+    hipStream_t st = c->stream;
+    *total = 0;
+    s->ms[1] = 0.f;
+    if (!s->n_pairs) return DMX_OK;
+    const uint32_t nb = lg_blocks(s->n_pairs);
+    LG_CK(who, s->blk.reserve((size_t)nb + 1));
+    LG_CK(who, s->sel_a.reserve(cap));
+    LG_CK(who, s->sel_b.reserve(cap));
+    if (!kEdges) LG_CK(who, s->sel_rev.reserve(cap));
+    LgCompact A;
+    A.outc = s->outc.p, A.q = s->q.p, A.t = s->t.p, A.tie = s->tie.p;
+    A.n_pairs = (uint32_t)s->n_pairs, A.n_reads = (uint32_t)s->n_reads;
+    A.blk = s->blk.p, A.out_a = s->sel_a.p, A.out_b = s->sel_b.p, A.out_rev = s->sel_rev.p;
+    A.out_cap = (uint32_t)cap;
+    LG_CK(who, hipEventRecord(s->ev[0], st));
+    hipLaunchKernelGGL(lg_count_kernel<kEdges>, dim3(nb), dim3(kLgBlock), 0, st, A);
+    hipLaunchKernelGGL(lg_scan_kernel, dim3(1), dim3(kLgBlock), 0, st, s->blk.p, nb);
+    hipLaunchKernelGGL(lg_scatter_kernel<kEdges>, dim3(nb), dim3(kLgBlock), 0, st, A);
+    LG_CK(who, hipGetLastError());
+    LG_CK(who, hipEventRecord(s->ev[1], st));
+    LG_CK(who, hipMemcpyAsync(total, s->blk.p + nb, 4, hipMemcpyDeviceToHost, st));
+    LG_CK(who, hipStreamSynchronize(st));
+    hipEventElapsedTime(&s->ms[1], s->ev[0], s->ev[1]);
+    return DMX_OK;
+}
+
+// The components of the device edge list (d_a, d_b) over n nodes into s->labels.  ms[2] = the
+// time from the first kernel to the last, the flag's trips to the host between the rounds
+// included.  Synchronises.
+int lg_components(Ctx* c, const char* who, const uint32_t* d_a, const uint32_t* d_b, uint32_t ne,
+                  uint32_t n) {
+    LgState* s = c->lg;
+    hipStream_t st = c->stream;
+    s->ms[2] = 0.f;
+    s->rounds = 0;
+    if (!n) return DMX_OK;
+    const uint32_t vb = lg_blocks(n), eb = lg_blocks(ne);
+    LG_CK(who, s->parent.reserve(n));
+    LG_CK(who, s->labels.reserve(n));
+    LG_CK(who, s->flag.reserve(1));
+    LG_CK(who, hipEventRecord(s->ev[0], st));
+    hipLaunchKernelGGL(lg_init_kernel, dim3(vb), dim3(kLgBlock), 0, st, s->parent.p, s->labels.p, n);
+    if (ne) {
+        hipLaunchKernelGGL(lg_mark_kernel, dim3(eb), dim3(kLgBlock), 0, st, d_a, d_b, ne, n,
+                           s->labels.p);
+        // every round that goes on lowers a parent, so n rounds are never reached (lg_hook_kernel)
+        for (uint32_t round = 0;; ++round) {
+            uint32_t changed = 0;
+            LG_CK(who, hipMemsetAsync(s->flag.p, 0, 4, st));
+            hipLaunchKernelGGL(lg_hook_kernel, dim3(eb), dim3(kLgBlock), 0, st, d_a, d_b, ne, n,
+                               s->parent.p, s->flag.p);
+            LG_CK(who, hipGetLastError());
+            LG_CK(who, hipMemcpyAsync(&changed, s->flag.p, 4, hipMemcpyDeviceToHost, st));
+            LG_CK(who, hipStreamSynchronize(st));
+            s->rounds = (int)round + 1;
+            if (!changed) break;
+            if (round >= n) {
+                c->err = std::string(who) + ": the hooking rounds did not end";
+                return DMX_E_STATE;
+            }
+            hipLaunchKernelGGL(lg_jump_kernel, dim3(vb), dim3(kLgBlock), 0, st, s->parent.p, n);
+        }
+        hipLaunchKernelGGL(lg_flatten_kernel, dim3(vb), dim3(kLgBlock), 0, st, s->parent.p,
+                           s->labels.p, n);
+    }
+    LG_CK(who, hipGetLastError());
+    LG_CK(who, hipEventRecord(s->ev[1], st));
+    LG_CK(who, hipStreamSynchronize(st));
+    hipEventElapsedTime(&s->ms[2], s->ev[0], s->ev[1]);
+    return DMX_OK;
+}
+
+// The sequential union-find of the host twins: the root of a tree is its smallest node.
+struct HostSets {
+    std::vector<uint32_t> parent;
+    explicit HostSets(size_t n) : parent(n) { std::iota(parent.begin(), parent.end(), 0u); }
+    uint32_t find(uint32_t v) {
+        uint32_t r = v;
+        while (parent[r] != r) r = parent[r];
+        while (parent[v] != r) {
+            const uint32_t up = parent[v];
+            parent[v] = r;
+            v = up;
+        }
+        return r;
+    }
+    void join(uint32_t x, uint32_t y) {
+        const uint32_t rx = find(x), ry = find(y);
+        if (rx != ry) parent[std::max(rx, ry)] = std::min(rx, ry);
+    }
+};
+
+// 0, or DMX_E_INVALID with *err naming the first edge with an end outside the nodes.
+int lg_validate_edges(const char* who, const uint32_t* a, const uint32_t* b, size_t n_edges,
+                      uint32_t n_nodes, std::string* err) {
+    for (size_t e = 0; e < n_edges; ++e)
+        if (a[e] >= n_nodes || b[e] >= n_nodes) {
+            *err = std::string(who) + ": edge " + std::to_string(e) + " names a node outside the " +
+                   std::to_string(n_nodes) + " given";
+            return DMX_E_INVALID;
+        }
+    return DMX_OK;
+}
+
+void lg_host_labels(const uint32_t* a, const uint32_t* b, size_t n_edges, size_t n_nodes,
+                    uint32_t* labels) {
+    HostSets hs(n_nodes);
+    std::vector<uint8_t> on(n_nodes, 0);
+    for (size_t e = 0; e < n_edges; ++e) {
+        on[a[e]] = on[b[e]] = 1;
+        hs.join(a[e], b[e]);
+    }
+    for (size_t v = 0; v < n_nodes; ++v) labels[v] = on[v] ? hs.find((uint32_t)v) : DMX_LG_NONE;
+}
+
+}  // namespace
+
+// ---- dmx_pairhits' device-side bookkeeping (dmx_internal.h) ------------------------------------
+
+namespace dmx {
+
+int lg_hits_begin(Ctx* c, const char* who, const uint32_t* q, const uint32_t* t,
+                  const int32_t* cap_hit, const int32_t* cap_half, size_t n_pairs, size_t n_reads) {
+    if (const int rc = lg_state(c, who)) return rc;
+    LgState* s = c->lg;
+    hipStream_t st = c->stream;
+    s->valid = false;
+    s->n_pairs = n_pairs;
+    s->n_reads = n_reads;
+    s->n_hits = 0;
+    s->ms[0] = 0.f;
+    LG_CK(who, s->q.reserve(n_pairs));
+    LG_CK(who, s->t.reserve(n_pairs));
+    LG_CK(who, s->outc.reserve(n_pairs));
+    LG_CK(who, s->cap_hit.reserve(n_pairs));
+    LG_CK(who, s->cap_half.reserve(n_pairs));
+    LG_CK(who, s->best.reserve(n_reads));
+    LG_CK(who, s->cnt.reserve(1));
+    if (n_pairs) {
+        LG_CK(who, hipMemcpyAsync(s->q.p, q, n_pairs * 4, hipMemcpyHostToDevice, st));
+        LG_CK(who, hipMemcpyAsync(s->t.p, t, n_pairs * 4, hipMemcpyHostToDevice, st));
+        LG_CK(who, hipMemcpyAsync(s->cap_hit.p, cap_hit, n_pairs * 4, hipMemcpyHostToDevice, st));
+        LG_CK(who, hipMemcpyAsync(s->cap_half.p, cap_half, n_pairs * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(lg_fill_kernel, dim3(lg_blocks(n_pairs)), dim3(kLgBlock), 0, st,
+                           s->outc.p, (uint32_t)n_pairs, (uint32_t)DMX_LG_NONE);
+    }
+    if (n_reads)
+        hipLaunchKernelGGL(lg_fill_kernel, dim3(lg_blocks(n_reads)), dim3(kLgBlock), 0, st,
+                           s->best.p, (uint32_t)n_reads, (uint32_t)DMX_LG_NONE);
+    LG_CK(who, hipGetLastError());
+    LG_CK(who, hipMemsetAsync(s->cnt.p, 0, sizeof(unsigned long long), st));
+    LG_CK(who, hipStreamSynchronize(st));   // the caller's arrays are pageable
+    return DMX_OK;
+}
+
+int lg_hits_decide(Ctx* c, const char* who, const uint32_t* d_dist, const uint32_t* orig, size_t np,
+                   int pass, size_t lo, std::vector<uint32_t>* need) {
+    LgState* s = c->lg;
+    hipStream_t st = c->stream;
+    const size_t words = (np + 31) / 32;
+    LG_CK(who, s->orig.reserve(np));
+    LG_CK(who, s->need.reserve(words));
+    LG_CK(who, hipMemcpyAsync(s->orig.p, orig, np * 4, hipMemcpyHostToDevice, st));
+    if (pass == 0) LG_CK(who, hipMemsetAsync(s->need.p, 0, words * 4, st));
+    PhDecide A;
+    A.dist = d_dist, A.orig = s->orig.p;
+    A.np = (uint32_t)np, A.pass = (uint32_t)pass, A.lo = (uint32_t)lo;
+    A.cap_hit = s->cap_hit.p, A.cap_half = s->cap_half.p, A.t = s->t.p;
+    A.n_pairs = (uint32_t)s->n_pairs, A.n_reads = (uint32_t)s->n_reads;
+    A.outc = s->outc.p, A.best = s->best.p, A.need = s->need.p;
+    A.need_words = pass == 0 ? (uint32_t)words : 0u;
+    A.cnt = s->cnt.p;
+    hipLaunchKernelGGL(ph_decide_kernel, dim3(lg_blocks(np)), dim3(kLgBlock), 0, st, A);
+    LG_CK(who, hipGetLastError());
+    if (pass == 0 && need) {
+        need->resize(words);
+        LG_CK(who, hipMemcpyAsync(need->data(), s->need.p, words * 4, hipMemcpyDeviceToHost, st));
+    }
+    LG_CK(who, hipStreamSynchronize(st));
+    return DMX_OK;
+}
+
+int lg_hits_end(Ctx* c, const char* who, float forward_ms, uint32_t* best, uint64_t* n_hits) {
+    LgState* s = c->lg;
+    hipStream_t st = c->stream;
+    unsigned long long cnt = 0;
+    LG_CK(who, hipMemcpyAsync(&cnt, s->cnt.p, sizeof cnt, hipMemcpyDeviceToHost, st));
+    if (s->n_reads)
+        LG_CK(who, hipMemcpyAsync(best, s->best.p, s->n_reads * 4, hipMemcpyDeviceToHost, st));
+    LG_CK(who, hipStreamSynchronize(st));
+    s->n_hits = cnt;
+    s->ms[0] = forward_ms;
+    s->valid = true;
+    *n_hits = cnt;
+    return DMX_OK;
+}
+
+}  // namespace dmx
+
+// ---- the entry points (include/dmx.h) -----------------------------------------------------------
+
+extern "C" int dmx_edgegroups_host(const uint32_t* a, const uint32_t* b, size_t n_edges,
+                                   uint32_t n_nodes, uint32_t* labels) {
+    const char* const who = "dmx_edgegroups_host";
+    if ((n_edges && (!a || !b)) || (n_nodes && !labels)) {
+        set_process_error(std::string(who) + ": null argument");
+        return DMX_E_INVALID;
+    }
+    std::string err;
+    if (const int rc = lg_validate_edges(who, a, b, n_edges, n_nodes, &err)) {
+        set_process_error(err);
+        return rc;
+    }
+    lg_host_labels(a, b, n_edges, n_nodes, labels);
+    return DMX_OK;
+}
+
+extern "C" int dmx_edgegroups(dmx_ctx* c, const uint32_t* a, const uint32_t* b, size_t n_edges,
+                              uint32_t n_nodes, uint32_t* labels) {
+    const char* const who = "dmx_edgegroups";
+    if (!c) return DMX_E_INVALID;
+    if ((n_edges && (!a || !b)) || (n_nodes && !labels)) {
+        c->err = "dmx_edgegroups: null edge list or output";
+        return DMX_E_INVALID;
+    }
+    if (n_edges > DMX_LG_MAX_PAIRS) {
+        c->err = "dmx_edgegroups: at most " + std::to_string(DMX_LG_MAX_PAIRS) + " edges supported";
+        return DMX_E_UNSUPPORTED;
+    }
+    if (const int rc = lg_validate_edges(who, a, b, n_edges, n_nodes, &c->err)) return rc;
+    if (!n_nodes) return DMX_OK;
+    if (const int rc = lg_state(c, who)) return rc;
+    LgState* s = c->lg;
+    hipStream_t st = c->stream;
+    LG_CK(who, s->sel_a.reserve(n_edges));
+    LG_CK(who, s->sel_b.reserve(n_edges));
+    if (n_edges) {
+        LG_CK(who, hipMemcpyAsync(s->sel_a.p, a, n_edges * 4, hipMemcpyHostToDevice, st));
+        LG_CK(who, hipMemcpyAsync(s->sel_b.p, b, n_edges * 4, hipMemcpyHostToDevice, st));
+    }
+    if (const int rc = lg_components(c, who, s->sel_a.p, s->sel_b.p, (uint32_t)n_edges, n_nodes))
+        return rc;
+    LG_CK(who, hipMemcpy(labels, s->labels.p, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
+    return DMX_OK;
+}
+
+extern "C" int dmx_pairhits_host(const uint32_t* seq2b, const uint32_t* nmask,
+                                 const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
+                                 const uint32_t* q, const uint32_t* t, const int32_t* cap_hit,
+                                 const int32_t* cap_half, size_t n_pairs, uint32_t* outcome,
+                                 uint32_t* best, uint64_t* n_hits, int n_threads) {
+    const char* const who = "dmx_pairhits_host";
+    if (!n_hits || (n_reads && !best) || (n_pairs && (!q || !t || !cap_hit || !cap_half || !outcome))) {
+        set_process_error(std::string(who) + ": null argument");
+        return DMX_E_INVALID;
+    }
+    for (size_t i = 0; i < n_pairs; ++i)
+        if (cap_hit[i] < -1 || cap_half[i] < -1) {
+            set_process_error(std::string(who) + ": pair " + std::to_string(i) +
+                              ": a cap is a distance, or -1 for none");
+            return DMX_E_INVALID;
+        }
+    std::vector<uint32_t> fcap(n_pairs), df(n_pairs);
+    for (size_t i = 0; i < n_pairs; ++i)
+        fcap[i] = (uint32_t)std::max(std::max(cap_hit[i], cap_half[i]), 0);
+    if (const int rc = dmx_pairdist_host(DMX_PD_NW, seq2b, nmask, offsets, lens, n_reads, q, t,
+                                         nullptr, fcap.data(), n_pairs, df.data(), n_threads))
+        return rc;
+    std::vector<uint32_t> rq, rt, rcap, ri;
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const int64_t d = df[i];
+        outcome[i] = d <= cap_hit[i] ? df[i] : DMX_LG_NONE;
+        if (d > cap_hit[i] && cap_hit[i] >= 0 && d > cap_half[i]) {
+            ri.push_back((uint32_t)i);
+            rq.push_back(q[i]);
+            rt.push_back(t[i]);
+            rcap.push_back((uint32_t)cap_hit[i]);
+        }
+    }
+    std::vector<uint8_t> rflags(ri.size(), DMX_PD_RC);
+    std::vector<uint32_t> dr(ri.size());
+    if (const int rc = dmx_pairdist_host(DMX_PD_NW, seq2b, nmask, offsets, lens, n_reads, rq.data(),
+                                         rt.data(), rflags.data(), rcap.data(), ri.size(),
+                                         dr.data(), n_threads))
+        return rc;
+    for (size_t k = 0; k < ri.size(); ++k)
+        if (dr[k] <= rcap[k]) outcome[ri[k]] = dr[k] | DMX_LG_REV;
+    for (size_t r = 0; r < n_reads; ++r) best[r] = DMX_LG_NONE;
+    uint64_t hits = 0;
+    for (size_t i = 0; i < n_pairs; ++i)
+        if (outcome[i] != DMX_LG_NONE) {
+            ++hits;
+            best[t[i]] = std::min(best[t[i]], outcome[i] & kLgDist);
+        }
+    *n_hits = hits;
+    return DMX_OK;
+}
+
+extern "C" int dmx_hitgroups_host(const uint32_t* q, const uint32_t* t, const uint32_t* outcome,
+                                  size_t n_pairs, const uint32_t* tie, size_t n_reads,
+                                  uint32_t* labels) {
+    const char* const who = "dmx_hitgroups_host";
+    if ((n_pairs && (!q || !t || !outcome)) || (n_reads && (!tie || !labels))) {
+        set_process_error(std::string(who) + ": null argument (no dmx_pairhits_host outcomes?)");
+        return DMX_E_INVALID;
+    }
+    if (n_reads > DMX_LG_NONE) {
+        set_process_error(std::string(who) + ": too many reads");
+        return DMX_E_UNSUPPORTED;
+    }
+    std::string err;
+    if (const int rc = lg_validate_edges(who, q, t, n_pairs, (uint32_t)n_reads, &err)) {
+        set_process_error(err);
+        return rc;
+    }
+    std::vector<uint32_t> a, b;
+    for (size_t i = 0; i < n_pairs; ++i)
+        if (outcome[i] != DMX_LG_NONE && (outcome[i] & kLgDist) <= tie[t[i]]) {
+            a.push_back(q[i]);
+            b.push_back(t[i]);
+        }
+    lg_host_labels(a.data(), b.data(), a.size(), n_reads, labels);
+    return DMX_OK;
+}
+
+extern "C" int dmx_pairhits_fetch(dmx_ctx* c, uint32_t* pair, uint32_t* d, uint8_t* rev, size_t cap,
+                                  size_t* n) {
+    const char* const who = "dmx_pairhits_fetch";
+    if (!c) return DMX_E_INVALID;
+    if (!n) {
+        c->err = "dmx_pairhits_fetch: null count";
+        return DMX_E_INVALID;
+    }
+    *n = 0;
+    if (!c->lg || !c->lg->valid) {
+        c->err = "dmx_pairhits_fetch: no dmx_pairhits since the last dmx_load";
+        return DMX_E_INVALID;
+    }
+    LgState* s = c->lg;
+    *n = (size_t)s->n_hits;
+    if (!s->n_hits) return DMX_OK;
+    if (cap < s->n_hits || !pair || !d || !rev) {
+        c->err = "dmx_pairhits_fetch: room for " + std::to_string(cap) + " hits, " +
+                 std::to_string(s->n_hits) + " to return";
+        return DMX_E_INVALID;
+    }
+    LG_CK(who, hipSetDevice(c->device));
+    uint32_t total = 0;
+    if (const int rc = lg_compact<false>(c, who, (size_t)s->n_hits, &total)) return rc;
+    if (total != s->n_hits) {
+        c->err = "dmx_pairhits_fetch: the compaction kept " + std::to_string(total) + " of " +
+                 std::to_string(s->n_hits) + " hits";
+        return DMX_E_STATE;
+    }
+    LG_CK(who, hipMemcpy(pair, s->sel_a.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    LG_CK(who, hipMemcpy(d, s->sel_b.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    LG_CK(who, hipMemcpy(rev, s->sel_rev.p, (size_t)total, hipMemcpyDeviceToHost));
+    return DMX_OK;
+}
+
+extern "C" int dmx_hitgroups(dmx_ctx* c, const uint32_t* tie, uint32_t* labels) {
+    const char* const who = "dmx_hitgroups";
+    if (!c) return DMX_E_INVALID;
+    if (!c->lg || !c->lg->valid) {
+        c->err = "dmx_hitgroups: no dmx_pairhits since the last dmx_load";
+        return DMX_E_INVALID;
+    }
+    LgState* s = c->lg;
+    if (!s->n_reads) return DMX_OK;
+    if (!tie || !labels) {
+        c->err = "dmx_hitgroups: null tie table or output";
+        return DMX_E_INVALID;
+    }
+    LG_CK(who, hipSetDevice(c->device));
+    LG_CK(who, s->tie.reserve(s->n_reads));
+    LG_CK(who, hipMemcpyAsync(s->tie.p, tie, s->n_reads * 4, hipMemcpyHostToDevice, c->stream));
+    uint32_t n_edges = 0;
+    if (const int rc = lg_compact<true>(c, who, (size_t)s->n_hits, &n_edges)) return rc;
+    if (n_edges > s->n_hits) {
+        c->err = "dmx_hitgroups: the compaction kept more edges than there are hits";
+        return DMX_E_STATE;
+    }
+    if (const int rc = lg_components(c, who, s->sel_a.p, s->sel_b.p, n_edges, (uint32_t)s->n_reads))
+        return rc;
+    LG_CK(who, hipMemcpy(labels, s->labels.p, s->n_reads * 4, hipMemcpyDeviceToHost));
+    return DMX_OK;
+}
+
+extern "C" int dmx_hitgroups_stats(dmx_ctx* c, float* ms, int n_ms) {
+    if (!c) return DMX_E_INVALID;
+    for (int k = 0; k < n_ms && k < 3 && ms; ++k) ms[k] = c->lg ? c->lg->ms[k] : 0.f;
+    return c->lg ? c->lg->rounds : 0;
+}

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -17,6 +18,30 @@ struct PdState;     // pairwise read distance (dmx_pairdist.hip)
 struct PaState;     // pairwise alignment with edit path (dmx_pairdist.hip)
 struct GaState;     // progressive alignment of read groups (dmx_pairdist.hip)
 struct RdState;     // read distance against rows of masks (dmx_pairdist.hip)
+struct LgState;     // hits of dmx_pairhits, link groups (dmx_groups.hip)
+
+// A device buffer that grows on demand, never shrinks, and is freed with its owner.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;   // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) hipFree(p);
+    }
+    hipError_t reserve(size_t n) {   // room for n elements (one at least); the content is not kept
+        if (p && cap >= n) return hipSuccess;
+        if (p) hipFree(p);
+        p = nullptr;
+        cap = 0;
+        n = std::max<size_t>(n, 1);
+        const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
+        if (e == hipSuccess) cap = n;
+        return e;
+    }
+};
 
 // Reach of a panel's gathers around a view, in nt (panel_reach below).
 struct PanelReach {
@@ -148,6 +173,7 @@ struct Ctx {
     PaState* pa = nullptr;       // dmx_pairalign buffers, created by its first call
     GaState* ga = nullptr;       // dmx_groupalign buffers, created by its first call
     RdState* rd = nullptr;       // dmx_rowdist buffers, created by its first call
+    LgState* lg = nullptr;       // dmx_pairhits' outcomes and the link-group buffers
 
     // RCCL communicator for the per-bin count exchange (dmx_comm.cpp)
     ncclComm* comm = nullptr;
@@ -158,6 +184,7 @@ struct Ctx {
 
 void chop_release(Ctx* c);
 void pd_release(Ctx* c);
+void lg_release(Ctx* c);
 void comm_release(Ctx* c);
 int reset_counts(Ctx* c);      // size d_counts for the current panels/mode and zero it (sync)
 // The last error of a call that has no context to keep it in (dmx_comm_unique_id's RCCL load),
@@ -165,6 +192,19 @@ int reset_counts(Ctx* c);      // size d_counts for the current panels/mode and 
 void set_process_error(const std::string& msg);
 std::string process_error();
 void chop_invalidate(Ctx* c);   // a new dmx_load makes the last dmx_chop_exec's results stale
+void lg_invalidate(Ctx* c);     // ... and the last dmx_pairhits' outcomes
+// dmx_pairhits (dmx_pairdist.hip) runs the distance form's launches; what becomes of a launch's
+// distances stays on the device and is dmx_groups.hip's:
+// lg_hits_begin uploads the call's pair list and caps and clears the outcomes;
+// lg_hits_decide turns the distances `d_dist` of one launch (sorted pair k is input pair
+// orig[k]) into outcomes: pass 0 the forward decisions, with bit i - lo of `need` set where input
+// pair i has to be tried on the reverse complement, pass 1 the reverse decisions (synchronises);
+// lg_hits_end brings down best[] and the number of hits and makes the state valid.
+int lg_hits_begin(Ctx* c, const char* who, const uint32_t* q, const uint32_t* t,
+                  const int32_t* cap_hit, const int32_t* cap_half, size_t n_pairs, size_t n_reads);
+int lg_hits_decide(Ctx* c, const char* who, const uint32_t* d_dist, const uint32_t* orig, size_t np,
+                   int pass, size_t lo, std::vector<uint32_t>* need);
+int lg_hits_end(Ctx* c, const char* who, float forward_ms, uint32_t* best, uint64_t* n_hits);
 // Round `round` resolves its candidates with the band kernels (every adapter has kk <= 7 and
 // DMX_RESOLVE=ring is not set): its winner keys carry their origin (make_key_o), and nothing
 // reads or writes d_origin[round].

@@ -133,29 +133,6 @@ struct RdArgs : PdHead<RdPair> {
     uint32_t* out;               // per pair: the distance
 };
 
-// A device buffer that grows on demand, never shrinks, and is freed with its owner.
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;   // elements
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
-        if (p) hipFree(p);
-    }
-    hipError_t reserve(size_t n) {   // room for n elements (one at least); the content is not kept
-        if (p && cap >= n) return hipSuccess;
-        if (p) hipFree(p);
-        p = nullptr;
-        cap = 0;
-        n = std::max<size_t>(n, 1);
-        const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-};
-
 // The buffers and events of either form; they go with the context (pd_release).
 template <class Pair>
 struct PdBufs {
@@ -968,6 +945,101 @@ extern "C" int dmx_pairdist(dmx_ctx* c, int mode, const uint32_t* q, const uint3
     }
     s->ms = total_ms;
     return DMX_OK;
+}
+
+// ---- dmx_pairhits: dmx_pairdist's launches, the hit decision on the device ------
+// The distances of a launch stay in the distance form's output buffer; dmx_groups.hip turns them
+// into outcomes there (lg_hits_decide) and only the bitmap of the pairs to retry on the reverse
+// complement comes back.  The retries of all chunks are planned again as a list of their own.
+
+extern "C" int dmx_pairhits(dmx_ctx* c, const uint32_t* q, const uint32_t* t,
+                            const int32_t* cap_hit, const int32_t* cap_half, size_t n_pairs,
+                            uint32_t* best, uint64_t* n_hits) {
+    const char* const who = "dmx_pairhits";
+    if (!c) return DMX_E_INVALID;
+    lg_invalidate(c);
+    const size_t n_reads = c->d_seq ? c->n_reads : 0;
+    if (!n_hits || (n_reads && !best) || (n_pairs && (!q || !t || !cap_hit || !cap_half))) {
+        c->err = "dmx_pairhits: null pair list, caps or output";
+        return DMX_E_INVALID;
+    }
+    if (n_pairs > DMX_LG_MAX_PAIRS) {
+        c->err = "dmx_pairhits: at most " + std::to_string(DMX_LG_MAX_PAIRS) + " pairs supported";
+        return DMX_E_UNSUPPORTED;
+    }
+    std::vector<uint32_t> lens;
+    if (const int rc = pd_fetch_lens(c, who, n_pairs, lens)) return rc;
+    if (const int rc = pd_validate(who, DMX_PD_NW, lens.data(), lens.size(), q, t, nullptr, n_pairs,
+                                   &c->err))
+        return rc;
+    std::vector<uint32_t> fcap(n_pairs);
+    for (size_t i = 0; i < n_pairs; ++i) {
+        if (cap_hit[i] < -1 || cap_half[i] < -1) {
+            c->err = "dmx_pairhits: pair " + std::to_string(i) +
+                     ": a cap is a distance, or -1 for none";
+            return DMX_E_INVALID;
+        }
+        fcap[i] = (uint32_t)std::max(std::max(cap_hit[i], cap_half[i]), 0);
+    }
+    PD_CK(who, hipSetDevice(c->device));
+    if (const int rc = lg_hits_begin(c, who, q, t, cap_hit, cap_half, n_pairs, n_reads)) return rc;
+    float total_ms = 0.f;
+    if (n_pairs) {
+        if (const int rc = pd_state(c, who, c->pd)) return rc;
+        PdState* s = c->pd;   // dmx_pairdist's buffers; its ms stays its own
+        hipStream_t st = c->stream;
+        const size_t chunk = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+        PdPlan<PdPair> pl;
+        std::vector<uint32_t> orig, need, retry;
+        // one launch of pairs[lo .. ) of a list; in[k]: the input pair of the list's pair k
+        auto launch = [&](const uint32_t* lq, const uint32_t* lt, const uint8_t* lf,
+                          const uint32_t* lcap, size_t n, size_t lo, const uint32_t* in, int pass,
+                          size_t* end) -> int {
+            const size_t hi = pd_plan(pl, lens.data(), lq, lt, lf, lcap, n, lo, chunk, kPdNoBudget);
+            const size_t np = hi - lo;
+            PdArgs A;
+            if (const int rc = pd_stage(c, who, *s, pl, np, kKerPairdist, A)) return rc;
+            A.mode = DMX_PD_NW;
+            A.out = s->out.p;
+            PD_CK(who, hipEventRecord(s->ev[0], st));
+            pd_launch_forward(pairdist_kernel, A, st);
+            PD_CK(who, hipGetLastError());
+            PD_CK(who, hipEventRecord(s->ev[1], st));
+            orig.resize(np);
+            for (size_t k = 0; k < np; ++k)
+                orig[k] = in ? in[lo + pl.place(k)] : (uint32_t)(lo + pl.place(k));
+            if (const int rc = lg_hits_decide(c, who, A.out, orig.data(), np, pass, lo, &need))
+                return rc;
+            if (const int brc = bounds_check(c, who)) return brc;
+            float ms = 0.f;
+            hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+            total_ms += ms;
+            *end = hi;
+            return DMX_OK;
+        };
+        for (size_t lo = 0, hi = 0; lo < n_pairs; lo = hi) {
+            if (const int rc = launch(q, t, nullptr, fcap.data(), n_pairs, lo, nullptr, 0, &hi))
+                return rc;
+            for (size_t w = 0; w < need.size(); ++w)
+                for (uint32_t bits = need[w]; bits; bits &= bits - 1u) {
+                    const size_t b = 32 * w + (size_t)__builtin_ctz(bits);
+                    if (b < hi - lo) retry.push_back((uint32_t)(lo + b));
+                }
+        }
+        const size_t n2 = retry.size();
+        std::vector<uint32_t> q2(n2), t2(n2), cap2(n2);
+        const std::vector<uint8_t> rc2(n2, DMX_PD_RC);
+        for (size_t k = 0; k < n2; ++k) {
+            q2[k] = q[retry[k]];
+            t2[k] = t[retry[k]];
+            cap2[k] = (uint32_t)cap_hit[retry[k]];   // >= 0 where a retry is asked for
+        }
+        for (size_t lo = 0, hi = 0; lo < n2; lo = hi)
+            if (const int rc = launch(q2.data(), t2.data(), rc2.data(), cap2.data(), n2, lo,
+                                      retry.data(), 1, &hi))
+                return rc;
+    }
+    return lg_hits_end(c, who, total_ms, best, n_hits);
 }
 
 // ---- dmx_pairalign: the NW distance and the edit path (include/dmx.h) -----------

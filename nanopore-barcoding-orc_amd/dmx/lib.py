@@ -43,7 +43,9 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_debug_bounds_selftest", "dmx_panel_pieces", "dmx_pairdist", "dmx_pairdist_host",
            "dmx_pairdist_group_sizes", "dmx_pairalign", "dmx_pairalign_host",
            "dmx_pairalign_stats", "dmx_groupalign", "dmx_groupalign_host", "dmx_groupalign_stats",
-           "dmx_rowdist", "dmx_rowdist_host"]
+           "dmx_rowdist", "dmx_rowdist_host", "dmx_edgegroups", "dmx_edgegroups_host",
+           "dmx_pairhits", "dmx_pairhits_fetch", "dmx_hitgroups", "dmx_pairhits_host",
+           "dmx_hitgroups_host", "dmx_hitgroups_stats"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -52,6 +54,8 @@ LOC_IGNORE_CASE, LOC_ONLY_POSITIVE = 0x1, 0x2
 PD_NW, PD_HW, PD_RC, PD_MAX_LEN = 0, 1, 0x1, 16384
 # include/dmx.h dmx_pairalign: the ops of an edit path (edlib's numbering)
 PA_MATCH, PA_INSERT, PA_DELETE, PA_MISMATCH = 0, 1, 2, 3
+# include/dmx.h dmx_edgegroups / dmx_pairhits: no label, no hit; an outcome's reverse bit
+LG_NONE, LG_REV = 0xFFFFFFFF, 0x80000000
 HIT_DTYPE = np.dtype([("seq", "<u8"), ("pattern", "<i4"), ("strand", "<i4"), ("start", "<i4"),
                       ("end", "<i4")])
 assert HIT_DTYPE.itemsize == 24
@@ -172,6 +176,16 @@ def load() -> ctypes.CDLL:
                                        P, c_int]
         L.dmx_rowdist_ms.argtypes = [P]
         L.dmx_rowdist_ms.restype = ctypes.c_float
+    if hasattr(L, "dmx_edgegroups"):
+        L.dmx_edgegroups.argtypes = [P, P, P, c_size, ctypes.c_uint32, P]
+        L.dmx_edgegroups_host.argtypes = [P, P, c_size, ctypes.c_uint32, P]
+        L.dmx_pairhits.argtypes = [P, P, P, P, P, c_size, P, ctypes.POINTER(ctypes.c_uint64)]
+        L.dmx_pairhits_fetch.argtypes = [P, P, P, P, c_size, ctypes.POINTER(c_size)]
+        L.dmx_hitgroups.argtypes = [P, P, P]
+        L.dmx_pairhits_host.argtypes = [P, P, c_u64p, P, c_size, P, P, P, P, c_size, P, P,
+                                        ctypes.POINTER(ctypes.c_uint64), c_int]
+        L.dmx_hitgroups_host.argtypes = [P, P, P, c_size, P, c_size, P]
+        L.dmx_hitgroups_stats.argtypes = [P, ctypes.POINTER(ctypes.c_float), c_int]
     # DMX_ALLOW_ABI=1: load an older in-tree build for a regression A/B (tools/replay_sweep.py)
     if L.dmx_abi_version() != ABI_VERSION and os.environ.get("DMX_ALLOW_ABI") != "1":
         raise DmxError("libdmx ABI mismatch")
@@ -488,6 +502,62 @@ class Context:
         """Device time (ms) of the last rowdist call."""
         return float(self._L.dmx_rowdist_ms(self._h))
 
+    # ---- gene groups (include/dmx.h dmx_edgegroups .. dmx_hitgroups; DESIGN.md §8i) -------------
+    def edgegroups(self, a, b, n_nodes: int) -> np.ndarray:
+        """Connected components of the edges {a[e], b[e]} over n_nodes nodes: per node the
+        smallest node of its component, LG_NONE for a node on no edge.  Returns uint32."""
+        aa, ba = _edge_arrays(a, b)
+        labels = np.zeros(int(n_nodes), dtype=np.uint32)
+        self._check(self._L.dmx_edgegroups(self._h, aa.ctypes.data, ba.ctypes.data, len(aa),
+                                           int(n_nodes), labels.ctypes.data), "dmx_edgegroups")
+        return labels
+
+    def pairhits(self, q, t, cap_hit, cap_half):
+        """The similarity pass with the hit decision on the device (dmx_pairhits): per pair of
+        resident reads a forward hit (d <= cap_hit), a reverse hit (forward d > cap_half, then
+        d against the reverse complement <= cap_hit) or none; caps are int32, -1 = none.  The
+        outcomes stay in the context for pairhits_fetch / hitgroups.  Returns (best, n_hits):
+        best[r] = the least d over the hits whose target is r (LG_NONE: none), uint32."""
+        qa, ta, ha, fa = _pairhits_arrays(q, t, cap_hit, cap_half)
+        best = np.zeros(int(getattr(self, "_n_loaded", 0)), dtype=np.uint32)
+        n = ctypes.c_uint64(0)
+        self._check(self._L.dmx_pairhits(self._h, qa.ctypes.data, ta.ctypes.data, ha.ctypes.data,
+                                         fa.ctypes.data, len(qa), best.ctypes.data,
+                                         ctypes.byref(n)), "dmx_pairhits")
+        self._n_hits = int(n.value)
+        return best, int(n.value)
+
+    def pairhits_fetch(self):
+        """The hits of the last pairhits in ascending place in its pair list: (pair uint32,
+        d uint32, rev uint8)."""
+        n = ctypes.c_size_t(0)
+        cap = int(getattr(self, "_n_hits", 0))
+        pair, d = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        rev = np.zeros(cap, dtype=np.uint8)
+        self._check(self._L.dmx_pairhits_fetch(self._h, pair.ctypes.data, d.ctypes.data,
+                                               rev.ctypes.data, cap, ctypes.byref(n)),
+                    "dmx_pairhits_fetch")
+        return pair[:n.value], d[:n.value], rev[:n.value]
+
+    def hitgroups(self, tie) -> np.ndarray:
+        """Components of the last pairhits' hits with d <= tie[t] (tie: uint32 per resident
+        read): per read the smallest read of its group, LG_NONE for a read on no kept hit."""
+        ta = np.ascontiguousarray(tie, dtype=np.uint32)
+        if ta.shape != (int(getattr(self, "_n_loaded", 0)),):
+            raise DmxError("hitgroups: tie must have one entry per resident read")
+        labels = np.zeros(len(ta), dtype=np.uint32)
+        self._check(self._L.dmx_hitgroups(self._h, ta.ctypes.data, labels.ctypes.data),
+                    "dmx_hitgroups")
+        return labels
+
+    def hitgroups_stats(self) -> dict:
+        """Device time (ms): the distance launches of the last pairhits, the last compaction, the
+        last components run; and that run's hooking rounds."""
+        ms = (ctypes.c_float * 3)()
+        n = self._check(self._L.dmx_hitgroups_stats(self._h, ms, 3), "dmx_hitgroups_stats")
+        return {"forward": float(ms[0]), "compact": float(ms[1]), "components": float(ms[2]),
+                "rounds": int(n)}
+
     def n_counts(self) -> int:
         a1 = 0 if self.mode == MODE_SINGLE else self.panel_sizes[1]
         return (self.panel_sizes[0] + 1) * (a1 + 1) + 2
@@ -763,6 +833,86 @@ def rowdist_host(p: "Packed", rows, q, r, caps=None, n_threads: int = 1) -> np.n
         msg = L.dmx_last_error(None)
         raise DmxError(f"dmx_rowdist_host failed ({rc}): {msg.decode() if msg else ''}")
     return out
+
+
+def _edge_arrays(a, b):
+    aa = np.ascontiguousarray(a, dtype=np.uint32)
+    ba = np.ascontiguousarray(b, dtype=np.uint32)
+    if aa.ndim != 1 or aa.shape != ba.shape:
+        raise DmxError("edgegroups: a and b must be one-dimensional and of equal length")
+    return aa, ba
+
+
+def _pairhits_arrays(q, t, cap_hit, cap_half):
+    qa, ta, _, _ = _pair_arrays(q, t, None, None)
+    ha = np.ascontiguousarray(cap_hit, dtype=np.int32)
+    fa = np.ascontiguousarray(cap_half, dtype=np.int32)
+    if ha.shape != qa.shape or fa.shape != qa.shape:
+        raise DmxError("pairhits: cap_hit and cap_half must have one entry per pair")
+    return qa, ta, ha, fa
+
+
+def _host_check(L, rc: int, what: str):
+    if rc < 0:
+        msg = L.dmx_last_error(None)
+        raise DmxError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+
+def edgegroups_host(a, b, n_nodes: int) -> np.ndarray:
+    """dmx_edgegroups' contract on the host, by a sequential union-find (no GPU)."""
+    L = load()
+    aa, ba = _edge_arrays(a, b)
+    labels = np.zeros(int(n_nodes), dtype=np.uint32)
+    _host_check(L, L.dmx_edgegroups_host(aa.ctypes.data, ba.ctypes.data, len(aa), int(n_nodes),
+                                         labels.ctypes.data), "dmx_edgegroups_host")
+    return labels
+
+
+class HostHits:
+    """The state of pairhits_host: the pair list and per pair the outcome word (d, d | LG_REV or
+    LG_NONE); best per read; what Context keeps on the device."""
+
+    def __init__(self, q, t, outcome, best, n_reads):
+        self.q, self.t, self.outcome, self.best, self.n_reads = q, t, outcome, best, n_reads
+
+    def fetch(self):
+        """(pair, d, rev) as Context.pairhits_fetch returns them."""
+        pair = np.flatnonzero(self.outcome != LG_NONE).astype(np.uint32)
+        o = self.outcome[pair]
+        return pair, o & np.uint32(LG_REV - 1), (o >> np.uint32(31)).astype(np.uint8)
+
+
+def pairhits_host(p: "Packed", q, t, cap_hit, cap_half, n_threads: int = 1) -> HostHits:
+    """dmx_pairhits' contract on the host (dmx_pairdist_host's DP; no GPU).  Returns the state
+    hitgroups_host reads."""
+    L = load()
+    qa, ta, ha, fa = _pairhits_arrays(q, t, cap_hit, cap_half)
+    outcome = np.zeros(len(qa), dtype=np.uint32)
+    best = np.zeros(p.n_reads, dtype=np.uint32)
+    n = ctypes.c_uint64(0)
+    _host_check(L, L.dmx_pairhits_host(p.seq2b.ctypes.data, p.nmask.ctypes.data,
+                                       p.offsets.ctypes.data, p.lengths.ctypes.data, p.n_reads,
+                                       qa.ctypes.data, ta.ctypes.data, ha.ctypes.data,
+                                       fa.ctypes.data, len(qa), outcome.ctypes.data,
+                                       best.ctypes.data, ctypes.byref(n), int(n_threads)),
+                "dmx_pairhits_host")
+    assert int(n.value) == int((outcome != LG_NONE).sum())
+    return HostHits(qa, ta, outcome, best, p.n_reads)
+
+
+def hitgroups_host(hits, tie) -> np.ndarray:
+    """dmx_hitgroups' contract on the host, on the state of pairhits_host (a HostHits)."""
+    L = load()
+    if not isinstance(hits, HostHits):
+        raise DmxError("hitgroups_host failed (-1): no pairhits_host state")
+    ta = np.ascontiguousarray(tie, dtype=np.uint32)
+    if ta.shape != (hits.n_reads,):
+        raise DmxError("hitgroups: tie must have one entry per read")
+    labels = np.zeros(hits.n_reads, dtype=np.uint32)
+    _host_check(L, L.dmx_hitgroups_host(hits.q.ctypes.data, hits.t.ctypes.data,
+                                        hits.outcome.ctypes.data, len(hits.q), ta.ctypes.data,
+                                        hits.n_reads, labels.ctypes.data), "dmx_hitgroups_host")
+    return labels
 
 
 def cigar(ops, extended: bool = False) -> str:

@@ -3,8 +3,11 @@
 identity lines, restated from scripts/auxiliary_code/amplicon_sorter.py (:550-623 selection,
 :648-716 pairs, :225-235 + :777-808 identities) on top of dmx_pairdist (include/dmx.h).
 
-Clustering and species grouping are NOT replaced: similarity() stops at the similarity lines
-(`i:j:iden`, `i:j:iden:reverse`) the reference's later steps read.  The random selection modes
+similarity() stops at the similarity lines (`i:j:iden`, `i:j:iden:reverse`); gene_groups() goes
+on to what update_list (:983-1034) and merge_groups (:1058-1087) make of them, the gene groups,
+on dmx_pairhits / dmx_hitgroups, without forming the lines.  NOT replaced:
+comp_consensus_groups (:1206, which samples 50 reads of a group at random) and everything after
+it, the species groups (SSG / Estimate) and the .group files.  The random selection modes
 (-ra, -a) are out of scope.  Alphabet: A, C, G, T, N (a read with any other byte is refused;
 the reference would compare such bytes literally).
 
@@ -381,14 +384,10 @@ def _clean(reads, what: str = "read") -> list:
     return out
 
 
-def similarity(ctx, reads, similar_genes: float = 80.0, minlength: int = 300, maxlength=None,
-               maxreads: int = 10000, allreads: bool = False, out=None) -> list:
-    """The similarity pass (:777-808) over `reads` (str or bytes): the lines `i:j:iden` for
-    pairs whose forward identity is >= similar_genes / 100, and `i:j:iden:reverse` for pairs
-    whose forward identity is below 0.5 and whose identity against the reverse complement of
-    the longer read is >= similar_genes / 100; i, j index the length-filtered reads, shorter
-    first.  Lines come in pair-generation order (the reference's workers interleave theirs) and
-    are written to `out` (a path) when given."""
+def _similarity_plan(reads, similar_genes, minlength, maxlength, maxreads, allreads):
+    """What similarity() and gene_groups() compare: the length-filtered reads packed, their
+    lengths, the pairs (shorter, longer) and, per pair, the largest distance whose identity is
+    still >= similar_genes / 100 and >= 0.5 (-1: none).  p is None when there is no pair."""
     seqs = _clean(reads)
     idx = usable([len(s) for s in seqs], minlength, maxlength)
     groups = select_groups([len(s) for s in seqs], minlength, maxlength, maxreads, allreads)
@@ -397,34 +396,50 @@ def similarity(ctx, reads, similar_genes: float = 80.0, minlength: int = 300, ma
     if len(ln) and int(ln.max()) > lib.PD_MAX_LEN:
         raise DmxError(f"a read is longer than {lib.PD_MAX_LEN} nt (pass maxlength)")
     q, t = pairs(groups, ln)
+    if not len(q):
+        return None, ln, q, t, np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    sg = similar_genes / 100
+    # the two caps once per distinct length of the longer read, by the reference's own
+    # expression; the decisions are integer comparisons against them
+    cap_half = np.full(int(ln.max()) + 1, -1, dtype=np.int64)
+    cap_sg = np.full(int(ln.max()) + 1, -1, dtype=np.int64)
+    for L in np.unique(ln[t]):
+        cap_half[L] = identity_cap(int(L), 0.5)
+        cap_sg[L] = identity_cap(int(L), sg)
+    blob = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+    offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
+    p = lib.pack(blob, offs, ln.astype(np.uint32))
+    return p, ln, q, t, cap_sg[ln[t]], cap_half[ln[t]]
+
+
+def similarity(ctx, reads, similar_genes: float = 80.0, minlength: int = 300, maxlength=None,
+               maxreads: int = 10000, allreads: bool = False, out=None) -> list:
+    """The similarity pass (:777-808) over `reads` (str or bytes): the lines `i:j:iden` for
+    pairs whose forward identity is >= similar_genes / 100, and `i:j:iden:reverse` for pairs
+    whose forward identity is below 0.5 and whose identity against the reverse complement of
+    the longer read is >= similar_genes / 100; i, j index the length-filtered reads, shorter
+    first.  Lines come in pair-generation order (the reference's workers interleave theirs) and
+    are written to `out` (a path) when given."""
+    p, ln, q, t, cap_sg, cap_half = _similarity_plan(reads, similar_genes, minlength, maxlength,
+                                                     maxreads, allreads)
     lines = []
     if len(q):
-        sg = similar_genes / 100
-        # the two caps once per distinct length of the longer read, by the reference's own
-        # expression; the decisions below are integer comparisons against them
-        cap_half = np.full(int(ln.max()) + 1, -1, dtype=np.int64)
-        cap_sg = np.full(int(ln.max()) + 1, -1, dtype=np.int64)
-        for L in np.unique(ln[t]):
-            cap_half[L] = identity_cap(int(L), 0.5)
-            cap_sg[L] = identity_cap(int(L), sg)
-        blob = np.frombuffer(b"".join(seqs), dtype=np.uint8)
-        offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
-        ctx.load(lib.pack(blob, offs, ln.astype(np.uint32)))
+        ctx.load(p)
         lt = ln[t]
         # the exact distance is needed wherever the identity is >= 0.5 or >= sg
-        fcap = np.maximum(np.maximum(cap_half[lt], cap_sg[lt]), 0).astype(np.uint32)
+        fcap = np.maximum(np.maximum(cap_half, cap_sg), 0).astype(np.uint32)
         df = ctx.pairdist(q, t, lib.PD_NW, caps=fcap).astype(np.int64)
-        plain = df <= cap_sg[lt]
-        need_rc = ~plain & (df > cap_half[lt]) & (cap_sg[lt] >= 0)
+        plain = df <= cap_sg
+        need_rc = ~plain & (df > cap_half) & (cap_sg >= 0)
         rcs = np.flatnonzero(need_rc)
         dr = np.zeros(0, dtype=np.int64)
         if len(rcs):
             dr = ctx.pairdist(q[rcs], t[rcs], lib.PD_NW,
                               flags=np.full(len(rcs), lib.PD_RC, dtype=np.uint8),
-                              caps=cap_sg[lt[rcs]].astype(np.uint32)).astype(np.int64)
+                              caps=cap_sg[rcs].astype(np.uint32)).astype(np.int64)
         rev = np.zeros(len(q), dtype=bool)
         dist = df.copy()
-        hit = dr <= cap_sg[lt[rcs]]
+        hit = dr <= cap_sg[rcs]
         rev[rcs[hit]] = True
         dist[rcs[hit]] = dr[hit]
         for k in np.flatnonzero(plain | rev):
@@ -434,6 +449,57 @@ def similarity(ctx, reads, similar_genes: float = 80.0, minlength: int = 300, ma
         with open(out, "w") as f:
             f.write("".join(x + "\n" for x in lines))
     return lines
+
+
+def identity_tie(d: int, length: int) -> int:
+    """The largest distance whose identity(., length) equals identity(d, length): lines of one
+    longer read whose distances differ but round to the same identity tie in update_list.  Below
+    1000 nt the step 1 / length is above the rounding's 0.001 and this is d itself."""
+    d, length = int(d), int(length)
+    iden = identity(d, length)
+    while d < length and identity(d + 1, length) == iden:
+        d += 1
+    return d
+
+
+def gene_groups(ctx, reads, similar_genes: float = 80.0, minlength: int = 300, maxlength=None,
+                maxreads: int = 10000, allreads: bool = False, n_threads: int = 16) -> list:
+    """The gene groups update_list (:983-1034) and merge_groups (:1058-1087) make of the
+    similarity lines, without the lines: similarity()'s selection, pairs and caps, the hit
+    decisions on the device (dmx_pairhits), per longer read the hits of the largest identity
+    with every tie, and the connected components of those links (dmx_hitgroups).
+    Returns the groups as ascending index arrays into the length-filtered reads, ordered as the
+    reference's grouplist: by falling (best identity in the group, largest longer read among the
+    links with that identity).  Reads on no kept link are in no group.  ctx: a Context, or None
+    to run the host twins (lib.pairhits_host, lib.hitgroups_host; n_threads)."""
+    p, ln, q, t, cap_sg, cap_half = _similarity_plan(reads, similar_genes, minlength, maxlength,
+                                                     maxreads, allreads)
+    if not len(q):
+        return []
+    if ctx is not None:
+        ctx.load(p)
+        best, _ = ctx.pairhits(q, t, cap_sg, cap_half)
+    else:
+        hits = lib.pairhits_host(p, q, t, cap_sg, cap_half, n_threads=n_threads)
+        best = hits.best
+    has = np.flatnonzero(best != lib.LG_NONE)
+    tie = np.full(len(ln), lib.LG_NONE, dtype=np.uint32)
+    for r in has:
+        tie[r] = identity_tie(int(best[r]), int(ln[r]))
+    labels = ctx.hitgroups(tie) if ctx is not None else lib.hitgroups_host(hits, tie)
+    # a group stands where its first link does in the list sorted by (iden, j), reverse=True;
+    # every kept link of j has the identity of best[j]
+    first = {}
+    for r in has:
+        key = (identity(int(best[r]), int(ln[r])), int(r))
+        g = int(labels[r])
+        if g not in first or key > first[g]:
+            first[g] = key
+    members = {g: [] for g in first}
+    for r in np.flatnonzero(labels != lib.LG_NONE):
+        members[int(labels[r])].append(int(r))
+    order = sorted(first, key=lambda g: first[g], reverse=True)
+    return [np.array(members[g], dtype=np.int64) for g in order]
 
 
 def read_sequences(path: str) -> list:
@@ -451,9 +517,14 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(
         prog="dmx-similarity",
         description="The similarity pass of amplicon_sorter.py (pairwise identities of one "
-                    "bin's reads) on the GPU; clustering and consensus stay with the reference.")
+                    "bin's reads) on the GPU, and with --groups the gene groups of its best "
+                    "hits; comp_consensus_groups onward stays with the reference.")
     ap.add_argument("-i", "--input", required=True, help="bin in FASTQ/FASTA, optionally .gz")
-    ap.add_argument("-o", "--output", required=True, help="similarity lines (i:j:iden[:reverse])")
+    ap.add_argument("-o", "--output", default=None,
+                    help="similarity lines (i:j:iden[:reverse]); optional with --groups")
+    ap.add_argument("--groups", default=None, metavar="FILE",
+                    help="gene groups, one per line: space-separated read indices, in the "
+                         "reference's group order")
     ap.add_argument("-min", "--minlength", type=int, default=300)
     ap.add_argument("-max", "--maxlength", type=int, default=None)
     ap.add_argument("-maxr", "--maxreads", type=int, default=10000)
@@ -461,14 +532,24 @@ def main(argv=None) -> int:
     ap.add_argument("-sg", "--similar_genes", type=float, default=80.0)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.output is None and a.groups is None:
+        ap.error("the following arguments are required: -o/--output")
     try:
         reads = read_sequences(a.input)
         with lib.Context(a.device) as ctx:
-            lines = similarity(ctx, reads, a.similar_genes, a.minlength, a.maxlength, a.maxreads,
-                               a.allreads, out=a.output)
+            if a.output is not None:
+                lines = similarity(ctx, reads, a.similar_genes, a.minlength, a.maxlength,
+                                   a.maxreads, a.allreads, out=a.output)
+                print(f"dmx-similarity: {len(reads)} reads, {len(lines)} similarity lines -> "
+                      f"{a.output}", file=sys.stderr)
+            if a.groups is not None:
+                groups = gene_groups(ctx, reads, a.similar_genes, a.minlength, a.maxlength,
+                                     a.maxreads, a.allreads)
+                with open(a.groups, "w") as f:
+                    f.write("".join(" ".join(str(int(x)) for x in g) + "\n" for g in groups))
+                print(f"dmx-similarity: {len(reads)} reads, {len(groups)} gene groups -> "
+                      f"{a.groups}", file=sys.stderr)
     except (DmxError, OSError, ValueError) as e:
         print(f"dmx-similarity: {e}", file=sys.stderr)
         return 1
-    print(f"dmx-similarity: {len(reads)} reads, {len(lines)} similarity lines -> {a.output}",
-          file=sys.stderr)
     return 0
