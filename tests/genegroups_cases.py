@@ -1,10 +1,12 @@
 """Shared inputs and the oracle of the gene-group tests (test_genegroups_host.py on the CPU,
-test_genegroups.py on the GPU).
+test_genegroups.py and test_genegroups_scale.py on the GPU).
 
 The oracle is a literal restatement of amplicon_sorter.py update_list (:983-1034) and merge_groups
 (:1058-1087), fed the lines of a plain restatement of similarity (:777-808) on the numpy DP of
-pairdist_cases with built-in round.  It is computed once per process and shared."""
+pairdist_cases with built-in round.  It is computed once per process and shared.  The pair
+lists of many blocks and tiles (scale_case) have an oracle of their own, in numpy alone."""
 import functools
+import zlib
 
 import numpy as np
 
@@ -282,3 +284,182 @@ def bin_plan(reads, sg=80.0):
     t, cap_hit, cap_half), from the sorter's own planning."""
     from dmx import sorter
     return sorter._similarity_plan(reads, sg, 0, None, 10000, False)
+
+
+# ---- pair lists at scale -------------------------------------------------------------------------
+# dmx_pairhits' pair list is arbitrary and its caps are per pair, so a list of any length can be
+# drawn from the few thousand distinct pairs of a small batch, and the caps of every place chosen
+# so that the documented rule (sorter.similarity; the comment above ph_decide_kernel) gives the
+# class wanted there.  The numpy DP runs once, over the distinct pairs; everything expected of a
+# list is then numpy arithmetic on those distances.
+
+SCALE_SIZES = (255, 256, 257, 16384, 16385, 65536, 65537, 131329)
+SCALE_LAYOUTS = ("all_forward", "none", "every_257th", "block_stripes", "tile_heads", "last_only",
+                 "mixed", "one_target")
+SCALE_TOP = SCALE_SIZES[-1]        # 514 blocks of 256: three tiles of the scan, a ragged last block
+SCALE_HOST_N = 65537               # the CPU tests' size: 257 blocks, the second tile holds one
+F, R, M, X = 0, 1, 2, 3            # forward hit, reverse hit, miss without a retry, retried miss
+
+
+def scale_cases():
+    """(layout, N) of the GPU tests: every layout at the largest size; at the sizes on either side
+    of 64 and 256 blocks (and of one block), `mixed` and `all_forward`."""
+    return [(name, SCALE_TOP) for name in SCALE_LAYOUTS] + \
+        [(name, n) for n in SCALE_SIZES[:-1] for name in ("all_forward", "mixed")]
+
+
+@functools.lru_cache(maxsize=None)
+def scale_reads():
+    """64 reads of 24-60 nt (one 64-row word each): 8 founders, of each two mutated copies (5-10 %)
+    and two reverse-complemented mutated copies, 18 unrelated reads and 6 reads with N; shuffled.
+    Returns (reads, packed, d_fwd, d_rev): d_fwd[a, b] = NW(a, b), d_rev[a, b] = NW(a, revcomp(b))
+    by the numpy DP, int64; the diagonal is not used."""
+    rng = np.random.default_rng(41)
+    reads = []
+    for _ in range(8):
+        f = pc.rand_seq(rng, int(rng.integers(30, 56)), p_n=0.0)
+        reads.append(f)
+        for k in range(4):
+            c = pc.mutate(rng, f, float(rng.uniform(0.05, 0.10)))[:60]
+            reads.append(pc.revcomp(c) if k >= 2 else c)
+    reads += [pc.rand_seq(rng, int(rng.integers(24, 61)), p_n=0.0) for _ in range(18)]
+    reads += [pc.rand_seq(rng, int(rng.integers(24, 61)), p_n=0.1) for _ in range(6)]
+    reads = [reads[i] for i in rng.permutation(len(reads))]
+    n = len(reads)
+    assert n == 64 and all(24 <= len(r) <= 60 for r in reads)
+    assert sum(b"N" in r for r in reads) >= 6
+    a, b = [x.reshape(-1) for x in np.meshgrid(np.arange(n), np.arange(n), indexing="ij")]
+    qs = [reads[i] for i in a]
+    d_fwd = pc.np_dist(qs, [reads[j] for j in b], lib.PD_NW).reshape(n, n)
+    d_rev = pc.np_dist(qs, [pc.revcomp(reads[j]) for j in b], lib.PD_NW).reshape(n, n)
+    return reads, pc.pack_reads(reads), d_fwd, d_rev
+
+
+def _between(rng, lo, hi):
+    """Per place an integer of lo .. hi (arrays, lo <= hi): a third each the lower end, the upper
+    end and a uniform draw, so that both sides of every comparison of the rule occur often."""
+    k = rng.integers(0, 3, len(lo))
+    return np.where(k == 0, lo, np.where(k == 1, hi, rng.integers(lo, hi + 1)))
+
+
+def _class_pattern(layout, n, rng):
+    i = np.arange(n)
+    if layout == "all_forward":
+        return np.full(n, F)
+    if layout == "none":
+        return np.full(n, M)
+    if layout == "every_257th":      # the one hit walks through every lane over consecutive blocks
+        return np.where(i % 257 == 0, F, M)
+    if layout == "block_stripes":
+        return np.where((i // 256) % 2 == 0, F, M)
+    if layout == "tile_heads":       # 65,536 pairs = 256 blocks = one tile of the scan
+        return np.where((i % 65536 == 0) | (i == n - 1), F, M)
+    if layout == "last_only":
+        return np.where(i == n - 1, R, M)
+    if layout in ("mixed", "one_target"):
+        return rng.permutation(i % 4)
+    raise KeyError(layout)
+
+
+class ScaleCase:
+    """A pair list and everything expected of it, from numpy alone."""
+
+    def __init__(self, layout, n):
+        reads, self.packed, d_fwd, d_rev = scale_reads()
+        rng = np.random.default_rng([zlib.crc32(layout.encode()), n])
+        self.layout, self.n, self.n_reads = layout, n, len(reads)
+        self.cls = cls = _class_pattern(layout, n, rng)
+        # the distinct ordered pairs, and which of them can produce which class
+        a, b = np.nonzero(~np.eye(self.n_reads, dtype=bool))
+        if layout == "one_target":   # three targets with a query for every class
+            ok = [r for r in range(self.n_reads) if (d_rev[:, r] < d_fwd[:, r]).sum() >= 2]
+            keep = np.isin(b, ok[:3])
+            a, b = a[keep], b[keep]
+        df, dr = d_fwd[a, b], d_rev[a, b]
+        # hits land on reads with a relative only (a read within a quarter of their length, either
+        # strand): an unrelated hit there loses against the relative's in the tie filter, so the
+        # kept edges fall into several groups and the reads without a relative keep no label
+        ln = np.array([len(r) for r in reads])
+        near = np.where(np.eye(self.n_reads, dtype=bool), 99, np.minimum(d_fwd, d_rev)).min(axis=0)
+        fam = (near <= ln // 4)[b] | (layout == "one_target")
+        can = {F: fam, R: fam & (dr < df), M: df >= 1, X: np.minimum(df, dr) >= 1}
+        pick = np.zeros(n, dtype=np.int64)
+        for c, mask in can.items():
+            where = np.flatnonzero(cls == c)
+            pick[where] = rng.choice(np.flatnonzero(mask), len(where))
+        self.q, self.t = a[pick].astype(np.uint32), b[pick].astype(np.uint32)
+        self.d_fwd, self.d_rev = df, dr = df[pick], dr[pick]
+        one, any_half = np.ones(n, dtype=np.int64), rng.integers(-1, 70, n)
+        # F: d_fwd <= cap_hit, whatever cap_half is
+        hit_f = df + rng.choice([0, 0, 1, 5], n)
+        # R and X: d_fwd > cap_hit >= 0 and d_fwd > cap_half; R: d_rev <= cap_hit, X: d_rev > cap_hit
+        lo_half = _between(rng, -one, np.maximum(df - 1, -1))
+        hit_r = _between(rng, dr, np.maximum(df - 1, dr))
+        hit_x = _between(rng, 0 * one, np.maximum(np.minimum(df, dr) - 1, 0))
+        # M: no hit cap at all (every other M), or cap_hit < d_fwd <= cap_half
+        bare = (np.cumsum(cls == M) % 2 == 1)
+        hit_m = np.where(bare, -1, _between(rng, 0 * one, np.maximum(df - 1, 0)))
+        half_m = np.where(bare, any_half, _between(rng, df, df + 4))
+        self.cap_hit = np.select([cls == F, cls == R, cls == X], [hit_f, hit_r, hit_x],
+                                 hit_m).astype(np.int32)
+        self.cap_half = np.select([cls == F, cls == M], [any_half, half_m], lo_half).astype(np.int32)
+        # what the rule gives, restated on the exact distances
+        ch, chalf = self.cap_hit.astype(np.int64), self.cap_half.astype(np.int64)
+        fwd = df <= ch
+        tried = ~fwd & (ch >= 0) & (df > chalf)
+        back = tried & (dr <= ch)
+        got = np.select([fwd, back, tried], [F, R, X], M)
+        assert (got == cls).all(), "the generator missed a class it asked for"
+        self.hit = fwd | back
+        self.outcome = np.where(fwd, df, np.where(back, dr | lib.LG_REV, NONE)).astype(np.uint32)
+        self.pair = np.flatnonzero(self.hit).astype(np.uint32)
+        self.d = np.where(fwd, df, dr)[self.pair].astype(np.uint32)
+        self.rev = back[self.pair].astype(np.uint8)
+        self.n_hits = len(self.pair)
+        self.best = np.full(self.n_reads, NONE, dtype=np.uint32)
+        np.minimum.at(self.best, self.t[self.pair], self.d)
+
+    def args(self):
+        return self.q, self.t, self.cap_hit, self.cap_half
+
+    def ties(self):
+        """name -> tie table: the best distance per read, and one more where there is a best."""
+        return {"best": self.best,
+                "best+1": np.where(self.best != NONE, self.best + np.uint32(1), self.best)}
+
+    def edges(self, tie):
+        """The hits dmx_hitgroups keeps for `tie`, as a mask over the hits."""
+        return self.d <= np.asarray(tie, dtype=np.uint32)[self.t[self.pair]]
+
+    def labels(self, tie):
+        """dmx_hitgroups' labels for `tie` by label propagation over the distinct kept edges."""
+        keep = self.pair[self.edges(tie)]
+        e = np.unique(np.stack([self.q[keep], self.t[keep]], axis=1), axis=0)
+        return components(e, self.n_reads)
+
+    @functools.cached_property
+    def host(self):
+        """The host twin's state for this list (pinned to the oracle by test_genegroups_host.py)."""
+        return lib.pairhits_host(self.packed, *self.args(), n_threads=16)
+
+
+@functools.lru_cache(maxsize=None)
+def scale_case(layout, n):
+    return ScaleCase(layout, n)
+
+
+def first_differences(got, exp, what, most=5):
+    """A message naming the first places where two arrays differ (or their lengths), or None."""
+    got, exp = np.asarray(got), np.asarray(exp)
+    if got.shape != exp.shape:
+        return f"{what}: {len(got)} entries, {len(exp)} expected"
+    bad = np.flatnonzero(got != exp)
+    if not len(bad):
+        return None
+    return f"{what}: {len(bad)} of {len(exp)} differ, first at " + ", ".join(
+        f"[{k}] {got[k]} != {exp[k]}" for k in bad[:most])
+
+
+def assert_same(got, exp, what):
+    msg = first_differences(got, exp, what)
+    assert msg is None, msg

@@ -126,6 +126,73 @@ def test_update_list_can_keep_a_line_below_the_best():
     assert gc.best_lines(lines) <= {(int(x[0]), int(x[1])) for x in templist}
 
 
+# ---- pair lists of many blocks and tiles (genegroups_cases.scale_case) ---------------------------
+
+@pytest.mark.parametrize("layout", gc.SCALE_LAYOUTS)
+def test_host_twins_equal_the_numpy_oracle_at_scale(layout):
+    """The twins the GPU tests compare with, against numpy arithmetic on the distinct pairs'
+    distances: outcomes, hits, best, and the labels for both tie tables."""
+    c = gc.scale_case(layout, gc.SCALE_HOST_N)
+    host = c.host
+    gc.assert_same(host.outcome, c.outcome, "outcome")
+    pair, d, rev = host.fetch()
+    gc.assert_same(pair, c.pair, "pair")
+    gc.assert_same(d, c.d, "d")
+    gc.assert_same(rev, c.rev, "rev")
+    gc.assert_same(host.best, c.best, "best")
+    for name, tie in c.ties().items():
+        gc.assert_same(lib.hitgroups_host(host, tie), c.labels(tie), f"labels, tie = {name}")
+
+
+def test_the_scale_lists_hold_what_they_are_meant_to():
+    """Conditions on the generator, not on code under test: a weak list cannot hide a failure."""
+    n = gc.SCALE_TOP
+    assert sorted(set(gc.scale_cases())) == sorted(
+        [(name, n) for name in gc.SCALE_LAYOUTS] +
+        [(name, k) for name in ("all_forward", "mixed")
+         for k in (255, 256, 257, 16384, 16385, 65536, 65537)])
+    reads, p, d_fwd, d_rev = gc.scale_reads()
+    assert len(reads) == 64 and p.lengths.max() <= 64     # one 64-row word per read
+
+    def per_block(c):
+        return np.add.reduceat(c.hit.astype(np.int64), np.arange(0, c.n, 256))
+
+    mixed = gc.scale_case("mixed", n)
+    assert (np.bincount(mixed.cls, minlength=4) >= n // 8).all()
+    assert mixed.rev.any() and not mixed.rev.all()
+    for name, tie in mixed.ties().items():                # the tie filter removes and keeps
+        assert 0 < mixed.edges(tie).sum() < mixed.n_hits, name
+    assert mixed.edges(mixed.ties()["best"]).sum() < mixed.edges(mixed.ties()["best+1"]).sum()
+    labels = mixed.labels(mixed.best)
+    assert len(gc.groups_of(labels)) >= 4 and (labels == gc.NONE).any()
+
+    c = gc.scale_case("all_forward", n)
+    assert c.n_hits == n and (per_block(c)[:-1] == 256).all() and per_block(c)[-1] == n % 256
+    c = gc.scale_case("none", n)
+    assert c.n_hits == 0 and abs(int((c.cap_hit == -1).sum()) - n // 2) <= 1
+    assert ((c.cap_hit >= 0) & (c.cap_half >= c.d_fwd)).any()
+    c = gc.scale_case("every_257th", n)
+    assert sorted(set((c.pair % 256).tolist())) == list(range(256))   # every place in a block
+    assert set(per_block(c).tolist()) == {0, 1}
+    c = gc.scale_case("block_stripes", n)
+    assert {0, 256} <= set(per_block(c).tolist())
+    c = gc.scale_case("tile_heads", n)
+    tiles = per_block(c)[:256 * (len(per_block(c)) // 256)].reshape(-1, 256).sum(axis=1)
+    assert (tiles == 1).any() and c.hit[-1] and c.pair.tolist() == [0, 65536, 131072, n - 1]
+    c = gc.scale_case("last_only", n)
+    assert c.pair.tolist() == [n - 1] and c.rev.tolist() == [1]
+    c = gc.scale_case("one_target", n)
+    assert len(set(c.t.tolist())) == 3
+    assert np.bincount(c.t[c.pair], minlength=c.n_reads).max() > 10000
+    assert (np.bincount(c.cls, minlength=4) >= n // 8).all()
+    # both sides of every comparison of the rule, at the boundary
+    assert (mixed.d_fwd == mixed.cap_hit).any() and (mixed.d_fwd == mixed.cap_hit + 1).any()
+    assert (mixed.d_fwd == mixed.cap_half).any() and (mixed.d_fwd == mixed.cap_half + 1).any()
+    tried = (mixed.cls == gc.R) | (mixed.cls == gc.X)
+    assert (mixed.d_rev == mixed.cap_hit)[tried].any()
+    assert (mixed.d_rev == mixed.cap_hit + 1)[tried].any()
+
+
 def test_argument_checks():
     with pytest.raises(lib.DmxError, match=r"\(-1\)"):
         lib.edgegroups_host([0, 5], [1, 2], 5)            # an endpoint out of range
