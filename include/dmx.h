@@ -425,6 +425,29 @@ int dmx_groupalign_host(const uint32_t* seq2b, const uint32_t* nmask, const uint
                         uint64_t* col_off, uint8_t* mask, uint16_t* count, uint16_t* first,
                         size_t cols_cap, uint32_t* dist, uint64_t* op_off, uint8_t* ops,
                         size_t ops_cap, int n_threads);
+/* dmx_groupalign with a strand per member (consensus_direction's outcome, :1826-1838, applied in
+ * place): member_flags is parallel to members; bit DMX_PD_RC takes the member
+ * reverse-complemented (read backwards, codes complemented, masked positions stay masked: what
+ * DMX_PD_RC means for dmx_pairdist's target).  dist, ops, count and first are then those of the
+ * reverse-complemented read against the row; everything else (tie rule, rounds, the
+ * DMX_PA_TRACE_MB split, max_cols, the refusals) is dmx_groupalign's.  Any other bit is
+ * DMX_E_INVALID, naming group and member, checked on the host before anything is launched.
+ * member_flags == NULL is dmx_groupalign itself (the two entry points above are these with
+ * NULL). */
+int dmx_groupalign_strands(dmx_ctx* ctx, size_t n_groups, const uint8_t* seed_masks,
+                           const uint64_t* seed_off, const uint32_t* members,
+                           const uint8_t* member_flags, const uint64_t* member_off,
+                           uint32_t max_cols, uint64_t* col_off, uint8_t* mask, uint16_t* count,
+                           uint16_t* first, size_t cols_cap, uint32_t* dist, uint64_t* op_off,
+                           uint8_t* ops, size_t ops_cap);
+int dmx_groupalign_strands_host(const uint32_t* seq2b, const uint32_t* nmask,
+                                const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
+                                size_t n_groups, const uint8_t* seed_masks,
+                                const uint64_t* seed_off, const uint32_t* members,
+                                const uint8_t* member_flags, const uint64_t* member_off,
+                                uint32_t max_cols, uint64_t* col_off, uint8_t* mask,
+                                uint16_t* count, uint16_t* first, size_t cols_cap, uint32_t* dist,
+                                uint64_t* op_off, uint8_t* ops, size_t ops_cap, int n_threads);
 /* ms[0] = the forward passes, ms[1] = the tracebacks, ms[2] = the merges of the last
  * dmx_groupalign (first n_ms written); *rounds (may be NULL) = its lock-step rounds; returns
  * the number of launches of each kernel. */

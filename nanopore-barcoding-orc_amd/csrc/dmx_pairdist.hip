@@ -28,7 +28,8 @@
 // NW, no trace, the rows given by the caller per call (rowdist_kernel).
 //
 // All forms share one forward pass (pd_forward: pairdist_kernel, pairalign_kernel,
-// groupalign_kernel and rowdist_kernel are its instantiations, told apart at compile time by
+// groupalign_kernel, groupalign_strands_kernel (members taken reverse-complemented,
+// dmx_groupalign_strands) and rowdist_kernel are its instantiations, told apart at compile time by
 // their argument struct), one traceback (pa_traceback) and one host path: the chunk planner (pd_plan: chunk
 // limits, sort, wave packing, pair records), the staging of a launch (pd_stage: buffers, upload,
 // the arguments every kernel takes) and the buffers themselves (PdBufs).  A change to the block
@@ -65,6 +66,8 @@ struct PaPair : PdPair {
 // dmx_groupalign's record: the target is a row of masks, `n` columns long now, at mask[row ..);
 // the merge writes the group's next row at mask[dst ..).  PdPair::t is the group, PdPair::cap
 // the most columns a row may have (a longer path is left unmerged and refused by the host).
+// PdPair::flags & DMX_PD_RC: the member (the query) is taken reverse-complemented
+// (dmx_groupalign_strands; pd_masks<true> and the merge read it backwards).
 struct GaPair : PaPair {
     uint64_t row, dst;           // columns: an index into mask, times 5 into count / first
     uint32_t n;                  // the row's length in this round
@@ -125,6 +128,11 @@ struct GaArgs : PdHead<GaPair> {
     uint64_t cols;               // columns of mask (count and first have 5 entries per column)
     uint32_t* out;               // per pair: distance, path length
 };
+
+// The same, for a launch in which some member is flagged DMX_PD_RC: a form of its own, so that
+// groupalign_kernel (no flag in the launch, and every dmx_groupalign call) keeps the
+// instructions it had before members had strands (groupalign_strands_kernel).
+struct GaStrandArgs : GaArgs {};
 
 // dmx_rowdist: the distance form's arguments (NW only, so no mode) and the call's rows.
 struct RdArgs : PdHead<RdPair> {
@@ -189,17 +197,30 @@ void pd_release(Ctx* c) {
 // The five match masks (A, C, G, T, N) of query rows 64 wi .. 64 wi + 63, built in registers
 // from the packed query.  A masked row is the fifth symbol whatever code it carries: it is kept
 // out of the A/C/G/T masks.  Rows past the query's end match nothing.
+// kStrand (GaStrandArgs: dmx_groupalign_strands' launches with a flagged member, DESIGN.md
+// §8g): with rc set the query is the read taken
+// reverse-complemented, row i = 3 - code[m - 1 - i].  The 64 positions of word wi then end at
+// m - 1 - 64 wi and begin at m - 64 (wi + 1), which in the query's last word lies up to 63 nt
+// before the read (before the packed buffer for a read at offset 16).  That word is loaded from
+// the read's first nt instead and shifted up by the rows it lacks, so the positions below the
+// read become zero bits and the ones loaded past the word's end fall off the top: nothing
+// outside [qoff, qoff + m) reaches peq, and the loads stay where the forward form's are.
+// kStrand = false holds no instruction of this.
+template <bool kStrand>
 __device__ __forceinline__ void pd_masks(const Packed& pk, uint64_t qoff, uint32_t m, uint32_t wi,
-                                         uint64_t (&peq)[5]) {
-    const int64_t g0 = (int64_t)qoff + 64ll * wi;
+                                         uint32_t rc, uint64_t (&peq)[5]) {
     const uint32_t rows = min(64u, m - 64u * wi);
+    int64_t g0 = (int64_t)qoff + 64ll * wi;
+    if constexpr (kStrand) {
+        if (rc) g0 = (int64_t)qoff + (int64_t)(m - 64u * wi - rows);   // m - 64 (wi + 1), or 0
+    }
     uint32_t cw[4], nw[2];
 #pragma unroll
     for (int k = 0; k < 4; ++k) cw[k] = code32(pk, g0 + 16 * k);
 #pragma unroll
     for (int k = 0; k < 2; ++k) nw[k] = mask32(pk, g0 + 32 * k);
     const uint64_t valid = rows >= 64u ? ~0ull : ((1ull << rows) - 1ull);
-    const uint64_t nb = (((uint64_t)nw[1] << 32) | nw[0]) & valid;
+    uint64_t nb = (((uint64_t)nw[1] << 32) | nw[0]) & valid;
     uint64_t lo = 0, hi = 0;   // bit i: low / high bit of row i's code
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -211,6 +232,14 @@ __device__ __forceinline__ void pd_masks(const Packed& pk, uint64_t qoff, uint32
         }
         lo |= (uint64_t)l << (16 * k);
         hi |= (uint64_t)h << (16 * k);
+    }
+    if constexpr (kStrand) {
+        if (rc) {   // bit k is position g0 + k: row 63 - (k + 64 - rows), complemented
+            const uint32_t up = 64u - rows;   // 0..63
+            lo = ~__brevll(lo << up);
+            hi = ~__brevll(hi << up);
+            nb = __brevll(nb << up);
+        }
     }
     const uint64_t acgt = valid & ~nb;
     peq[0] = ~hi & ~lo & acgt;
@@ -250,7 +279,9 @@ __device__ __forceinline__ uint64_t pd_target_off(const uint64_t* offs, const Pa
 // GaArgs, the trace against a row of masks (dmx_groupalign's forward pass): as PaArgs, but the
 // target is P.n mask bytes at A.mask[P.row ..), the group's first lane loads 16 of them per 16
 // columns, and the value that travels down the lanes carries the mask, not a symbol; Eq is the
-// OR of the peq[c] whose bit is set (a gap column, mask 0, equals nothing).
+// OR of the peq[c] whose bit is set (a gap column, mask 0, equals nothing).  Here the pair's RC
+// flag turns the query, not the target: GaStrandArgs takes peq from pd_masks<true>, the only
+// strand branch (GaArgs ignores the flag: the host launches it only where none is set).
 // RdArgs, the distance against a row of masks (dmx_rowdist): the target and its fetch are
 // GaArgs's, the score handling PdArgs's in NW (there is no mode and no reversed target: the
 // caller gives a reversed row as a row of its own); out[k] = the distance, clamped by the cap.
@@ -261,8 +292,9 @@ __device__ __forceinline__ uint64_t pd_target_off(const uint64_t* offs, const Pa
 template <class Args>
 __device__ __forceinline__ void pd_forward(const Args& A) {
     constexpr bool kRd = std::is_same<Args, RdArgs>::value;
-    constexpr bool kRow = std::is_same<Args, GaArgs>::value || kRd;
-    constexpr bool kTrace = std::is_same<Args, PaArgs>::value || std::is_same<Args, GaArgs>::value;
+    constexpr bool kGa = std::is_base_of<GaArgs, Args>::value;   // GaArgs or GaStrandArgs
+    constexpr bool kRow = kGa || kRd;
+    constexpr bool kTrace = std::is_same<Args, PaArgs>::value || kGa;
     constexpr uint32_t kColsBuf = kRd ? kBufRdCols : kBufGaCols;
     const uint32_t wave = blockIdx.x * kPdWavesPerBlock + (threadIdx.x >> 6);
     if (wave >= A.n_waves) return;   // whole waves leave: the shift below sees full waves
@@ -314,7 +346,7 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
             wi = s * G + w;
             live = wi < mw;
             last = wi + 1u == mw;
-            if (live) pd_masks(A.pk, qoff, m, wi, peq);
+            if (live) pd_masks<std::is_same<Args, GaStrandArgs>::value>(A.pk, qoff, m, wi, rc, peq);
             Pv = ~0ull;
             Mv = 0ull;
             // the word's last row: the query's in its last word, so no padded row is ever read
@@ -417,6 +449,9 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairdist_kernel(PdArgs 
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void pairalign_kernel(PaArgs A) { pd_forward(A); }
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void groupalign_kernel(GaArgs A) { pd_forward(A); }
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void rowdist_kernel(RdArgs A) { pd_forward(A); }
+__global__ __launch_bounds__(64 * kPdWavesPerBlock) void groupalign_strands_kernel(GaStrandArgs A) {
+    pd_forward(A);
+}
 
 // dmx_pairalign's traceback: one lane per pair walks back from (m, n), preferring up (INSERT),
 // then left (DELETE), then the diagonal (include/dmx.h).  Bit b of a word's Pv / Mv at column j
@@ -496,7 +531,8 @@ __global__ __launch_bounds__(kPaTbLanes) void groupalign_traceback_kernel(GaArgs
 // dmx_groupalign's merge: one wave per pair lays the pair's forward path over the group's row.
 // The path is taken 64 ops at a time, one op per lane; the column an op reads in the old row and
 // the query symbol it shows are its ranks among the ops that consume the target / the query: a
-// ballot, a popcount of the lanes below, and a base that runs over the chunks.  Column `col` of
+// ballot, a popcount of the lanes below, and a base that runs over the chunks (the query symbol
+// at rank r of a reversed member is the complement of the read's at m - 1 - r).  Column `col` of
 // the new row is written by the lane of op `col` alone (plain stores, no atomics: the result
 // does not depend on the order the lanes or the waves run in):
 //   mask:  the old column's for M / X / D, 0 (a gap: equals nothing) for I
@@ -513,6 +549,7 @@ __global__ __launch_bounds__(64 * kGaMergeWaves) void groupalign_merge_kernel(Ga
     const uint32_t m = A.lens[P.q], n = P.n, len = A.out[2u * k + 1u];
     if (len > P.cap || len > m + n || len < max(m, n)) return;
     const uint64_t qoff = A.offs[P.q];
+    const uint32_t rc = P.flags & DMX_PD_RC;
     const uint64_t start = P.roff + (m + n - len);
     const uint64_t below = (1ull << lane) - 1ull;
     uint32_t tbase = 0, qbase = 0;
@@ -539,8 +576,13 @@ __global__ __launch_bounds__(64 * kGaMergeWaves) void groupalign_merge_kernel(Ga
                 }
             }
             if (takes_q) {
-                const int64_t g = (int64_t)qoff + qbase + (uint32_t)__popcll(bq & below);
-                const uint32_t sym = (mask32(A.pk, g) & 1u) ? 4u : (code32(A.pk, g) & 3u);
+                // rank r among the ops that consume the query; a reversed member shows
+                // 3 - code of position m - 1 - r (a rank past the query reads position 0)
+                const uint32_t r = qbase + (uint32_t)__popcll(bq & below);
+                const uint32_t at = rc ? (r < m ? m - 1u - r : 0u) : r;
+                const int64_t g = (int64_t)qoff + at;
+                const uint32_t code = code32(A.pk, g) & 3u;
+                const uint32_t sym = (mask32(A.pk, g) & 1u) ? 4u : rc ? 3u - code : code;
 #pragma unroll
                 for (int c = 0; c < 5; ++c)
                     if (sym == (uint32_t)c) {
@@ -1204,8 +1246,8 @@ struct GaShape {
 // Every argument check of both entry points, naming the group.  0, or the code with *err set.
 int ga_validate(const char* who, const uint32_t* lens, size_t n_reads, size_t n_groups,
                 const uint8_t* seed_masks, const uint64_t* seed_off, const uint32_t* members,
-                const uint64_t* member_off, uint32_t max_cols, size_t cols_cap, bool want_ops,
-                size_t ops_cap, GaShape& sh, std::string* err) {
+                const uint8_t* member_flags, const uint64_t* member_off, uint32_t max_cols,
+                size_t cols_cap, bool want_ops, size_t ops_cap, GaShape& sh, std::string* err) {
     const std::string name = std::string(who) + ": ";
     if (max_cols > DMX_PD_MAX_LEN) {
         *err = name + "max_cols " + std::to_string(max_cols) + " is above " +
@@ -1242,6 +1284,11 @@ int ga_validate(const char* who, const uint32_t* lens, size_t n_reads, size_t n_
             if (members[x] >= n_reads) {
                 *err = grp + "member " + std::to_string(x - member_off[g]) +
                        " names a read outside the batch";
+                return DMX_E_INVALID;
+            }
+            if (member_flags && (member_flags[x] & ~DMX_PD_RC)) {
+                *err = grp + "member " + std::to_string(x - member_off[g]) +
+                       " has an unknown flag";
                 return DMX_E_INVALID;
             }
             const uint32_t m = lens[members[x]];
@@ -1298,15 +1345,14 @@ extern "C" int dmx_groupalign_stats(dmx_ctx* c, float* ms, int n_ms, int* rounds
     return c->ga ? c->ga->launches : 0;
 }
 
-extern "C" int dmx_groupalign_host(const uint32_t* seq2b, const uint32_t* nmask,
-                                   const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
-                                   size_t n_groups, const uint8_t* seed_masks,
-                                   const uint64_t* seed_off, const uint32_t* members,
-                                   const uint64_t* member_off, uint32_t max_cols, uint64_t* col_off,
-                                   uint8_t* mask, uint16_t* count, uint16_t* first, size_t cols_cap,
-                                   uint32_t* dist, uint64_t* op_off, uint8_t* ops, size_t ops_cap,
-                                   int n_threads) {
-    const char* const who = "dmx_groupalign_host";
+// Both host entry points: member_flags == NULL is dmx_groupalign_host (`who` opens the messages).
+static int ga_host(const char* who, const uint32_t* seq2b, const uint32_t* nmask,
+                   const uint64_t* offsets, const uint32_t* lens, size_t n_reads, size_t n_groups,
+                   const uint8_t* seed_masks, const uint64_t* seed_off, const uint32_t* members,
+                   const uint8_t* member_flags, const uint64_t* member_off, uint32_t max_cols,
+                   uint64_t* col_off, uint8_t* mask, uint16_t* count, uint16_t* first,
+                   size_t cols_cap, uint32_t* dist, uint64_t* op_off, uint8_t* ops, size_t ops_cap,
+                   int n_threads) {
     const bool some = n_groups && member_off && member_off[n_groups] > member_off[0];
     if (!seed_off || !member_off || !col_off || (ops && !op_off) ||
         (n_groups && (!seed_masks || !mask || !count || !first)) ||
@@ -1317,8 +1363,8 @@ extern "C" int dmx_groupalign_host(const uint32_t* seq2b, const uint32_t* nmask,
     GaShape sh;
     std::string err;
     if (const int rc = ga_validate(who, lens, n_reads, n_groups, seed_masks, seed_off, members,
-                                   member_off, max_cols, cols_cap, ops != nullptr, ops_cap, sh,
-                                   &err)) {
+                                   member_flags, member_off, max_cols, cols_cap, ops != nullptr,
+                                   ops_cap, sh, &err)) {
         set_process_error(err);
         return rc;
     }
@@ -1340,7 +1386,8 @@ extern "C" int dmx_groupalign_host(const uint32_t* seq2b, const uint32_t* nmask,
             cur.first.assign(5 * cur.mask.size(), 0);
             for (uint64_t x = member_off[g]; x < member_off[g + 1]; ++x) {
                 const size_t r = (size_t)(x - member_off[g]);
-                pd_decode(seq2b, nmask, offsets[members[x]], lens[members[x]], false, a);
+                pd_decode(seq2b, nmask, offsets[members[x]], lens[members[x]],
+                          member_flags && (member_flags[x] & DMX_PD_RC), a);
                 const uint32_t d = pa_dp_path(a, cur.mask, D, rev, [](uint8_t sym, uint8_t mk) {
                     return ((mk >> sym) & 1u) != 0;
                 });
@@ -1394,12 +1441,38 @@ extern "C" int dmx_groupalign_host(const uint32_t* seq2b, const uint32_t* nmask,
     return DMX_OK;
 }
 
-extern "C" int dmx_groupalign(dmx_ctx* c, size_t n_groups, const uint8_t* seed_masks,
-                              const uint64_t* seed_off, const uint32_t* members,
-                              const uint64_t* member_off, uint32_t max_cols, uint64_t* col_off,
-                              uint8_t* mask, uint16_t* count, uint16_t* first, size_t cols_cap,
-                              uint32_t* dist, uint64_t* op_off, uint8_t* ops, size_t ops_cap) {
-    const char* const who = "dmx_groupalign";
+extern "C" int dmx_groupalign_host(const uint32_t* seq2b, const uint32_t* nmask,
+                                   const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
+                                   size_t n_groups, const uint8_t* seed_masks,
+                                   const uint64_t* seed_off, const uint32_t* members,
+                                   const uint64_t* member_off, uint32_t max_cols, uint64_t* col_off,
+                                   uint8_t* mask, uint16_t* count, uint16_t* first, size_t cols_cap,
+                                   uint32_t* dist, uint64_t* op_off, uint8_t* ops, size_t ops_cap,
+                                   int n_threads) {
+    return ga_host("dmx_groupalign_host", seq2b, nmask, offsets, lens, n_reads, n_groups,
+                   seed_masks, seed_off, members, nullptr, member_off, max_cols, col_off, mask,
+                   count, first, cols_cap, dist, op_off, ops, ops_cap, n_threads);
+}
+
+extern "C" int dmx_groupalign_strands_host(
+    const uint32_t* seq2b, const uint32_t* nmask, const uint64_t* offsets, const uint32_t* lens,
+    size_t n_reads, size_t n_groups, const uint8_t* seed_masks, const uint64_t* seed_off,
+    const uint32_t* members, const uint8_t* member_flags, const uint64_t* member_off,
+    uint32_t max_cols, uint64_t* col_off, uint8_t* mask, uint16_t* count, uint16_t* first,
+    size_t cols_cap, uint32_t* dist, uint64_t* op_off, uint8_t* ops, size_t ops_cap,
+    int n_threads) {
+    return ga_host("dmx_groupalign_strands_host", seq2b, nmask, offsets, lens, n_reads, n_groups,
+                   seed_masks, seed_off, members, member_flags, member_off, max_cols, col_off,
+                   mask, count, first, cols_cap, dist, op_off, ops, ops_cap, n_threads);
+}
+
+// Both device entry points: member_flags == NULL is dmx_groupalign (`who` opens the messages).
+static int ga_device(const char* who, dmx_ctx* c, size_t n_groups, const uint8_t* seed_masks,
+                     const uint64_t* seed_off, const uint32_t* members,
+                     const uint8_t* member_flags, const uint64_t* member_off, uint32_t max_cols,
+                     uint64_t* col_off, uint8_t* mask, uint16_t* count, uint16_t* first,
+                     size_t cols_cap, uint32_t* dist, uint64_t* op_off, uint8_t* ops,
+                     size_t ops_cap) {
     if (!c) return DMX_E_INVALID;
     if (c->ga) {
         c->ga->ms[0] = c->ga->ms[1] = c->ga->ms[2] = 0.f;
@@ -1408,15 +1481,15 @@ extern "C" int dmx_groupalign(dmx_ctx* c, size_t n_groups, const uint8_t* seed_m
     const bool some = n_groups && member_off && member_off[n_groups] > member_off[0];
     if (!seed_off || !member_off || !col_off || (ops && !op_off) ||
         (n_groups && (!seed_masks || !mask || !count || !first)) || (some && (!members || !dist))) {
-        c->err = "dmx_groupalign: null argument";
+        c->err = std::string(who) + ": null argument";
         return DMX_E_INVALID;
     }
     std::vector<uint32_t> lens;
     if (const int rc = pd_fetch_lens(c, who, some ? 1 : 0, lens)) return rc;
     GaShape sh;
     if (const int rc = ga_validate(who, lens.data(), lens.size(), n_groups, seed_masks, seed_off,
-                                   members, member_off, max_cols, cols_cap, ops != nullptr, ops_cap,
-                                   sh, &c->err))
+                                   members, member_flags, member_off, max_cols, cols_cap,
+                                   ops != nullptr, ops_cap, sh, &c->err))
         return rc;
     col_off[0] = 0;
     if (ops) op_off[0] = 0;
@@ -1453,22 +1526,24 @@ extern "C" int dmx_groupalign(dmx_ctx* c, size_t n_groups, const uint8_t* seed_m
 
     PdPlan<GaPair> pl;
     std::vector<uint32_t> rq, rg, rn, res;
-    std::vector<uint8_t> region;
+    std::vector<uint8_t> rf, region;   // rf: the round's member flags (empty without any)
     std::vector<std::vector<uint8_t>> paths(ops ? sh.members : 0);
     float ms3[3] = {0.f, 0.f, 0.f};
     for (size_t round = 0; round < sh.rounds; ++round) {
         // member `round` of every group that has one, against the group's row as it stands
-        rq.clear(), rg.clear(), rn.clear();
+        rq.clear(), rg.clear(), rn.clear(), rf.clear();
         for (size_t g = 0; g < n_groups; ++g)
             if (member_off[g + 1] - member_off[g] > round) {
                 rq.push_back(members[member_off[g] + round]);
                 rg.push_back((uint32_t)g);
                 rn.push_back(cur[g]);
+                if (member_flags) rf.push_back(member_flags[member_off[g] + round]);
             }
         const size_t n_pairs = rq.size();
         for (size_t lo = 0; lo < n_pairs;) {
-            const size_t hi = pd_plan(pl, lens.data(), rq.data(), rg.data(), nullptr, nullptr,
-                                      n_pairs, lo, kPdChunkDefault, budget, rn.data());
+            const size_t hi = pd_plan(pl, lens.data(), rq.data(), rg.data(),
+                                      member_flags ? rf.data() : nullptr, nullptr, n_pairs, lo,
+                                      kPdChunkDefault, budget, rn.data());
             const size_t np = hi - lo;
             for (GaPair& P : pl.pairs) {
                 const size_t g = P.t;
@@ -1495,7 +1570,15 @@ extern "C" int dmx_groupalign(dmx_ctx* c, size_t n_groups, const uint8_t* seed_m
             // a pair the kernels skip must not leave a stale length behind
             PD_CK(who, hipMemsetAsync(A.out, 0, 2 * np * 4, st));
             PD_CK(who, hipEventRecord(s->ev[0], st));
-            pd_launch_forward(groupalign_kernel, A, st);
+            bool any_rc = false;   // a launch without a flagged member runs the plain form
+            for (const GaPair& P : pl.pairs) any_rc = any_rc || (P.flags & DMX_PD_RC);
+            if (any_rc) {
+                GaStrandArgs S;
+                static_cast<GaArgs&>(S) = A;
+                pd_launch_forward(groupalign_strands_kernel, S, st);
+            } else {
+                pd_launch_forward(groupalign_kernel, A, st);
+            }
             PD_CK(who, hipGetLastError());
             PD_CK(who, hipEventRecord(s->ev[1], st));
             set_kid(A.pk.bd, kKerGroupalignTb);
@@ -1531,7 +1614,7 @@ extern "C" int dmx_groupalign(dmx_ctx* c, size_t n_groups, const uint8_t* seed_m
                 const size_t g = P.t;
                 const uint32_t m = lens[P.q], n = P.n, len = res[2 * k + 1];
                 if (len > m + n || len < std::max(m, n)) {
-                    c->err = "dmx_groupalign: group " + std::to_string(g) + ", round " +
+                    c->err = std::string(who) + ": group " + std::to_string(g) + ", round " +
                              std::to_string(round) + ": path of " + std::to_string(len) +
                              " ops for a read of " + std::to_string(m) + " nt and a row of " +
                              std::to_string(n) + " columns";
@@ -1571,6 +1654,28 @@ extern "C" int dmx_groupalign(dmx_ctx* c, size_t n_groups, const uint8_t* seed_m
     PD_CK(who, hipStreamSynchronize(st));
     if (ops) ga_emit_paths(paths, op_off, ops);
     return DMX_OK;
+}
+
+extern "C" int dmx_groupalign(dmx_ctx* c, size_t n_groups, const uint8_t* seed_masks,
+                              const uint64_t* seed_off, const uint32_t* members,
+                              const uint64_t* member_off, uint32_t max_cols, uint64_t* col_off,
+                              uint8_t* mask, uint16_t* count, uint16_t* first, size_t cols_cap,
+                              uint32_t* dist, uint64_t* op_off, uint8_t* ops, size_t ops_cap) {
+    return ga_device("dmx_groupalign", c, n_groups, seed_masks, seed_off, members, nullptr,
+                     member_off, max_cols, col_off, mask, count, first, cols_cap, dist, op_off,
+                     ops, ops_cap);
+}
+
+extern "C" int dmx_groupalign_strands(dmx_ctx* c, size_t n_groups, const uint8_t* seed_masks,
+                                      const uint64_t* seed_off, const uint32_t* members,
+                                      const uint8_t* member_flags, const uint64_t* member_off,
+                                      uint32_t max_cols, uint64_t* col_off, uint8_t* mask,
+                                      uint16_t* count, uint16_t* first, size_t cols_cap,
+                                      uint32_t* dist, uint64_t* op_off, uint8_t* ops,
+                                      size_t ops_cap) {
+    return ga_device("dmx_groupalign_strands", c, n_groups, seed_masks, seed_off, members,
+                     member_flags, member_off, max_cols, col_off, mask, count, first, cols_cap,
+                     dist, op_off, ops, ops_cap);
 }
 
 // ---- dmx_rowdist: resident reads against rows of masks (include/dmx.h) -----------

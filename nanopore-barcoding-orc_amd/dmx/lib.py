@@ -43,6 +43,7 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_debug_bounds_selftest", "dmx_panel_pieces", "dmx_pairdist", "dmx_pairdist_host",
            "dmx_pairdist_group_sizes", "dmx_pairalign", "dmx_pairalign_host",
            "dmx_pairalign_stats", "dmx_groupalign", "dmx_groupalign_host", "dmx_groupalign_stats",
+           "dmx_groupalign_strands", "dmx_groupalign_strands_host",
            "dmx_rowdist", "dmx_rowdist_host", "dmx_edgegroups", "dmx_edgegroups_host",
            "dmx_pairhits", "dmx_pairhits_fetch", "dmx_hitgroups", "dmx_pairhits_host",
            "dmx_hitgroups_host", "dmx_hitgroups_stats"]
@@ -168,6 +169,10 @@ def load() -> ctypes.CDLL:
               c_size]
         L.dmx_groupalign.argtypes = [P] + ga
         L.dmx_groupalign_host.argtypes = [P, P, c_u64p, P, c_size] + ga + [c_int]
+    if hasattr(L, "dmx_groupalign_strands"):
+        gs = ga[:4] + [P] + ga[4:]   # member_flags after members
+        L.dmx_groupalign_strands.argtypes = [P] + gs
+        L.dmx_groupalign_strands_host.argtypes = [P, P, c_u64p, P, c_size] + gs + [c_int]
         L.dmx_groupalign_stats.argtypes = [P, ctypes.POINTER(ctypes.c_float), c_int,
                                            ctypes.POINTER(c_int)]
     if hasattr(L, "dmx_rowdist"):
@@ -462,16 +467,25 @@ class Context:
         return {"forward": float(ms[0]), "traceback": float(ms[1]), "launches": int(n)}
 
     # ---- progressive alignment of read groups (include/dmx.h dmx_groupalign) ----
-    def groupalign(self, seeds, groups, max_cols: int = 0, paths: bool = False) -> dict:
+    def groupalign(self, seeds, groups, max_cols: int = 0, paths: bool = False,
+                   strands=None) -> dict:
         """create_alignment's loop for many groups at once: seeds[g] is group g's row 0 (str or
         bytes over A/C/G/T/N/-/IUPAC, or a uint8 array of masks as mask_row makes them),
         groups[g] its members (resident read indices, in alignment order).  Returns a dict:
         col_off (uint64, n + 1), mask (uint8 per column), count and first (uint16, columns x 5:
         members showing A/C/G/T/N in the column, and the 1-based place of the first that did),
         dist (uint32 per member, group after group) and, with paths, op_off / ops as
-        pairalign's, one path per member against the row it met."""
-        a = _groupalign_args(getattr(self, "_lengths", None), seeds, groups, max_cols, paths)
-        self._check(self._L.dmx_groupalign(self._h, *a.call), "dmx_groupalign")
+        pairalign's, one path per member against the row it met.  strands: None, or a list
+        parallel to groups of 0 / 1 per member; 1 (PD_RC) takes the member reverse-complemented
+        (dmx_groupalign_strands), and dist, ops, count and first are then those of the turned
+        read."""
+        a = _groupalign_args(getattr(self, "_lengths", None), seeds, groups, max_cols, paths,
+                             strands=strands)
+        if strands is None:
+            self._check(self._L.dmx_groupalign(self._h, *a.call), "dmx_groupalign")
+        else:
+            self._check(self._L.dmx_groupalign_strands(self._h, *a.call),
+                        "dmx_groupalign_strands")
         return a.result()
 
     def groupalign_stats(self) -> dict:
@@ -717,7 +731,8 @@ def mask_symbols(mask) -> str:
 class _groupalign_args:
     """The packed arguments and caller-sized outputs of dmx_groupalign(_host)."""
 
-    def __init__(self, lengths, seeds, groups, max_cols, paths, ops_cap=None, cols_cap=None):
+    def __init__(self, lengths, seeds, groups, max_cols, paths, ops_cap=None, cols_cap=None,
+                 strands=None):
         if len(seeds) != len(groups):
             raise DmxError("groupalign: one seed row per group")
         rows = [np.ascontiguousarray(s, dtype=np.uint8) if isinstance(s, np.ndarray)
@@ -731,6 +746,12 @@ class _groupalign_args:
             self.member_off[1:] = np.cumsum([len(g) for g in mem])
         self.seeds = np.concatenate(rows + [np.zeros(0, dtype=np.uint8)])
         self.members = np.concatenate(mem + [np.zeros(0, dtype=np.uint32)])
+        self.flags = None   # strands: one flag byte per member (dmx_groupalign_strands)
+        if strands is not None:
+            fl = [np.ascontiguousarray(f, dtype=np.uint8).reshape(-1) for f in strands]
+            if len(fl) != n or any(len(f) != len(g) for f, g in zip(fl, mem)):
+                raise DmxError("groupalign: strands must be parallel to groups, one per member")
+            self.flags = np.concatenate(fl + [np.zeros(0, dtype=np.uint8)])
         # the library's bounds (include/dmx.h): a row grows by a member's length at most
         nr = 0 if lengths is None else len(lengths)
         ln = np.zeros(nr + 1, dtype=np.int64)
@@ -752,7 +773,9 @@ class _groupalign_args:
         self.op_off = np.zeros(len(self.members) + 1, dtype=np.uint64) if paths else None
         self.ops = np.zeros(max(ops, 1), dtype=np.uint8) if paths else None
         self.call = (n, self.seeds.ctypes.data, self.seed_off.ctypes.data,
-                     self.members.ctypes.data, self.member_off.ctypes.data, int(max_cols),
+                     self.members.ctypes.data) + \
+                    (() if self.flags is None else (self.flags.ctypes.data,)) + \
+                    (self.member_off.ctypes.data, int(max_cols),
                      self.col_off.ctypes.data, self.mask.ctypes.data, self.count.ctypes.data,
                      self.first.ctypes.data, cols, self.dist.ctypes.data,
                      self.op_off.ctypes.data if paths else None,
@@ -769,18 +792,20 @@ class _groupalign_args:
 
 
 def groupalign_host(p: "Packed", seeds, groups, max_cols: int = 0, paths: bool = False,
-                    n_threads: int = 1, ops_cap=None, cols_cap=None) -> dict:
+                    n_threads: int = 1, ops_cap=None, cols_cap=None, strands=None) -> dict:
     """dmx_groupalign's contract on the host, group after group and member after member (no
     GPU): the checker of the kernels and the CPU comparator of tools/bench_groupalign.py.
     ops_cap, cols_cap: the room given to the library instead of its bounds (to see it refused).
-    Returns the dict of Context.groupalign."""
+    strands: as Context.groupalign's (dmx_groupalign_strands_host).  Returns the dict of
+    Context.groupalign."""
     L = load()
-    a = _groupalign_args(p.lengths, seeds, groups, max_cols, paths, ops_cap, cols_cap)
-    rc = L.dmx_groupalign_host(p.seq2b.ctypes.data, p.nmask.ctypes.data, p.offsets.ctypes.data,
-                               p.lengths.ctypes.data, p.n_reads, *a.call, int(n_threads))
+    a = _groupalign_args(p.lengths, seeds, groups, max_cols, paths, ops_cap, cols_cap, strands)
+    name = "dmx_groupalign_host" if strands is None else "dmx_groupalign_strands_host"
+    rc = getattr(L, name)(p.seq2b.ctypes.data, p.nmask.ctypes.data, p.offsets.ctypes.data,
+                          p.lengths.ctypes.data, p.n_reads, *a.call, int(n_threads))
     if rc < 0:
         msg = L.dmx_last_error(None)
-        raise DmxError(f"dmx_groupalign_host failed ({rc}): {msg.decode() if msg else ''}")
+        raise DmxError(f"{name} failed ({rc}): {msg.decode() if msg else ''}")
     return a.result()
 
 

@@ -15,8 +15,11 @@ consensus() restates create_consensus (:358-428) for many groups at once on top 
 dmx_groupalign, which runs create_alignment's loop (:324-356) in lock-step
 over the groups and returns per-column symbol counts, all the consensus reads of an alignment.
 alignment_rows() rebuilds the gapped rows themselves from the returned paths (the -aln output,
-and the tests).  Out of scope: -amb (ambiguity, degenerate), the callers' random sampling and
-consensus_direction (the reads are taken as they come, already oriented).
+and the tests).  orient() restates consensus_direction (:1826-1838) on dmx_pairdist, and
+make_consensus() is make_consensus (:1089-1105): orient(), then consensus() with every read's
+strand passed to dmx_groupalign_strands, so that gene groups, which mix both orientations, go
+straight into the alignment on one resident batch.  Out of scope: -amb (ambiguity, degenerate)
+and the callers' random sampling.
 """
 from __future__ import annotations
 
@@ -226,39 +229,149 @@ def _final_correction(top, top_n, c, treshold):
     return "".join(out)
 
 
-def consensus(ctx, reads, groups, ambiguous: bool = False, n_threads: int = 16) -> list:
+_RC = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def revcomp(seq: bytes) -> bytes:
+    """compl_reverse (:237-242) over A/C/G/T/N: backwards, complemented, N stays."""
+    return seq[::-1].translate(_RC)
+
+
+def _pack_reads(ctx, reads):
+    """The cleaned reads, their lengths and their batch, packed once and loaded into ctx (when
+    there is one): what orient(), consensus() and make_consensus() run on."""
+    seqs = _clean(reads)
+    ln = np.array([len(s) for s in seqs], dtype=np.int64)
+    if len(ln) and int(ln.max()) > lib.PD_MAX_LEN:
+        raise DmxError(f"a read is longer than {lib.PD_MAX_LEN} nt")
+    p = None
+    if len(seqs):
+        blob = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+        offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
+        p = lib.pack(blob, offs, ln.astype(np.uint32))
+        if ctx is not None:
+            ctx.load(p)
+    return seqs, ln, p
+
+
+def _orient(ctx, p, seqs, ln, groups, n_threads):
+    """orient() on a batch that is packed (p) and, with a ctx, resident."""
+    orders, q, t = [], [], []
+    for k, g in enumerate(groups):
+        g = np.asarray(g, dtype=np.int64).reshape(-1)
+        if len(g) and (int(g.min()) < 0 or int(g.max()) >= len(seqs)):
+            raise DmxError(f"orient: group {k} names a read outside the reads")
+        o = g[np.argsort(ln[g], kind="stable")] if len(g) else g
+        orders.append(o)
+        q.append(np.full(max(len(o) - 1, 0), o[0] if len(o) else 0, dtype=np.int64))
+        t.append(o[1:])
+    q = np.concatenate(q + [np.zeros(0, dtype=np.int64)])
+    t = np.concatenate(t + [np.zeros(0, dtype=np.int64)])
+    d = np.zeros(0, dtype=np.int64)
+    if len(q):   # one call: every (anchor, other) pair forward, then reverse-complemented
+        flags = np.concatenate([np.zeros(len(q), dtype=np.uint8),
+                                np.full(len(q), lib.PD_RC, dtype=np.uint8)])
+        q2, t2 = np.concatenate([q, q]), np.concatenate([t, t])
+        d = (ctx.pairdist(q2, t2, lib.PD_NW, flags=flags) if ctx is not None
+             else lib.pairdist_host(p, q2, t2, lib.PD_NW, flags=flags, n_threads=n_threads))
+        d = d.astype(np.int64)
+    members, strands, at = [], [], 0
+    for k, o in enumerate(orders):
+        mem, st, seen = [], [], set()
+        for x, y in enumerate(o):
+            turned = 0
+            if x:   # distance() divides by the longer read's length: y's (rising lengths)
+                iden = identity(int(d[at + x - 1]), int(ln[y]))
+                iden_r = identity(int(d[len(q) + at + x - 1]), int(ln[y]))
+                turned = 0 if iden > iden_r else 1
+            s = revcomp(seqs[y]) if turned else seqs[y]
+            if s not in seen and len(o) > 1:   # the anchor enters the set with the first other
+                seen.add(s)
+                mem.append(int(y))
+                st.append(turned)
+        at += max(len(o) - 1, 0)
+        if len(mem) < 2:
+            raise DmxError(f"orient: group {k} has {len(mem)} distinct oriented reads (2 at "
+                           "least make a consensus)")
+        members.append(np.array(mem, dtype=np.int64))
+        strands.append(np.array(st, dtype=np.uint8))
+    return members, strands
+
+
+def orient(ctx, reads, groups, n_threads: int = 16):
+    """consensus_direction (:1826-1838) as make_consensus (:1089-1105) calls it, for many groups
+    at once.  Per group (indices into `reads`): a stable sort by rising length; the first read
+    is the anchor x and stays forward; every other read y stays forward iff
+    identity(d(x, y), len(y)) > identity(d(x, rc(y)), len(y)), so a tie turns it round (a
+    palindromic read is always turned, into itself).  The distances are one pairdist call over
+    all groups (NW, half the pairs with PD_RC); ctx: a Context, or None for lib.pairdist_host.
+    The reference collects the oriented sequences in a set: equal oriented byte strings
+    collapse here to the first one.  Parity finding: the reference's resulting order is
+    Python's string-hash order of that set, which differs from run to run; here it is first
+    appearance in the length-sorted list.  A group left with fewer than 2 reads is refused (in
+    the reference a one-read group leaves the set empty and create_consensus fails on pop(0)).
+    Returns (members, strands): per group the kept read indices and, parallel, 0 = forward,
+    1 = reverse-complemented."""
+    seqs, ln, p = _pack_reads(ctx, reads)
+    return _orient(ctx, p, seqs, ln, groups, n_threads)
+
+
+def consensus(ctx, reads, groups, ambiguous: bool = False, n_threads: int = 16,
+              strands=None) -> list:
     """create_consensus (:358-428) for many groups at once: `groups` are lists of indices into
     `reads` (str or bytes over A/C/G/T/N, already oriented).  Per group: a stable sort by
     falling length, the longest read seeds cycle 1 and the others are aligned against it;
     cycles 2 and 3 align every read, the seed included, against the previous cycle's
     consensus.  Every group of the call goes into each of the three groupalign calls.  ctx: a
-    Context, or None to run on the host reference (lib.groupalign_host, n_threads).  Returns
-    the consensus strings, one per group."""
+    Context, or None to run on the host reference (lib.groupalign_host, n_threads).
+    strands: None, or parallel to groups, 0 / 1 per read as orient() returns them: a read
+    marked 1 enters reverse-complemented (groupalign's strands; no read is turned on the host
+    but a cycle-1 seed).  Returns the consensus strings, one per group."""
     if ambiguous:
         raise DmxError("consensus: -amb (ambiguity, degenerate) is not supported")
-    seqs = _clean(reads)
-    ln = np.array([len(s) for s in seqs], dtype=np.int64)
-    if len(ln) and int(ln.max()) > lib.PD_MAX_LEN:
-        raise DmxError(f"a read is longer than {lib.PD_MAX_LEN} nt")
-    orders = []
+    seqs, ln, p = _pack_reads(ctx, reads)
+    return _consensus(ctx, p, seqs, ln, groups, strands, n_threads)
+
+
+def make_consensus(ctx, reads, groups, n_threads: int = 16) -> list:
+    """make_consensus (:1089-1105) for many groups at once: orient(), then consensus()'s three
+    cycles with the strands passed through to groupalign.  The batch is packed and loaded
+    once; the orientation distances and the alignments both run on it, and no read is turned
+    round on the host.  Not restated: the random sampling of comp_consensus_groups, which picks
+    the reads before this is called."""
+    seqs, ln, p = _pack_reads(ctx, reads)
+    members, strands = _orient(ctx, p, seqs, ln, groups, n_threads)
+    return _consensus(ctx, p, seqs, ln, members, strands, n_threads)
+
+
+def _consensus(ctx, p, seqs, ln, groups, strands, n_threads):
+    """consensus() on a batch that is packed (p) and, with a ctx, resident."""
+    if strands is not None and len(strands) != len(groups):
+        raise DmxError("consensus: strands must be parallel to groups")
+    orders, sorders = [], None if strands is None else []
     for k, g in enumerate(groups):
         g = np.asarray(g, dtype=np.int64).reshape(-1)
         if not len(g):
             raise DmxError(f"consensus: group {k} has no reads")
-        orders.append(g[np.argsort(-ln[g], kind="stable")])
+        by_len = np.argsort(-ln[g], kind="stable")
+        orders.append(g[by_len])
+        if strands is not None:
+            s = np.asarray(strands[k], dtype=np.uint8).reshape(-1)
+            if len(s) != len(g) or (len(s) and int(s.max()) > 1):
+                raise DmxError(f"consensus: group {k}: strands are 0 or 1, one per read")
+            sorders.append(s[by_len])
     if not orders:
         return []
-    blob = np.frombuffer(b"".join(seqs), dtype=np.uint8)
-    offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
-    p = lib.pack(blob, offs, ln.astype(np.uint32))
-    if ctx is not None:
-        ctx.load(p)
     seeds = [seqs[o[0]] for o in orders]
     members = [o[1:] for o in orders]
+    mstr = None
+    if strands is not None:   # a reversed longest read seeds cycle 1 as its reverse complement
+        seeds = [revcomp(s) if so[0] else s for s, so in zip(seeds, sorders)]
+        mstr = [so[1:] for so in sorders]
     tops = []
     for treshold in THRESHOLDS:
-        res = (ctx.groupalign(seeds, members) if ctx is not None
-               else lib.groupalign_host(p, seeds, members, n_threads=n_threads))
+        res = (ctx.groupalign(seeds, members, strands=mstr) if ctx is not None
+               else lib.groupalign_host(p, seeds, members, n_threads=n_threads, strands=mstr))
         tops, seeds = [], []
         for k, mem in enumerate(members):
             c = len(mem) + 1
@@ -267,7 +380,7 @@ def consensus(ctx, reads, groups, ambiguous: bool = False, n_threads: int = 16) 
             seeds.append("".join(_SYMS[x] for x in top[top_n > c * treshold]))
             if not seeds[-1]:
                 raise DmxError(f"consensus: group {k}: no column passes the threshold")
-        members = orders   # the full list from the second cycle on
+        members, mstr = orders, sorders   # the full list from the second cycle on
     return [_final_correction(top, top_n, c, THRESHOLDS[-1]) for top, top_n, c in tops]
 
 
@@ -294,8 +407,8 @@ def assign(ctx, reads, unassigned, consensuses, similar: float, n_threads: int =
 
     Returns (lines, best, added): best has one (read, group, iden) per read that has a line, in
     first-appearance order; added are the entries of best with iden >= similar.  The outer
-    rest_reads loop, the sampling above 200 reads, finetune, compare_consensus and
-    consensus_direction are the caller's."""
+    rest_reads loop, the sampling above 200 reads, finetune and compare_consensus are the
+    caller's (consensus_direction is orient())."""
     seqs = _clean(reads)
     cons = _clean(consensuses, "consensus")
     for g, s in enumerate(cons):
@@ -518,13 +631,23 @@ def main(argv=None) -> int:
         prog="dmx-similarity",
         description="The similarity pass of amplicon_sorter.py (pairwise identities of one "
                     "bin's reads) on the GPU, and with --groups the gene groups of its best "
-                    "hits; comp_consensus_groups onward stays with the reference.")
+                    "hits, and with --consensus a consensus per gene group; "
+                    "comp_consensus_groups' sampling and merge loop and everything after stay "
+                    "with the reference.")
     ap.add_argument("-i", "--input", required=True, help="bin in FASTQ/FASTA, optionally .gz")
     ap.add_argument("-o", "--output", default=None,
                     help="similarity lines (i:j:iden[:reverse]); optional with --groups")
     ap.add_argument("--groups", default=None, metavar="FILE",
                     help="gene groups, one per line: space-separated read indices, in the "
                          "reference's group order")
+    ap.add_argument("--consensus", default=None, metavar="FILE",
+                    help="with --groups: FASTA, one '>group_<k>(<n reads>)' record per gene "
+                         "group, the consensus of the group's first --consensus-reads reads in "
+                         "index order, oriented and aligned on the GPU (make_consensus); the "
+                         "reference samples that many reads at random (comp_consensus_groups)")
+    ap.add_argument("--consensus-reads", type=int, default=50, metavar="N",
+                    help="reads per group that make its consensus (default 50, the reference's "
+                         "sample size)")
     ap.add_argument("-min", "--minlength", type=int, default=300)
     ap.add_argument("-max", "--maxlength", type=int, default=None)
     ap.add_argument("-maxr", "--maxreads", type=int, default=10000)
@@ -534,6 +657,10 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.output is None and a.groups is None:
         ap.error("the following arguments are required: -o/--output")
+    if a.consensus is not None and a.groups is None:
+        ap.error("--consensus needs --groups")
+    if a.consensus_reads < 2:
+        ap.error("--consensus-reads must be at least 2")
     try:
         reads = read_sequences(a.input)
         with lib.Context(a.device) as ctx:
@@ -549,6 +676,16 @@ def main(argv=None) -> int:
                     f.write("".join(" ".join(str(int(x)) for x in g) + "\n" for g in groups))
                 print(f"dmx-similarity: {len(reads)} reads, {len(groups)} gene groups -> "
                       f"{a.groups}", file=sys.stderr)
+                if a.consensus is not None:
+                    # the groups index the length-filtered reads
+                    kept = [reads[i] for i in usable([len(s) for s in reads], a.minlength,
+                                                     a.maxlength)]
+                    cons = make_consensus(ctx, kept, [g[:a.consensus_reads] for g in groups])
+                    with open(a.consensus, "w") as f:
+                        f.write("".join(f">group_{k}({len(g)})\n{c}\n"
+                                        for k, (g, c) in enumerate(zip(groups, cons))))
+                    print(f"dmx-similarity: {len(cons)} consensus sequences -> {a.consensus}",
+                          file=sys.stderr)
     except (DmxError, OSError, ValueError) as e:
         print(f"dmx-similarity: {e}", file=sys.stderr)
         return 1
