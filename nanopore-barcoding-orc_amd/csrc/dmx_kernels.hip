@@ -1879,7 +1879,12 @@ ps_lookups(const uint32_t* bm, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w
 // batches): one lane per (item, part) of the item's orientation-0 view; the lane streams its
 // part's codes, looks up the sampled 8-mers, checks hits against their (piece, offset) entries
 // on the codes held in registers, and marks the 16-position cells of the view where an
-// alignment containing a verified copy can end.  A part owns the copies that START in it.
+// alignment containing a verified copy can end.  A part [a, b) owns the copies that START in it
+// (a <= g < b, so no copy is marked twice) and samples x = a, a + S, ... < b + kPieceMaxOff: an
+// entry's 8-mer sits up to kPieceMaxOff nt into its piece, so the copies that start in the last
+// nt of the part are sampled past b.  (Sampling only to b + S - 1 lost the copies at b - 1 and
+// b - 2 of pieces whose sampled offsets start at S or later.)  The last part's samples past the
+// view read the pad, as every part's last step does, and own nothing (g + len <= n).
 // ---------------------------------------------------------------------------------------------
 #ifndef DMX_PIECE_WAVES
 #define DMX_PIECE_WAVES 1
@@ -1961,7 +1966,10 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
             }
             // stream the part: w0..w5 = view positions [a - 16 + 64k, a + 80 + 64k) in step k,
             // which samples x = a + 64k + q S: the 8-mer of positions [x, x + 8)
-            const int xe = b + S - 1;                  // copies starting in [a, b) are sampled
+            // A copy starting at g in [a, b) is found through the entry whose sampled 8-mer sits
+            // at x = g + off, off <= kPieceMaxOff: the part samples up to b - 1 + kPieceMaxOff
+            // (the samples past b serve only the copies starting before it: g < b below).
+            const int xe = b + kPieceMaxOff;
             const int nsteps = (act && n > 0) ? (xe - a + 63) / 64 : 0;
             if (nsteps > 0) {
                 uint32_t w0, w1, w2, w3, w4, w5, nb;
@@ -2000,7 +2008,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
                             const int off = (int)((ev >> 38) & 3u);
                             const int g = x - off;
                             if (g < a || g >= b || g + len > n) continue;
-                            const int ug = u - off;    // 14 .. 79
+                            const int ug = u - off;    // 13 .. 79: [ug, ug + 16) lies in w0..w5
                             const uint32_t gi = (uint32_t)ug >> 4;
                             const uint32_t cw = align32(sel5(gi, w1, w2, w3, w4, w5),
                                                         sel5(gi, w0, w1, w2, w3, w4),

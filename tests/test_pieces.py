@@ -5,14 +5,18 @@ its K + 1 pieces (so exactly one piece survives as an exact copy), for every sur
 both read orientations, at the read start, middle and end; partial adapters at both read ends;
 N inside and around the pieces.  The flat scan (dmx_pack layouts, permuted read order, reads
 that overlap in the packed batch), the per-part screen (DMX_NO_FLAT=1) and the full filter pass
-(DMX_NO_PIECES=1) must all equal the oracle on every result byte.
+(DMX_NO_PIECES=1) must all equal the oracle on every result byte.  The seam tests at the end
+place the surviving piece on the part boundaries of the per-part screen and on the lane and
+superblock seams of the flat scan (pieces_seam_cases.py).
 """
 import numpy as np
 import pytest
 
 import oracle
 from dmx import lib, synth
-from test_pieces_host import _flank_cases, full_k, mutate, pieces_of, revcomp
+from test_pieces_host import (SEAM_PANELS, _flank_cases, _seam_case, full_k, mutate, pieces_of,
+                              revcomp)
+import pieces_seam_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -227,3 +231,117 @@ def test_shared_flank_panels(name, panel, where, rate, variant, monkeypatch):
         tasks = c.stats()["filter_tasks"]
     _assert_same(got, exp)
     assert tasks[0] > 0
+
+
+# ---------------------------------------------------------------------------------------------
+# Seams: the surviving piece on a part boundary of the per-part screen, on a lane or superblock
+# seam of the flat scan, and block steps of the per-part screen with many items and parts
+# ---------------------------------------------------------------------------------------------
+def _run_checked(seqs, panel, where, rate, rc, use_perm=False):
+    """(results in read order, filter tasks) of one single-round run in a context of its own; the
+    pipeline flags show neither a cell outside a part's mask (16) nor a full list (4)."""
+    blob, offs, lens = oracle.pack_ascii(seqs)
+    p = lib.pack(blob, offs, lens)
+    perm = None
+    if use_perm:
+        perm = np.random.default_rng(2).permutation(p.n_reads)
+        p = lib.Packed(p.seq2b, p.nmask, p.offsets[perm].copy(), p.lengths[perm].copy())
+    with lib.Context(0) as c:
+        c.set_panel(0, list(panel), where | (lib.DMX_RC if rc else 0), rate)
+        c.set_mode(lib.MODE_SINGLE)
+        got = c.run(p)
+        tasks = c.stats()["filter_tasks"]
+        flags = int(c.debug_fetch(lib.DBG_FLAGS, 0)[0])
+    assert flags & (16 | 4) == 0, flags
+    if perm is not None:
+        inv = np.empty_like(perm)
+        inv[perm] = np.arange(len(perm))
+        got = got[inv]
+    return got, tasks
+
+
+def _oracle(seqs, panel, where, rate, rc):
+    blob, offs, lens = oracle.pack_ascii(seqs)
+    w = oracle.FRONT if where == lib.DMX_FRONT else oracle.BACK
+    return oracle.run_batch(oracle.Panel(list(panel), w, max_errors=rate), None, blob, offs, lens,
+                            mode=0, use_rc=rc, threads=8)
+
+
+@pytest.mark.parametrize("part", [64, 0])
+@pytest.mark.parametrize("variant", ["no_flat", "one_orientation"])
+@pytest.mark.parametrize("name", SEAM_PANELS)
+def test_part_seams(name, variant, part, monkeypatch):
+    """The seam reads of pieces_seam_cases.py (the surviving piece starts at b - 3 .. b + 1 of
+    the first and last interior part boundary b, both strands) through the per-part screen: with
+    both orientations (DMX_NO_FLAT=1) and as a one-orientation panel, which always takes it; with
+    64-position parts in reads of 160 nt and with the table's own parts in reads of 2.5 parts."""
+    rc = variant == "no_flat"
+    panel, where, rate = sc.panel(name)
+    seqs = _seam_case(name, rc, part, monkeypatch)[0]   # (sets DMX_PIECE_PART)
+    exp = _oracle(seqs, panel, where, rate, rc)
+    assert (exp["bin1"] >= 0).mean() > 0.7
+    if rc:
+        monkeypatch.setenv("DMX_NO_FLAT", "1")
+    got, tasks = _run_checked(seqs, panel, where, rate, rc)
+    _assert_same(got, exp)
+    assert tasks[0] > 0
+
+
+@pytest.mark.parametrize("where", [lib.DMX_FRONT, lib.DMX_BACK])
+def test_many_parts_per_block(where, monkeypatch):
+    """Per-part screen with 64-position parts over 1500 reads of 0 .. 1000 nt: a block step holds
+    512 items and thousands of (item, part) tasks (the prefix search, the task loop), views of
+    0 parts (an empty FRONT view), of 1 part (an empty BACK view: its last-column window; reads
+    of 1 .. 64 nt) and of up to 16; the adapter copy (one surviving piece) in a random part."""
+    n1, s5, n2, s27 = synth.panels(24, 24)
+    panel = s5 if where == lib.DMX_FRONT else s27
+    rng = np.random.default_rng(300 + where)
+    seqs = []
+    for i in range(1500):
+        ad = panel[i % 24]
+        K = full_k(len(ad), 0.1)
+        copy = mutate(rng, ad, pieces_of(len(ad), K), int(rng.integers(K + 1)))
+        n = int(rng.integers(0, 1001))
+        if n < len(copy) + 2:
+            s = _rand(rng, n)
+        else:
+            left = int(rng.integers(0, n - len(copy) + 1))
+            s = _rand(rng, left) + copy + _rand(rng, n - left - len(copy))
+        seqs.append(revcomp(s) if rng.random() < 0.5 else s)
+    seqs[0], seqs[1], seqs[700], seqs[701], seqs[-2], seqs[-1] = "", "G", "", "T", "C", ""
+    assert sum(sc.part_len(len(s), 64) and -(-len(s) // sc.part_len(len(s), 64))
+               for s in seqs[:512]) > 8 * 256
+    exp = _oracle(seqs, panel, where, 0.1, True)
+    assert (exp["bin1"] >= 0).mean() > 0.7
+    monkeypatch.setenv("DMX_NO_FLAT", "1")
+    monkeypatch.setenv("DMX_PIECE_PART", "64")
+    got, tasks = _run_checked(seqs, panel, where, 0.1, True)
+    _assert_same(got, exp)
+    assert tasks[0] > 0
+
+
+@pytest.mark.parametrize("flip", [0, 1])
+@pytest.mark.parametrize("name", ["sp5", "flank3"])
+def test_flat_scan_seams(name, flip):
+    """The flat scan with the surviving piece's copy starting at batch nt 64 j + d (lane seams:
+    the neighbour's words come by shuffles) and 4096 s + d (superblock seams: the LDS copy's 4
+    words before and after), d = -19 .. 3, on both strands; a copy starting at the first read's
+    first nt and one ending at the last read's last nt.  The permuted batch reads the same marks
+    by batch nt."""
+    panel, where, rate = sc.panel(name)
+    seqs, meta = sc.flat_seam_reads(np.random.default_rng(400 + flip), panel, rate, flip)
+    for kind in ("lane", "superblock"):
+        assert {(d, s) for k, _, d, s in meta if k == kind} == \
+            {(d, s) for d in sc.FLAT_D for s in (0, 1)}
+    blob, offs, lens = oracle.pack_ascii(seqs)
+    p = lib.pack(blob, offs, lens)
+    for (kind, nt, d, s), o, n in zip(meta, p.offsets.tolist(), p.lengths.tolist()):
+        assert o <= nt - min(d, 0) < o + n     # the seam lies in the read that holds the copy
+        assert (nt - d) % (4096 if kind == "superblock" else 64 if kind == "lane" else 1) == 0
+    assert meta[0][1] == p.offsets[0] and meta[-1][1] == p.offsets[-1] + p.lengths[-1] - 1
+    exp = _oracle(seqs, panel, where, rate, True)
+    assert (exp["bin1"] >= 0).mean() > 0.7
+    for use_perm in (False, True):
+        got, tasks = _run_checked(seqs, panel, where, rate, True, use_perm)
+        _assert_same(got, exp)
+        assert tasks[0] > 0

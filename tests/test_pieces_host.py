@@ -278,3 +278,97 @@ def test_entry_fields_on_random_panels():
             assert offs == list(range(offs[0], offs[0] + info["step"])) and offs[-1] <= 3
             assert offs[-1] + 8 <= es[0]["len"]
     assert seen >= 10
+
+
+# ---------------------------------------------------------------------------------------------
+# Part seams (pieces_seam_cases.py): the per-part screen's ownership and sampling rule
+# ---------------------------------------------------------------------------------------------
+import pieces_seam_cases as sc   # noqa: E402  (it takes mutate, pieces_of, ... from this module,
+                                 # so nothing of it is used before a test runs)
+
+SEAM_PANELS = ("flank3", "stride2", "sp5")   # == sc.PANELS (test_part_len_and_boundaries)
+SEAM_SEED = {"flank3": 31, "stride2": 32, "sp5": 33}
+
+
+def _seam_case(name, rc, part, monkeypatch):
+    """(reads, ends, strands, stats, info, ents, part_max) of a panel's seam reads: part = 64 with
+    reads of 160 nt (three parts), or the table's own part_max with reads of 2.5 parts."""
+    seqs, where, rate = sc.panel(name)
+    if part:
+        monkeypatch.setenv("DMX_PIECE_PART", str(part))
+    r, info, ents = lib.panel_pieces(list(seqs), where | (lib.DMX_RC if rc else 0), rate)
+    assert r == 0 and info["step"] > 0
+    pmax = info["part_max"]
+    assert pmax == (part or pmax)
+    n = 160 if part else pmax * 5 // 2
+    rng = np.random.default_rng(SEAM_SEED[name])
+    return sc.seam_reads(rng, seqs, rate, info, ents, pmax, n) + (info, ents, pmax)
+
+
+def _missed(case, n_orient, reach):
+    reads, ends, strands, _, info, ents, pmax = case
+    return [i for i, (r, e, s) in enumerate(zip(reads, ends, strands))
+            if e not in sc.model_marks_parts(r, ents, info["step"], pmax, n_orient, reach)[s]]
+
+
+def test_part_len_and_boundaries():
+    assert SEAM_PANELS == sc.PANELS
+    assert sc.part_len(160, 64) == 64 and sc.boundaries(160, 64) == [64, 128]
+    assert sc.part_len(1920, 768) == 640 and sc.boundaries(1920, 768) == [640, 1280]
+    assert sc.part_len(768, 768) == 768 and sc.boundaries(768, 768) == []
+    assert sc.part_len(769, 768) == 400 and sc.boundaries(769, 768) == [400]
+    assert sc.part_len(5, 768) == 16 and sc.part_len(0, 768) == 0
+
+
+@pytest.mark.parametrize("part", [64, 0])
+@pytest.mark.parametrize("rc", [True, False])
+@pytest.mark.parametrize("name", SEAM_PANELS)
+def test_seam_reads_end_in_marked_columns(name, rc, part, monkeypatch):
+    """The kernel's rule (sample up to kPieceMaxOff past the part) marks every seam read's end
+    column; at most 10 % of the cases are skipped as ambiguous; both strands and both
+    boundaries are there."""
+    case = _seam_case(name, rc, part, monkeypatch)
+    reads, ends, strands, stats = case[:4]
+    assert stats["skipped"] <= 0.1 * stats["cases"], stats
+    assert len(reads) == stats["cases"] - stats["skipped"] > 100, stats
+    assert set(strands) == ({0, 1} if rc else {0})
+    assert all(len(r) == len(reads[0]) for r in reads)
+    assert _missed(case, 2 if rc else 1, sc.PIECE_MAX_OFF) == []
+    if rc:   # a one-orientation run on the two-orientation table finds the forward copies
+        fwd = [i for i, s in enumerate(strands) if s == 0]
+        assert not set(_missed(case, 1, sc.PIECE_MAX_OFF)) & set(fwd)
+
+
+@pytest.mark.parametrize("part", [64, 0])
+@pytest.mark.parametrize("name", SEAM_PANELS)
+def test_seam_reads_are_telling(name, part, monkeypatch):
+    """A statement about the inputs, made on the model: sampling only to b + step - 1 (the rule
+    the kernel had before it sampled to b + kPieceMaxOff) loses seam reads of the panels whose
+    pieces are sampled past offset `step - 1`, every one of them with the piece starting before
+    the boundary, and none of SP5's, whose windows are {0, 1} and {1, 2}."""
+    case = _seam_case(name, True, part, monkeypatch)
+    reads, ends, strands, _, info, ents, pmax = case
+    missed = _missed(case, 2, info["step"] - 1)
+    if name == "sp5":
+        assert missed == []
+        return
+    assert missed, name
+    for i in missed:   # only a piece that starts at b - 1 or b - 2 can be lost
+        full = sc.model_marks_parts(reads[i], ents, info["step"], pmax, 2, sc.PIECE_MAX_OFF)
+        assert ends[i] in full[strands[i]]
+
+
+def test_stride2_panel_keeps_its_offsets():
+    """The frozen stride-2 panel still has a piece sampled at offsets {2, 3}, in the table of
+    both orientations and of one (a change of build_pieces must not disarm the seam cases)."""
+    seqs, where, rate = sc.panel("stride2")
+    for flags in (where | lib.DMX_RC, where):
+        r, info, ents = lib.panel_pieces(list(seqs), flags, rate)
+        assert r == 0 and info["step"] == 2
+        by_piece = {}
+        for e in ents:
+            by_piece.setdefault((e["val"], e["len"], e["o"]), []).append(e["off"])
+        assert any(sorted(v) == [2, 3] for v in by_piece.values())
+    seqs, where, rate = sc.panel("flank3")   # and flank3 its stride 1 with offsets >= 1
+    r, info, ents = lib.panel_pieces(list(seqs), where | lib.DMX_RC, rate)
+    assert r == 0 and info["step"] == 1 and any(e["off"] >= 1 for e in ents)
