@@ -2881,12 +2881,116 @@ __device__ __forceinline__ void myers_step_pk(uint32_t eq, uint32_t& pv, uint32_
     mv = ph2 & xv;
 }
 
+// The same step without the cost: d is redundant state.  Row 0 is free and the padding rows
+// always match, so a half's last-row cost is the sum of its vertical deltas,
+// popcount(pv) - popcount(mv), at every column (pk_cost_from_deltas).
+__device__ __forceinline__ void myers_step_pk_bare(uint32_t eq, uint32_t& pv, uint32_t& mv) {
+    const uint32_t xv = eq | mv;
+    const uint32_t s = as_u32(as_pk(eq & pv) + as_pk(pv));
+    const uint32_t ph = mv | ~(s | pv | eq);
+    const uint32_t mh = pv & ((s ^ pv) | eq);
+    const uint32_t ph2 = as_u32(as_pk(ph) << (uint16_t)1);
+    const uint32_t mh2 = as_u32(as_pk(mh) << (uint16_t)1);
+    pv = mh2 | ~(xv | ph2);
+    mv = ph2 & xv;
+}
+
+__device__ __forceinline__ u16x2 pk_cost_from_deltas(uint32_t pv, uint32_t mv) {
+    const uint32_t lo = (uint32_t)__builtin_popcount(pv & 0xFFFFu) -
+                        (uint32_t)__builtin_popcount(mv & 0xFFFFu);
+    const uint32_t hi = (uint32_t)__builtin_popcount(pv >> 16) -
+                        (uint32_t)__builtin_popcount(mv >> 16);
+    return as_pk((lo & 0xFFFFu) | (hi << 16));   // (D >= 0: neither half wraps)
+}
+
 // f * 32 as one v_lshl_add with the lane's row base (left to itself the compiler turns the
 // bit-field extract + scale into shift + mask + add: three VALU per column instead of two)
 __device__ __forceinline__ uint32_t lds_off32(uint32_t f, uint32_t base) {
     uint32_t r;
     asm("v_lshl_add_u32 %0, %1, 5, %2" : "=v"(r) : "v"(f), "v"(base));
     return r;
+}
+
+// Warm-up columns: a lane counts columns only from qlo on, and the first l
+// columns of its scan, plus up to 15 in front of the end-aligned chunk grid, never count.
+// DMX_SCREEN_BARE = G (16, 8 or 4) runs each group of G columns of the unrolled chunk in one of
+// three wave-uniform kinds: bare (no lane of the wave counts a column of the group: no cost
+// update, no minimum), counted (every lane counts every column: the plain minimum) or masked.
+// 0 keeps the two chunk-wide loops (A/B).  Measured (profiles/ab_screen_bare_near.txt, c2x24
+// 10 M reads, screen ms per step): 0: 8.92, 16: 8.32, 8: 8.13, 4: 8.16; 8 is the coarsest at
+// the best time.
+#ifndef DMX_SCREEN_BARE
+#define DMX_SCREEN_BARE 8
+#endif
+static_assert(DMX_SCREEN_BARE == 0 || DMX_SCREEN_BARE == 4 || DMX_SCREEN_BARE == 8 ||
+              DMX_SCREEN_BARE == 16, "DMX_SCREEN_BARE: 0, 4, 8 or 16");
+
+struct ScreenState {
+    uint32_t pv0, mv0, pv1, mv1;   // two adapters per dword
+    u16x2 d0, d1;                  // last-row costs (stale after a bare group)
+    u16x2 m0, m1;                  // the chunk's minima over counted columns
+};
+
+enum { kGroupBare = 0, kGroupCounted = 1, kGroupMasked = 2 };
+
+// columns C0 .. C0 + G - 1 of a chunk (lo / hi: their code-row nibbles, column index immediate)
+template <int C0, int G, int KIND>
+__device__ __forceinline__ void screen_cols(const char* qb, uint32_t lo, uint32_t hi, uint32_t q8,
+                                            int qlo, ScreenState& s) {
+#pragma unroll
+    for (int c = C0; c < C0 + G; ++c) {
+        const uint64_t e = *reinterpret_cast<const uint64_t*>(
+            qb + lds_off32(__builtin_amdgcn_ubfe(c < 8 ? lo : hi, 4 * (c & 7), 4), q8));
+        if constexpr (KIND == kGroupBare) {
+            myers_step_pk_bare((uint32_t)e, s.pv0, s.mv0);
+            myers_step_pk_bare((uint32_t)(e >> 32), s.pv1, s.mv1);
+        } else {
+            myers_step_pk((uint32_t)e, s.pv0, s.mv0, s.d0);
+            myers_step_pk((uint32_t)(e >> 32), s.pv1, s.mv1, s.d1);
+            if (KIND == kGroupCounted || c >= qlo) {
+                s.m0 = __builtin_elementwise_min(s.m0, s.d0);
+                s.m1 = __builtin_elementwise_min(s.m1, s.d1);
+            }
+        }
+    }
+}
+
+// One group, its kind chosen by two ballots over the lanes still scanning (they have run the
+// same chunks, so `stale` is the same for all of them); the costs come back from the deltas
+// before the first group that reads them.
+template <int C0, int G>
+__device__ __forceinline__ void screen_group(const char* qb, uint32_t lo, uint32_t hi, uint32_t q8,
+                                             int qlo, ScreenState& s, bool& stale) {
+    if (__builtin_amdgcn_ballot_w64(qlo < C0 + G) == 0) {
+        screen_cols<C0, G, kGroupBare>(qb, lo, hi, q8, qlo, s);
+        stale = true;
+        return;
+    }
+    if (stale) {
+        s.d0 = pk_cost_from_deltas(s.pv0, s.mv0);
+        s.d1 = pk_cost_from_deltas(s.pv1, s.mv1);
+        stale = false;
+    }
+    if (__builtin_amdgcn_ballot_w64(qlo > C0) == 0)
+        screen_cols<C0, G, kGroupCounted>(qb, lo, hi, q8, qlo, s);
+    else
+        screen_cols<C0, G, kGroupMasked>(qb, lo, hi, q8, qlo, s);
+}
+
+template <int G>
+__device__ __forceinline__ void screen_chunk(const char* qb, uint32_t lo, uint32_t hi, uint32_t q8,
+                                             int qlo, ScreenState& s, bool& stale) {
+    if constexpr (G == 16) {
+        screen_group<0, 16>(qb, lo, hi, q8, qlo, s, stale);
+    } else if constexpr (G == 8) {
+        screen_group<0, 8>(qb, lo, hi, q8, qlo, s, stale);
+        screen_group<8, 8>(qb, lo, hi, q8, qlo, s, stale);
+    } else {
+        screen_group<0, 4>(qb, lo, hi, q8, qlo, s, stale);
+        screen_group<4, 4>(qb, lo, hi, q8, qlo, s, stale);
+        screen_group<8, 4>(qb, lo, hi, q8, qlo, s, stale);
+        screen_group<12, 4>(qb, lo, hi, q8, qlo, s, stale);
+    }
 }
 
 // bit k of b (k < 8) -> bit 4k + 3 (the no-match bit of column k's nibble)
@@ -3082,6 +3186,9 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
                     pv1 = r2 | (r3 << 16);
                 }
                 u16x2 d0 = as_pk(lp[0]), d1 = as_pk(lp[1]);
+#if DMX_SCREEN_BARE
+                bool stale = false;                          // d0 / d1 behind a bare group
+#endif
                 TaskView tv;
                 tv.read = 0;
                 tv.n = w.n;
@@ -3113,6 +3220,14 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
                     }
                     uint32_t cm0 = 0xFFFFFFFFu, cm1 = 0xFFFFFFFFu;
                     u16x2 m0 = as_pk(cm0), m1 = as_pk(cm1);
+#if DMX_SCREEN_BARE
+                    {
+                        ScreenState ss{pv0, mv0, pv1, mv1, d0, d1, m0, m1};
+                        screen_chunk<DMX_SCREEN_BARE>(qb, lo, hi, q8, qlo, ss, stale);
+                        pv0 = ss.pv0, mv0 = ss.mv0, pv1 = ss.pv1, mv1 = ss.mv1;
+                        d0 = ss.d0, d1 = ss.d1, m0 = ss.m0, m1 = ss.m1;
+                    }
+#else
                     if (__builtin_amdgcn_ballot_w64(qlo > 0) == 0) {   // every column counts
 #pragma unroll
                         for (int c = 0; c < 16; ++c) {
@@ -3138,6 +3253,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
                             }
                         }
                     }
+#endif
                     cm0 = as_u32(m0);
                     cm1 = as_u32(m1);
 #pragma unroll
