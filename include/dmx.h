@@ -553,6 +553,54 @@ int dmx_hitgroups_host(const uint32_t* q, const uint32_t* t, const uint32_t* out
  * host between the rounds included).  Returns that run's hooking rounds. */
 int dmx_hitgroups_stats(dmx_ctx* ctx, float* ms, int n_ms);
 
+/* ---- Rows of masks against rows of masks ----------------------------------------
+ * The comparisons of iden_consensus() (amplicon_sorter.py:1140-1159) as the pair loops of
+ * comp_consensus_groups (:1276-1296) and compare_consensus (:1869-1889) run them: every consensus
+ * against every later one, edlib's HW mode, both strands.  Query and target are both rows of the
+ * call, laid out as dmx_rowdist's (row g is masks[row_off[g] .. row_off[g + 1]), n_rows + 1
+ * offsets, bits 5..7 refused); q[i] and t[i] are row indices.  Two columns are equal iff their
+ * masks intersect: literal equality for A/C/G/T/N, a gap column (0) equals nothing on either
+ * side, an IUPAC column equals each of its letters.
+ * dmx_rowpairdist: out[i] = the distance of row q[i] (query, rows of the matrix) against row
+ * t[i] (target, columns), mode DMX_PD_NW or DMX_PD_HW, against the target's reverse complement
+ * (the row backwards, bits A <-> T and C <-> G swapped, N and gap columns fixed) where flags[i]
+ * has DMX_PD_RC; min(d, caps[i] + 1) with caps.  flags and caps may be NULL.
+ * dmx_rowhits: per pair df = the forward distance and dr = the distance against the reversed
+ * target, both always computed; d = min(df, dr), rev = dr < df (ties are forward); a hit iff
+ * cap[i] >= 0 and d <= cap[i] (cap[i] = -1: never a hit; below -1 is DMX_E_INVALID).  The
+ * decision and the compaction (flag, prefix sum, scatter) run on the device and only the hits
+ * come back, ascending in their place in the pair list: pair[k], d[k], rev[k].  *n_hits is always
+ * set; with hits_cap below it nothing is written and the call is DMX_E_INVALID.
+ * Neither call needs or disturbs a resident batch: they work on a context that never saw
+ * dmx_load, and the outcomes of a previous dmx_load and dmx_pairhits stay valid.  Pairs may
+ * repeat and come in any order.  The rows some pair names are uploaded once per call; lists
+ * above DMX_PD_CHUNK pairs run as several launches with the same results.
+ * Everything is checked on the host before anything is launched, naming the pair or the row:
+ * DMX_E_INVALID for a null pointer with n_pairs > 0, a row index outside n_rows, decreasing
+ * offsets, a mask byte with bits 5..7 set, an unknown mode or flag; DMX_E_UNSUPPORTED for a named
+ * row of 0 or more than DMX_PD_MAX_LEN columns and for more than DMX_LG_MAX_PAIRS pairs.  A
+ * refused call launches nothing, leaves dmx_rowhits_ms at 0 and the context usable.
+ * Synchronous. */
+int dmx_rowpairdist(dmx_ctx* ctx, int mode, size_t n_rows, const uint8_t* masks,
+                    const uint64_t* row_off, const uint32_t* q, const uint32_t* t,
+                    const uint8_t* flags, const uint32_t* caps, size_t n_pairs, uint32_t* out);
+int dmx_rowhits(dmx_ctx* ctx, int mode, size_t n_rows, const uint8_t* masks,
+                const uint64_t* row_off, const uint32_t* q, const uint32_t* t, const int32_t* cap,
+                size_t n_pairs, uint32_t* pair, uint32_t* d, uint8_t* rev, size_t hits_cap,
+                size_t* n_hits);
+/* Host only (no GPU; tests, ctx=None of dmx.sorter.compare_consensuses): the same contracts by
+ * a plain full-matrix DP with the intersect equality (HW: row 0 is free, the result is the
+ * least of the last row); dmx_rowhits_host sits on dmx_rowpairdist_host.  Errors:
+ * dmx_last_error(NULL). */
+int dmx_rowpairdist_host(int mode, size_t n_rows, const uint8_t* masks, const uint64_t* row_off,
+                         const uint32_t* q, const uint32_t* t, const uint8_t* flags,
+                         const uint32_t* caps, size_t n_pairs, uint32_t* out, int n_threads);
+int dmx_rowhits_host(int mode, size_t n_rows, const uint8_t* masks, const uint64_t* row_off,
+                     const uint32_t* q, const uint32_t* t, const int32_t* cap, size_t n_pairs,
+                     uint32_t* pair, uint32_t* d, uint8_t* rev, size_t hits_cap, size_t* n_hits,
+                     int n_threads);
+float dmx_rowhits_ms(dmx_ctx* ctx);  /* device time of the last dmx_rowpairdist or dmx_rowhits */
+
 #ifdef __cplusplus
 }
 #endif

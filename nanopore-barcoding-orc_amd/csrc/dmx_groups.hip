@@ -511,6 +511,49 @@ int lg_hits_end(Ctx* c, const char* who, float forward_ms, uint32_t* best, uint6
     return DMX_OK;
 }
 
+int lg_compact_outcomes(Ctx* c, const char* who, const uint32_t* d_outc, size_t n_pairs,
+                        size_t hits_cap, uint32_t* pair, uint32_t* d, uint8_t* rev, size_t* n_hits,
+                        float* ms) {
+    *n_hits = 0;
+    *ms = 0.f;
+    if (!n_pairs) return DMX_OK;
+    if (const int rc = lg_state(c, who)) return rc;
+    LgState* s = c->lg;
+    hipStream_t st = c->stream;
+    const size_t room = std::min(hits_cap, n_pairs);   // the scatter writes no place at or past it
+    const uint32_t nb = lg_blocks(n_pairs);
+    LG_CK(who, s->blk.reserve((size_t)nb + 1));
+    LG_CK(who, s->sel_a.reserve(room));
+    LG_CK(who, s->sel_b.reserve(room));
+    LG_CK(who, s->sel_rev.reserve(room));
+    LgCompact A;
+    A.outc = d_outc, A.q = nullptr, A.t = nullptr, A.tie = nullptr;   // hits: the outcomes alone
+    A.n_pairs = (uint32_t)n_pairs, A.n_reads = 0;
+    A.blk = s->blk.p, A.out_a = s->sel_a.p, A.out_b = s->sel_b.p, A.out_rev = s->sel_rev.p;
+    A.out_cap = (uint32_t)room;
+    uint32_t total = 0;
+    LG_CK(who, hipEventRecord(s->ev[0], st));
+    hipLaunchKernelGGL(lg_count_kernel<false>, dim3(nb), dim3(kLgBlock), 0, st, A);
+    hipLaunchKernelGGL(lg_scan_kernel, dim3(1), dim3(kLgBlock), 0, st, s->blk.p, nb);
+    hipLaunchKernelGGL(lg_scatter_kernel<false>, dim3(nb), dim3(kLgBlock), 0, st, A);
+    LG_CK(who, hipGetLastError());
+    LG_CK(who, hipEventRecord(s->ev[1], st));
+    LG_CK(who, hipMemcpyAsync(&total, s->blk.p + nb, 4, hipMemcpyDeviceToHost, st));
+    LG_CK(who, hipStreamSynchronize(st));
+    hipEventElapsedTime(ms, s->ev[0], s->ev[1]);
+    *n_hits = total;
+    if (!total) return DMX_OK;
+    if (hits_cap < total || !pair || !d || !rev) {
+        c->err = std::string(who) + ": room for " + std::to_string(hits_cap) + " hits, " +
+                 std::to_string(total) + " to return";
+        return DMX_E_INVALID;
+    }
+    LG_CK(who, hipMemcpy(pair, s->sel_a.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    LG_CK(who, hipMemcpy(d, s->sel_b.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    LG_CK(who, hipMemcpy(rev, s->sel_rev.p, (size_t)total, hipMemcpyDeviceToHost));
+    return DMX_OK;
+}
+
 }  // namespace dmx
 
 // ---- the entry points (include/dmx.h) -----------------------------------------------------------

@@ -18,6 +18,7 @@ struct PdState;     // pairwise read distance (dmx_pairdist.hip)
 struct PaState;     // pairwise alignment with edit path (dmx_pairdist.hip)
 struct GaState;     // progressive alignment of read groups (dmx_pairdist.hip)
 struct RdState;     // read distance against rows of masks (dmx_pairdist.hip)
+struct RrState;     // distance between rows of masks, their hits (dmx_pairdist.hip)
 struct LgState;     // hits of dmx_pairhits, link groups (dmx_groups.hip)
 
 // A device buffer that grows on demand, never shrinks, and is freed with its owner.
@@ -173,6 +174,7 @@ struct Ctx {
     PaState* pa = nullptr;       // dmx_pairalign buffers, created by its first call
     GaState* ga = nullptr;       // dmx_groupalign buffers, created by its first call
     RdState* rd = nullptr;       // dmx_rowdist buffers, created by its first call
+    RrState* rr = nullptr;       // dmx_rowpairdist / dmx_rowhits buffers, created by the first call
     LgState* lg = nullptr;       // dmx_pairhits' outcomes and the link-group buffers
 
     // RCCL communicator for the per-bin count exchange (dmx_comm.cpp)
@@ -205,6 +207,14 @@ int lg_hits_begin(Ctx* c, const char* who, const uint32_t* q, const uint32_t* t,
 int lg_hits_decide(Ctx* c, const char* who, const uint32_t* d_dist, const uint32_t* orig, size_t np,
                    int pass, size_t lo, std::vector<uint32_t>* need);
 int lg_hits_end(Ctx* c, const char* who, float forward_ms, uint32_t* best, uint64_t* n_hits);
+// dmx_rowhits (dmx_pairdist.hip): the hit compaction (count, scan, scatter) over outcome words
+// d_outc[0 .. n_pairs) that are the caller's, not the last dmx_pairhits': that call's outcomes,
+// its pair list and the times of dmx_hitgroups_stats stay as they are (only the compaction's
+// scratch buffers are shared).  *n_hits is always set; with hits_cap below it nothing is written
+// and the call is DMX_E_INVALID.  *ms = the device time of the three kernels.  Synchronises.
+int lg_compact_outcomes(Ctx* c, const char* who, const uint32_t* d_outc, size_t n_pairs,
+                        size_t hits_cap, uint32_t* pair, uint32_t* d, uint8_t* rev, size_t* n_hits,
+                        float* ms);
 // Round `round` resolves its candidates with the band kernels (every adapter has kk <= 7 and
 // DMX_RESOLVE=ring is not set): its winner keys carry their origin (make_key_o), and nothing
 // reads or writes d_origin[round].

@@ -27,10 +27,18 @@
 // not yet in a group against every group's consensus) is the distance form against such rows:
 // NW, no trace, the rows given by the caller per call (rowdist_kernel).
 //
+// dmx_rowpairdist / dmx_rowhits (iden_consensus, :1140-1159, as the pair loops of
+// comp_consensus_groups and compare_consensus run it: every consensus against every later one, HW,
+// both strands) is the distance form with both sides rows of masks given per call
+// (rowpair_kernel): two columns are equal iff their masks intersect; NW or HW; a reversed target
+// is the row's reverse complement, which rowpair_rc_kernel writes beside the rows once per call.
+// dmx_rowhits decides the hits on the device (rowhits_decide_kernel) and compacts them with
+// dmx_groups.hip's kernels; only the hits come back.
+//
 // All forms share one forward pass (pd_forward: pairdist_kernel, pairalign_kernel,
 // groupalign_kernel, groupalign_strands_kernel (members taken reverse-complemented,
-// dmx_groupalign_strands) and rowdist_kernel are its instantiations, told apart at compile time by
-// their argument struct), one traceback (pa_traceback) and one host path: the chunk planner (pd_plan: chunk
+// dmx_groupalign_strands), rowdist_kernel and rowpair_kernel are its instantiations, told apart at
+// compile time by their argument struct), one traceback (pa_traceback) and one host path: the chunk planner (pd_plan: chunk
 // limits, sort, wave packing, pair records), the staging of a launch (pd_stage: buffers, upload,
 // the arguments every kernel takes) and the buffers themselves (PdBufs).  A change to the block
 // step, the stripes or the planner is made once.
@@ -81,6 +89,16 @@ struct RdPair : PdPair {
     uint32_t n;                  // the row's length
 };
 static_assert(sizeof(RdPair) == 40, "the row form uploads 40 bytes per pair");
+// dmx_rowpairdist's record: query and target are both rows of the call's mask array.  PdPair::q
+// and ::t are row indices; a pair flagged DMX_PD_RC has `row` in the reverse-complemented copy.
+struct RrPair : PdPair {
+    uint64_t row;                // first column of the target row in the device mask array
+    uint64_t qrow;               // first column of the query row
+    uint32_t n, m;               // their lengths
+    uint32_t dst;                // the pair's place in the call's list: where its distance goes
+    uint32_t pad;
+};
+static_assert(sizeof(RrPair) == 56, "the row-pair form uploads 56 bytes per pair");
 struct PdWave {
     uint32_t first, count, G, steps;   // pairs[first .. first + count), one group of G lanes each
 };
@@ -141,6 +159,18 @@ struct RdArgs : PdHead<RdPair> {
     uint32_t* out;               // per pair: the distance
 };
 
+// dmx_rowpairdist / dmx_rowhits: the distance form's arguments with the mode, and the call's rows
+// (forward copies, then the reverse complements where some pair asks for one).  out is indexed by
+// the pair's place in the call's list (RrPair::dst), not by its place in the launch: the
+// distances of every chunk stay on the device for the hit decision.
+struct RrArgs : PdHead<RrPair> {
+    const uint8_t* mask;         // per column: the mask, every row padded to 16 columns
+    uint64_t cols;               // columns of mask
+    int mode;
+    uint32_t out_n;              // entries of out
+    uint32_t* out;               // per pair of the list: the distance
+};
+
 // The buffers and events of either form; they go with the context (pd_release).
 template <class Pair>
 struct PdBufs {
@@ -183,15 +213,30 @@ struct RdState : PdBufs<RdPair> {
     float ms = 0.f;
 };
 
+// A row of dmx_rowpairdist on the device: where it starts in the mask array and its length.
+struct RrRow {
+    uint64_t off;
+    uint32_t n, pad;
+};
+struct RrState : PdBufs<RrPair> {   // DESIGN.md §8j; PdBufs::out holds the whole list's distances
+    DevBuf<uint8_t> mask;        // the rows of the last call, then their reverse complements
+    DevBuf<RrRow> rows;          // the uploaded rows (rowpair_rc_kernel)
+    DevBuf<uint32_t> outc;       // dmx_rowhits: per pair d | DMX_LG_REV, or DMX_LG_NONE
+    DevBuf<int32_t> cap;         // dmx_rowhits: the caller's caps
+    float ms = 0.f;
+};
+
 void pd_release(Ctx* c) {
     delete c->pd;
     delete c->pa;
     delete c->ga;
     delete c->rd;
+    delete c->rr;
     c->pd = nullptr;
     c->pa = nullptr;
     c->ga = nullptr;
     c->rd = nullptr;
+    c->rr = nullptr;
 }
 
 // The five match masks (A, C, G, T, N) of query rows 64 wi .. 64 wi + 63, built in registers
@@ -249,10 +294,46 @@ __device__ __forceinline__ void pd_masks(const Packed& pk, uint64_t qoff, uint32
     peq[4] = nb;
 }
 
+// pd_masks for a query that is itself a row of masks (RrArgs): peq[c] bit i = bit c of the mask
+// of query row 64 wi + i, so that Eq = OR of peq[c] over the target mask's bits says "the masks
+// intersect".  Four aligned 16-byte loads; a chunk is loaded only where it begins below the
+// query's end, and then lies inside the row's padding to 16 columns (zeros: they match nothing,
+// and `valid` clears them anyway).  Bit c of 4 mask bytes in a word is gathered into 4 adjacent
+// bits by one multiply: bit 8 k moves to 24 + k (0x01020408 = 2^24 + 2^17 + 2^10 + 2^3; the other
+// partial products land below bit 24 or leave the word, and no two meet, so nothing carries).
+__device__ __forceinline__ void pd_masks_row(const Bounds& bd, const uint8_t* mask, uint64_t cols,
+                                             uint64_t qrow, uint32_t m, uint32_t wi,
+                                             uint64_t (&peq)[5]) {
+    const uint32_t rows = min(64u, m - 64u * wi);
+    const uint64_t g0 = qrow + 64ull * wi;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) peq[c] = 0ull;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        const uint64_t ri = g0 + 16u * k;
+        if (16u * k < rows && ri + 16u <= cols &&
+            bchk(bd, (int64_t)ri + 15, 15, (int64_t)cols, kBufRrCols))
+            v = *reinterpret_cast<const uint4*>(mask + ri);
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j)
+#pragma unroll
+            for (uint32_t c = 0; c < 5u; ++c) {
+                const uint32_t nib = (((w4[j] >> c) & 0x01010101u) * 0x01020408u) >> 24;
+                peq[c] |= (uint64_t)(nib & 15u) << (16u * k + 4u * j);
+            }
+    }
+    const uint64_t valid = rows >= 64u ? ~0ull : ((1ull << rows) - 1ull);
+#pragma unroll
+    for (int c = 0; c < 5; ++c) peq[c] &= valid;
+}
+
 // Where a pair's target lies: a read of the batch, or a row of masks (dmx_groupalign's group
-// row, dmx_rowdist's given row).
+// row, dmx_rowdist's and dmx_rowpairdist's given row).
 template <class Pair>
-constexpr bool kPdRowPair = std::is_same<Pair, GaPair>::value || std::is_same<Pair, RdPair>::value;
+constexpr bool kPdRowPair = std::is_same<Pair, GaPair>::value || std::is_same<Pair, RdPair>::value ||
+                            std::is_same<Pair, RrPair>::value;
 template <class Pair>
 __device__ __forceinline__ bool pd_target_ok(const Bounds& bd, const Pair& P) {
     if constexpr (kPdRowPair<Pair>) return true;   // P.t is a group or a row, not a read
@@ -285,6 +366,11 @@ __device__ __forceinline__ uint64_t pd_target_off(const uint64_t* offs, const Pa
 // RdArgs, the distance against a row of masks (dmx_rowdist): the target and its fetch are
 // GaArgs's, the score handling PdArgs's in NW (there is no mode and no reversed target: the
 // caller gives a reversed row as a row of its own); out[k] = the distance, clamped by the cap.
+// RrArgs, the distance between two rows of masks (dmx_rowpairdist, dmx_rowhits): the target and
+// its fetch are RdArgs's, the query's peq comes from pd_masks_row, the mode and the score
+// handling are PdArgs's (NW or HW); the record carries both lengths and both rows, so nothing of
+// the resident batch is read, and a reversed target is a row of its own in the mask array;
+// out[P.dst] = the distance, clamped by the cap.
 // Every branch on the form is `if constexpr`: an instantiation holds no instruction of another.
 // That is a constraint, not a style: pairdist_kernel and pairalign_kernel are sensitive to where
 // their loop lands in the code, so a new form must leave their instructions as
@@ -292,10 +378,11 @@ __device__ __forceinline__ uint64_t pd_target_off(const uint64_t* offs, const Pa
 template <class Args>
 __device__ __forceinline__ void pd_forward(const Args& A) {
     constexpr bool kRd = std::is_same<Args, RdArgs>::value;
+    constexpr bool kRr = std::is_same<Args, RrArgs>::value;
     constexpr bool kGa = std::is_base_of<GaArgs, Args>::value;   // GaArgs or GaStrandArgs
-    constexpr bool kRow = kGa || kRd;
+    constexpr bool kRow = kGa || kRd || kRr;
     constexpr bool kTrace = std::is_same<Args, PaArgs>::value || kGa;
-    constexpr uint32_t kColsBuf = kRd ? kBufRdCols : kBufGaCols;
+    constexpr uint32_t kColsBuf = kRr ? kBufRrCols : kRd ? kBufRdCols : kBufGaCols;
     const uint32_t wave = blockIdx.x * kPdWavesPerBlock + (threadIdx.x >> 6);
     if (wave >= A.n_waves) return;   // whole waves leave: the shift below sees full waves
     const uint32_t lane = threadIdx.x & 63u;
@@ -306,11 +393,20 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
     bool nw = true;
     if constexpr (!kTrace && !kRd) nw = A.mode == DMX_PD_NW;
 
-    uint32_t m = 1, n = 1, rc = 0, cap = 0, has_cap = 0;
+    uint32_t m = 1, n = 1, rc = 0, cap = 0, has_cap = 0, dst = 0;
     uint64_t qoff = 0, toff = 0, soff = 0, trace = 0;
     if (active) {
         const auto P = A.pairs[W.first + g];
-        if (DMX_BOUND(A.pk.bd, reads, P.q, kBufRead) && pd_target_ok(A.pk.bd, P)) {
+        if constexpr (kRr) {   // both sides are rows: the record has all of it
+            m = P.m;
+            n = P.n;
+            qoff = P.qrow;
+            toff = P.row;
+            soff = P.soff;
+            has_cap = P.flags & 0x100u;
+            cap = P.cap;
+            dst = P.dst;
+        } else if (DMX_BOUND(A.pk.bd, reads, P.q, kBufRead) && pd_target_ok(A.pk.bd, P)) {
             m = A.lens[P.q];
             n = pd_target_len(A.lens, P);
             qoff = A.offs[P.q];
@@ -346,7 +442,11 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
             wi = s * G + w;
             live = wi < mw;
             last = wi + 1u == mw;
-            if (live) pd_masks<std::is_same<Args, GaStrandArgs>::value>(A.pk, qoff, m, wi, rc, peq);
+            if constexpr (kRr) {
+                if (live) pd_masks_row(A.pk.bd, A.mask, A.cols, qoff, m, wi, peq);
+            } else {
+                if (live) pd_masks<std::is_same<Args, GaStrandArgs>::value>(A.pk, qoff, m, wi, rc, peq);
+            }
             Pv = ~0ull;
             Mv = 0ull;
             // the word's last row: the query's in its last word, so no padded row is ever read
@@ -435,7 +535,11 @@ __device__ __forceinline__ void pd_forward(const Args& A) {
                     } else {
                         uint32_t d = (uint32_t)(nw ? score : best);
                         if (has_cap && d > cap) d = cap + 1u;
-                        A.out[W.first + g] = d;
+                        if constexpr (kRr) {
+                            if (dst < A.out_n) A.out[dst] = d;
+                        } else {
+                            A.out[W.first + g] = d;
+                        }
                     }
                 }
             } else {
@@ -451,6 +555,59 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void groupalign_kernel(GaArg
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void rowdist_kernel(RdArgs A) { pd_forward(A); }
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void groupalign_strands_kernel(GaStrandArgs A) {
     pd_forward(A);
+}
+__global__ __launch_bounds__(64 * kPdWavesPerBlock) void rowpair_kernel(RrArgs A) { pd_forward(A); }
+
+// The reverse complement of every uploaded row, written `half` columns after the row itself (the
+// second half of the mask array, padded as the first): column i of the copy is the complement
+// (A <-> T, C <-> G; N and a gap column stay) of column n - 1 - i.  One block per row; the padding
+// up to 16 columns is written as zeros.
+constexpr uint32_t kRrRcBlock = 256;
+struct RrRcArgs {
+    Bounds bd;
+    const RrRow* rows;
+    uint32_t n_rows;
+    uint8_t* mask;
+    uint64_t half, cols;
+};
+__global__ __launch_bounds__(kRrRcBlock) void rowpair_rc_kernel(RrRcArgs A) {
+    if (blockIdx.x >= A.n_rows) return;
+    const RrRow R = A.rows[blockIdx.x];
+    const uint32_t padded = (R.n + 15u) & ~15u;
+    for (uint32_t i = threadIdx.x; i < padded; i += kRrRcBlock) {
+        uint32_t v = 0;
+        if (i < R.n) {
+            const uint64_t src = R.off + (R.n - 1u - i);
+            if (src < A.half && bchk(A.bd, (int64_t)src, 0, (int64_t)A.cols, kBufRrCols)) {
+                const uint32_t x = A.mask[src];
+                v = (x & 16u) | ((x & 1u) << 3) | ((x & 2u) << 1) | ((x & 4u) >> 1) | ((x & 8u) >> 3);
+            }
+        }
+        const uint64_t dst = A.half + R.off + i;
+        if (dst < A.cols && bchk(A.bd, (int64_t)dst, 0, (int64_t)A.cols, kBufRrCols))
+            A.mask[dst] = (uint8_t)v;
+    }
+}
+
+// dmx_rowhits' decision on the distances of the whole list: pair i's forward distance is
+// dist[2 i], the one against the reversed target dist[2 i + 1] (both clamped at max(cap, 0) + 1,
+// which keeps the minimum, the comparison with the cap and, among hits, the strand as the exact
+// distances give them).  Ties are forward.  The outcome word is dmx_pairhits': d, d | DMX_LG_REV
+// or DMX_LG_NONE, so the hit compaction of dmx_groups.hip takes it as it is.
+struct RrDecide {
+    const uint32_t* dist;
+    const int32_t* cap;
+    uint32_t n_pairs;
+    uint32_t* outc;
+};
+__global__ __launch_bounds__(kRrRcBlock) void rowhits_decide_kernel(RrDecide A) {
+    const uint32_t i = blockIdx.x * kRrRcBlock + threadIdx.x;
+    if (i >= A.n_pairs) return;
+    const uint32_t df = A.dist[2ull * i], dr = A.dist[2ull * i + 1ull];
+    const bool rev = dr < df;
+    const uint32_t d = rev ? dr : df;
+    const int32_t cap = A.cap[i];
+    A.outc[i] = (cap >= 0 && d <= (uint32_t)cap) ? (d | (rev ? DMX_LG_REV : 0u)) : DMX_LG_NONE;
 }
 
 // dmx_pairalign's traceback: one lane per pair walks back from (m, n), preferring up (INSERT),
@@ -720,12 +877,13 @@ uint32_t pd_dp(int mode, const std::vector<uint8_t>& a, const std::vector<uint8_
 
 // The whole (m + 1) x (n + 1) matrix of query a against target b; returns D(m, n).
 // eq(x, y): does query symbol x equal target entry y (a symbol, or a row's mask)?
+// mode DMX_PD_HW (dmx_rowpairdist_host): row 0 is free and the result is the least of row m.
 template <class Eq>
 uint32_t pa_dp_matrix(const std::vector<uint8_t>& a, const std::vector<uint8_t>& b,
-                      std::vector<uint16_t>& D, Eq eq) {
+                      std::vector<uint16_t>& D, Eq eq, int mode = DMX_PD_NW) {
     const size_t m = a.size(), n = b.size(), W = n + 1;
     D.resize((m + 1) * W);
-    for (size_t j = 0; j <= n; ++j) D[j] = (uint16_t)j;
+    for (size_t j = 0; j <= n; ++j) D[j] = mode == DMX_PD_NW ? (uint16_t)j : (uint16_t)0;
     for (size_t i = 1; i <= m; ++i) {
         uint16_t* row = &D[i * W];
         const uint16_t* up = row - W;
@@ -736,6 +894,7 @@ uint32_t pa_dp_matrix(const std::vector<uint8_t>& a, const std::vector<uint8_t>&
             row[j] = (uint16_t)std::min<uint32_t>(sub, std::min<uint32_t>(up[j], row[j - 1]) + 1u);
         }
     }
+    if (mode != DMX_PD_NW) return *std::min_element(D.begin() + m * W, D.begin() + (m + 1) * W);
     return D[m * W + n];
 }
 
@@ -1837,4 +1996,342 @@ extern "C" int dmx_rowdist(dmx_ctx* c, size_t n_rows, const uint8_t* masks, cons
     }
     s->ms = total_ms;
     return DMX_OK;
+}
+
+// ---- dmx_rowpairdist, dmx_rowhits: rows of masks against rows of masks ----------
+
+namespace {
+
+// Every argument check of the four entry points, naming the pair or the row; rowlen[g] becomes
+// the length of row g.  0, or the code with *err set.
+int rr_validate(const char* who, int mode, size_t n_rows, const uint8_t* masks,
+                const uint64_t* row_off, const uint32_t* q, const uint32_t* t, const uint8_t* flags,
+                size_t n_pairs, std::vector<uint32_t>& rowlen, std::string* err) {
+    const std::string name = std::string(who) + ": ";
+    if (mode != DMX_PD_NW && mode != DMX_PD_HW) {
+        *err = name + "mode must be DMX_PD_NW or DMX_PD_HW";
+        return DMX_E_INVALID;
+    }
+    if (!n_pairs) return DMX_OK;
+    if (n_pairs > DMX_LG_MAX_PAIRS) {
+        *err = name + "at most " + std::to_string(DMX_LG_MAX_PAIRS) + " pairs supported";
+        return DMX_E_UNSUPPORTED;
+    }
+    rowlen.assign(n_rows, 0);
+    for (size_t g = 0; g < n_rows; ++g) {
+        if (row_off[g + 1] < row_off[g]) {
+            *err = name + "row " + std::to_string(g) + ": offsets must not decrease";
+            return DMX_E_INVALID;
+        }
+        for (uint64_t x = row_off[g]; x < row_off[g + 1]; ++x)
+            if (masks[x] & 0xE0u) {
+                *err = name + "row " + std::to_string(g) + ": column " +
+                       std::to_string(x - row_off[g]) + " has a mask bit above the five symbols";
+                return DMX_E_INVALID;
+            }
+        // a length above the limit is refused below, for the pairs that name the row
+        rowlen[g] = (uint32_t)std::min<uint64_t>(row_off[g + 1] - row_off[g], DMX_PD_MAX_LEN + 1u);
+    }
+    for (size_t i = 0; i < n_pairs; ++i) {
+        if (q[i] >= n_rows || t[i] >= n_rows) {
+            *err = name + "pair " + std::to_string(i) + " names a row outside the " +
+                   std::to_string(n_rows) + " given";
+            return DMX_E_INVALID;
+        }
+        if (flags && (flags[i] & ~DMX_PD_RC)) {
+            *err = name + "pair " + std::to_string(i) + " has an unknown flag";
+            return DMX_E_INVALID;
+        }
+    }
+    for (size_t i = 0; i < n_pairs; ++i)
+        for (const uint32_t g : {q[i], t[i]})
+            if (rowlen[g] < 1 || rowlen[g] > DMX_PD_MAX_LEN) {
+                *err = name + "pair " + std::to_string(i) + ": row " + std::to_string(g) + " has " +
+                       std::to_string(row_off[g + 1] - row_off[g]) + " columns (1.." +
+                       std::to_string(DMX_PD_MAX_LEN) + " supported)";
+                return DMX_E_UNSUPPORTED;
+            }
+    return DMX_OK;
+}
+
+// dmx_rowhits' caps: -1 = never a hit, below that refused.
+int rr_validate_caps(const char* who, const int32_t* cap, size_t n_pairs, std::string* err) {
+    for (size_t i = 0; i < n_pairs; ++i)
+        if (cap[i] < -1) {
+            *err = std::string(who) + ": pair " + std::to_string(i) +
+                   ": a cap is a distance, or -1 for none";
+            return DMX_E_INVALID;
+        }
+    return DMX_OK;
+}
+
+// A row's reverse complement (lib.mask_rc; rowpair_rc_kernel on the device).
+void rr_mask_rc(const uint8_t* row, size_t n, std::vector<uint8_t>& out) {
+    out.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t x = row[n - 1 - i];
+        out[i] = (uint8_t)((x & 16u) | ((x & 1u) << 3) | ((x & 2u) << 1) | ((x & 4u) >> 1) |
+                           ((x & 8u) >> 3));
+    }
+}
+
+// The distances of a validated list on the device, into the state's `out` in list order:
+// the rows some pair names closed up, padded to 16 columns and uploaded once; their reverse
+// complements written beside them when a pair is flagged; then dmx_pairdist's chunked launches.
+// *ms = the device time of the kernels.
+int rr_run(Ctx* c, const char* who, int mode, size_t n_rows, const uint8_t* masks,
+           const uint64_t* row_off, const std::vector<uint32_t>& rowlen, const uint32_t* q,
+           const uint32_t* t, const uint8_t* flags, const uint32_t* caps, size_t n_pairs,
+           float* ms_total) {
+    PD_CK(who, hipSetDevice(c->device));
+    if (const int rc = pd_state(c, who, c->rr)) return rc;
+    RrState* s = c->rr;
+    hipStream_t st = c->stream;
+    const size_t chunk = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+
+    std::vector<uint64_t> goff(n_rows, ~(uint64_t)0);
+    std::vector<RrRow> used;
+    std::vector<uint32_t> tn(n_pairs);
+    uint64_t total = 0;
+    bool any_rc = false;
+    for (size_t i = 0; i < n_pairs; ++i) {
+        for (const uint32_t g : {q[i], t[i]})
+            if (goff[g] == ~(uint64_t)0) {
+                goff[g] = total;
+                used.push_back(RrRow{total, rowlen[g], 0u});
+                total += ((uint64_t)rowlen[g] + 15u) & ~(uint64_t)15u;
+            }
+        tn[i] = rowlen[t[i]];
+        any_rc = any_rc || (flags && (flags[i] & DMX_PD_RC));
+    }
+    std::vector<uint8_t> rows(total, 0);
+    for (size_t g = 0; g < n_rows; ++g)
+        if (goff[g] != ~(uint64_t)0) std::memcpy(rows.data() + goff[g], masks + row_off[g], rowlen[g]);
+    PD_CK(who, s->mask.reserve(2 * total));
+    PD_CK(who, s->out.reserve(n_pairs));
+    PD_CK(who, hipMemcpyAsync(s->mask.p, rows.data(), total, hipMemcpyHostToDevice, st));
+    float ms_sum = 0.f;
+    if (any_rc) {
+        PD_CK(who, s->rows.reserve(used.size()));
+        PD_CK(who, hipMemcpyAsync(s->rows.p, used.data(), used.size() * sizeof(RrRow),
+                                  hipMemcpyHostToDevice, st));
+        PD_CK(who, bounds_reset(c, st));
+        RrRcArgs R;
+        R.bd = make_bounds(c, kKerRowpairRc);
+        R.rows = s->rows.p;
+        R.n_rows = (uint32_t)used.size();
+        R.mask = s->mask.p;
+        R.half = total;
+        R.cols = 2 * total;
+        PD_CK(who, hipEventRecord(s->ev[0], st));
+        hipLaunchKernelGGL(rowpair_rc_kernel, dim3(R.n_rows), dim3(kRrRcBlock), 0, st, R);
+        PD_CK(who, hipGetLastError());
+        PD_CK(who, hipEventRecord(s->ev[1], st));
+    }
+    PD_CK(who, hipStreamSynchronize(st));   // `rows` and `used` are pageable
+    if (any_rc) {
+        if (const int brc = bounds_check(c, who)) return brc;
+        hipEventElapsedTime(&ms_sum, s->ev[0], s->ev[1]);
+    }
+
+    PdPlan<RrPair> pl;
+    for (size_t lo = 0; lo < n_pairs;) {
+        const size_t hi = pd_plan(pl, rowlen.data(), q, t, flags, caps, n_pairs, lo, chunk,
+                                  kPdNoBudget, tn.data());
+        for (size_t k = 0; k < pl.pairs.size(); ++k) {
+            RrPair& P = pl.pairs[k];
+            P.row = goff[P.t] + ((P.flags & DMX_PD_RC) ? total : 0u);
+            P.qrow = goff[P.q];
+            P.m = rowlen[P.q];
+            P.dst = (uint32_t)(lo + pl.place(k));
+            P.pad = 0;
+        }
+        RrArgs A;
+        // out_words = the whole list: the buffer is not reallocated between the chunks
+        if (const int rc = pd_stage(c, who, *s, pl, n_pairs, kKerRowpair, A)) return rc;
+        A.mask = s->mask.p;
+        A.cols = any_rc ? 2 * total : total;
+        A.mode = mode;
+        A.out_n = (uint32_t)n_pairs;
+        A.out = s->out.p;
+        PD_CK(who, hipEventRecord(s->ev[0], st));
+        pd_launch_forward(rowpair_kernel, A, st);
+        PD_CK(who, hipGetLastError());
+        PD_CK(who, hipEventRecord(s->ev[1], st));
+        PD_CK(who, hipStreamSynchronize(st));   // the plan's pair records are pageable
+        if (const int brc = bounds_check(c, who)) return brc;
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+        ms_sum += ms;
+        lo = hi;
+    }
+    *ms_total = ms_sum;
+    return DMX_OK;
+}
+
+}  // namespace
+
+extern "C" float dmx_rowhits_ms(dmx_ctx* c) { return c && c->rr ? c->rr->ms : 0.f; }
+
+extern "C" int dmx_rowpairdist_host(int mode, size_t n_rows, const uint8_t* masks,
+                                    const uint64_t* row_off, const uint32_t* q, const uint32_t* t,
+                                    const uint8_t* flags, const uint32_t* caps, size_t n_pairs,
+                                    uint32_t* out, int n_threads) {
+    const char* const who = "dmx_rowpairdist_host";
+    if (n_pairs && (!q || !t || !out || !masks || !row_off)) {
+        set_process_error(std::string(who) + ": null argument");
+        return DMX_E_INVALID;
+    }
+    std::string err;
+    std::vector<uint32_t> rowlen;
+    if (const int rc = rr_validate(who, mode, n_rows, masks, row_off, q, t, flags, n_pairs, rowlen,
+                                   &err)) {
+        set_process_error(err);
+        return rc;
+    }
+    pd_parallel(n_pairs, n_threads, [&](size_t k, size_t nth) {
+        std::vector<uint8_t> a, b;
+        std::vector<uint16_t> D;
+        for (size_t i = k; i < n_pairs; i += nth) {
+            a.assign(masks + row_off[q[i]], masks + row_off[q[i] + 1]);
+            if (flags && (flags[i] & DMX_PD_RC))
+                rr_mask_rc(masks + row_off[t[i]], rowlen[t[i]], b);
+            else
+                b.assign(masks + row_off[t[i]], masks + row_off[t[i] + 1]);
+            uint32_t d = pa_dp_matrix(a, b, D, [](uint8_t x, uint8_t y) { return (x & y) != 0; },
+                                      mode);
+            if (caps && d > caps[i]) d = caps[i] + 1u;
+            out[i] = d;
+        }
+    });
+    return DMX_OK;
+}
+
+extern "C" int dmx_rowhits_host(int mode, size_t n_rows, const uint8_t* masks,
+                                const uint64_t* row_off, const uint32_t* q, const uint32_t* t,
+                                const int32_t* cap, size_t n_pairs, uint32_t* pair, uint32_t* d,
+                                uint8_t* rev, size_t hits_cap, size_t* n_hits, int n_threads) {
+    const char* const who = "dmx_rowhits_host";
+    if (!n_hits || (n_pairs && (!q || !t || !cap || !masks || !row_off))) {
+        set_process_error(std::string(who) + ": null argument");
+        return DMX_E_INVALID;
+    }
+    *n_hits = 0;
+    std::string err;
+    std::vector<uint32_t> rowlen;
+    int rc = rr_validate(who, mode, n_rows, masks, row_off, q, t, nullptr, n_pairs, rowlen, &err);
+    if (!rc) rc = rr_validate_caps(who, cap, n_pairs, &err);
+    if (rc) {
+        set_process_error(err);
+        return rc;
+    }
+    std::vector<uint32_t> df(n_pairs), dr(n_pairs);
+    const std::vector<uint8_t> rflags(n_pairs, DMX_PD_RC);
+    if ((rc = dmx_rowpairdist_host(mode, n_rows, masks, row_off, q, t, nullptr, nullptr, n_pairs,
+                                   df.data(), n_threads)))
+        return rc;
+    if ((rc = dmx_rowpairdist_host(mode, n_rows, masks, row_off, q, t, rflags.data(), nullptr,
+                                   n_pairs, dr.data(), n_threads)))
+        return rc;
+    size_t hits = 0;
+    for (size_t i = 0; i < n_pairs; ++i)
+        hits += cap[i] >= 0 && std::min(df[i], dr[i]) <= (uint32_t)cap[i];
+    *n_hits = hits;
+    if (!hits) return DMX_OK;
+    if (hits_cap < hits || !pair || !d || !rev) {
+        set_process_error(std::string(who) + ": room for " + std::to_string(hits_cap) + " hits, " +
+                          std::to_string(hits) + " to return");
+        return DMX_E_INVALID;
+    }
+    size_t k = 0;
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const uint32_t best = std::min(df[i], dr[i]);
+        if (cap[i] < 0 || best > (uint32_t)cap[i]) continue;
+        pair[k] = (uint32_t)i;
+        d[k] = best;
+        rev[k] = dr[i] < df[i] ? 1 : 0;   // ties are forward
+        ++k;
+    }
+    return DMX_OK;
+}
+
+extern "C" int dmx_rowpairdist(dmx_ctx* c, int mode, size_t n_rows, const uint8_t* masks,
+                               const uint64_t* row_off, const uint32_t* q, const uint32_t* t,
+                               const uint8_t* flags, const uint32_t* caps, size_t n_pairs,
+                               uint32_t* out) {
+    const char* const who = "dmx_rowpairdist";
+    if (!c) return DMX_E_INVALID;
+    if (c->rr) c->rr->ms = 0.f;
+    if (n_pairs && (!q || !t || !out || !masks || !row_off)) {
+        c->err = "dmx_rowpairdist: null rows, pair list or output";
+        return DMX_E_INVALID;
+    }
+    std::vector<uint32_t> rowlen;
+    if (const int rc = rr_validate(who, mode, n_rows, masks, row_off, q, t, flags, n_pairs, rowlen,
+                                   &c->err))
+        return rc;
+    if (!n_pairs) return DMX_OK;
+    float ms = 0.f;
+    if (const int rc = rr_run(c, who, mode, n_rows, masks, row_off, rowlen, q, t, flags, caps,
+                              n_pairs, &ms))
+        return rc;
+    PD_CK(who, hipMemcpy(out, c->rr->out.p, n_pairs * 4, hipMemcpyDeviceToHost));
+    c->rr->ms = ms;
+    return DMX_OK;
+}
+
+extern "C" int dmx_rowhits(dmx_ctx* c, int mode, size_t n_rows, const uint8_t* masks,
+                           const uint64_t* row_off, const uint32_t* q, const uint32_t* t,
+                           const int32_t* cap, size_t n_pairs, uint32_t* pair, uint32_t* d,
+                           uint8_t* rev, size_t hits_cap, size_t* n_hits) {
+    const char* const who = "dmx_rowhits";
+    if (!c) return DMX_E_INVALID;
+    if (c->rr) c->rr->ms = 0.f;
+    if (!n_hits || (n_pairs && (!q || !t || !cap || !masks || !row_off))) {
+        c->err = "dmx_rowhits: null rows, pair list, caps or count";
+        return DMX_E_INVALID;
+    }
+    *n_hits = 0;
+    std::vector<uint32_t> rowlen;
+    if (const int rc = rr_validate(who, mode, n_rows, masks, row_off, q, t, nullptr, n_pairs,
+                                   rowlen, &c->err))
+        return rc;
+    if (const int rc = rr_validate_caps(who, cap, n_pairs, &c->err)) return rc;
+    if (!n_pairs) return DMX_OK;
+    // the list the launches run: pair i forward at 2 i, against the reversed target at 2 i + 1
+    std::vector<uint32_t> q2(2 * n_pairs), t2(2 * n_pairs), cap2(2 * n_pairs);
+    std::vector<uint8_t> f2(2 * n_pairs);
+    for (size_t i = 0; i < n_pairs; ++i) {
+        q2[2 * i] = q2[2 * i + 1] = q[i];
+        t2[2 * i] = t2[2 * i + 1] = t[i];
+        cap2[2 * i] = cap2[2 * i + 1] = (uint32_t)std::max(cap[i], 0);
+        f2[2 * i] = 0;
+        f2[2 * i + 1] = DMX_PD_RC;
+    }
+    float ms = 0.f, ms_decide = 0.f, ms_compact = 0.f;
+    if (const int rc = rr_run(c, who, mode, n_rows, masks, row_off, rowlen, q2.data(), t2.data(),
+                              f2.data(), cap2.data(), 2 * n_pairs, &ms))
+        return rc;
+    RrState* s = c->rr;
+    hipStream_t st = c->stream;
+    PD_CK(who, s->outc.reserve(n_pairs));
+    PD_CK(who, s->cap.reserve(n_pairs));
+    PD_CK(who, hipMemcpyAsync(s->cap.p, cap, n_pairs * 4, hipMemcpyHostToDevice, st));
+    RrDecide D;
+    D.dist = s->out.p;
+    D.cap = s->cap.p;
+    D.n_pairs = (uint32_t)n_pairs;
+    D.outc = s->outc.p;
+    PD_CK(who, hipEventRecord(s->ev[0], st));
+    hipLaunchKernelGGL(rowhits_decide_kernel,
+                       dim3((uint32_t)((n_pairs + kRrRcBlock - 1) / kRrRcBlock)), dim3(kRrRcBlock),
+                       0, st, D);
+    PD_CK(who, hipGetLastError());
+    PD_CK(who, hipEventRecord(s->ev[1], st));
+    PD_CK(who, hipStreamSynchronize(st));   // `cap` is pageable
+    hipEventElapsedTime(&ms_decide, s->ev[0], s->ev[1]);
+    const int rc = lg_compact_outcomes(c, who, s->outc.p, n_pairs, hits_cap, pair, d, rev, n_hits,
+                                       &ms_compact);
+    if (rc == DMX_OK || rc == DMX_E_INVALID) s->ms = ms + ms_decide + ms_compact;
+    return rc;
 }

@@ -46,7 +46,8 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_groupalign_strands", "dmx_groupalign_strands_host",
            "dmx_rowdist", "dmx_rowdist_host", "dmx_edgegroups", "dmx_edgegroups_host",
            "dmx_pairhits", "dmx_pairhits_fetch", "dmx_hitgroups", "dmx_pairhits_host",
-           "dmx_hitgroups_host", "dmx_hitgroups_stats"]
+           "dmx_hitgroups_host", "dmx_hitgroups_stats", "dmx_rowpairdist", "dmx_rowpairdist_host",
+           "dmx_rowhits", "dmx_rowhits_host"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -191,6 +192,15 @@ def load() -> ctypes.CDLL:
                                         ctypes.POINTER(ctypes.c_uint64), c_int]
         L.dmx_hitgroups_host.argtypes = [P, P, P, c_size, P, c_size, P]
         L.dmx_hitgroups_stats.argtypes = [P, ctypes.POINTER(ctypes.c_float), c_int]
+    if hasattr(L, "dmx_rowpairdist"):
+        rr = [c_int, c_size, P, c_u64p, P, P]   # mode, n_rows, masks, row_off, q, t
+        L.dmx_rowpairdist.argtypes = [P] + rr + [P, P, c_size, P]
+        L.dmx_rowpairdist_host.argtypes = rr + [P, P, c_size, P, c_int]
+        hits = [P, c_size, P, P, P, c_size, ctypes.POINTER(c_size)]
+        L.dmx_rowhits.argtypes = [P] + rr + hits
+        L.dmx_rowhits_host.argtypes = rr + hits + [c_int]
+        L.dmx_rowhits_ms.argtypes = [P]
+        L.dmx_rowhits_ms.restype = ctypes.c_float
     # DMX_ALLOW_ABI=1: load an older in-tree build for a regression A/B (tools/replay_sweep.py)
     if L.dmx_abi_version() != ABI_VERSION and os.environ.get("DMX_ALLOW_ABI") != "1":
         raise DmxError("libdmx ABI mismatch")
@@ -515,6 +525,43 @@ class Context:
     def rowdist_ms(self) -> float:
         """Device time (ms) of the last rowdist call."""
         return float(self._L.dmx_rowdist_ms(self._h))
+
+    # ---- rows of masks against rows of masks (include/dmx.h dmx_rowpairdist; DESIGN.md §8j) -----
+    def rowpairdist(self, rows, q, t, mode: int, flags=None, caps=None) -> np.ndarray:
+        """Edit distance of rows[q[i]] (query) against rows[t[i]] (target), PD_NW or PD_HW; rows
+        as rowdist's (str / bytes over A/C/G/T/N/-/IUPAC, or uint8 masks), two columns equal iff
+        their masks intersect.  flags: PD_RC per pair (the target's reverse complement, mask_rc);
+        caps: out[i] = min(d, caps[i] + 1).  Needs no resident batch and leaves one alone.
+        Returns uint32."""
+        masks, off, qa, ta, fa, ca = _rowpair_args(rows, q, t, flags, caps)
+        out = np.zeros(len(qa), dtype=np.uint32)
+        self._check(self._L.dmx_rowpairdist(self._h, int(mode), len(off) - 1, masks.ctypes.data,
+                                            off.ctypes.data, qa.ctypes.data, ta.ctypes.data,
+                                            fa.ctypes.data if fa is not None else None,
+                                            ca.ctypes.data if ca is not None else None, len(qa),
+                                            out.ctypes.data), "dmx_rowpairdist")
+        return out
+
+    def rowhits(self, rows, q, t, cap, mode: int = PD_HW):
+        """Per pair the distance on both strands of the target, d = the smaller (ties are
+        forward), a hit iff cap[i] >= 0 and d <= cap[i] (cap: int32, -1 = never); decided and
+        compacted on the device.  Returns the hits in ascending place in the pair list: (pair
+        uint32, d uint32, rev uint8)."""
+        masks, off, qa, ta, _, _ = _rowpair_args(rows, q, t, None, None)
+        ha = _rowhits_cap(cap, qa)
+        n = ctypes.c_size_t(0)
+        room = len(qa)
+        pair, d = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
+        rev = np.zeros(room, dtype=np.uint8)
+        self._check(self._L.dmx_rowhits(self._h, int(mode), len(off) - 1, masks.ctypes.data,
+                                        off.ctypes.data, qa.ctypes.data, ta.ctypes.data,
+                                        ha.ctypes.data, len(qa), pair.ctypes.data, d.ctypes.data,
+                                        rev.ctypes.data, room, ctypes.byref(n)), "dmx_rowhits")
+        return pair[:n.value], d[:n.value], rev[:n.value]
+
+    def rowhits_ms(self) -> float:
+        """Device time (ms) of the last rowpairdist or rowhits call."""
+        return float(self._L.dmx_rowhits_ms(self._h))
 
     # ---- gene groups (include/dmx.h dmx_edgegroups .. dmx_hitgroups; DESIGN.md §8i) -------------
     def edgegroups(self, a, b, n_nodes: int) -> np.ndarray:
@@ -858,6 +905,60 @@ def rowdist_host(p: "Packed", rows, q, r, caps=None, n_threads: int = 1) -> np.n
         msg = L.dmx_last_error(None)
         raise DmxError(f"dmx_rowdist_host failed ({rc}): {msg.decode() if msg else ''}")
     return out
+
+
+def _rowpair_args(rows, q, t, flags, caps):
+    """(masks, row_off, q, t, flags, caps) of dmx_rowpairdist(_host) / dmx_rowhits(_host)."""
+    masks, off, qa, ta, ca = _rowdist_args(rows, q, t, caps)
+    fa = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+    if fa is not None and fa.shape != qa.shape:
+        raise DmxError("rowpairdist: flags must have one entry per pair")
+    return masks, off, qa, ta, fa, ca
+
+
+def _rowhits_cap(cap, qa):
+    ha = np.ascontiguousarray(cap, dtype=np.int32)
+    if ha.shape != qa.shape:
+        raise DmxError("rowhits: cap must have one entry per pair")
+    return ha
+
+
+def rowpairdist_host(rows, q, t, mode: int, flags=None, caps=None,
+                     n_threads: int = 1) -> np.ndarray:
+    """dmx_rowpairdist's contract on the host, by a plain full-matrix DP with the intersect
+    equality (no GPU): the checker of the kernel."""
+    L = load()
+    masks, off, qa, ta, fa, ca = _rowpair_args(rows, q, t, flags, caps)
+    out = np.zeros(len(qa), dtype=np.uint32)
+    rc = L.dmx_rowpairdist_host(int(mode), len(off) - 1, masks.ctypes.data, off.ctypes.data,
+                                qa.ctypes.data, ta.ctypes.data,
+                                fa.ctypes.data if fa is not None else None,
+                                ca.ctypes.data if ca is not None else None, len(qa),
+                                out.ctypes.data, int(n_threads))
+    if rc < 0:
+        msg = L.dmx_last_error(None)
+        raise DmxError(f"dmx_rowpairdist_host failed ({rc}): {msg.decode() if msg else ''}")
+    return out
+
+
+def rowhits_host(rows, q, t, cap, mode: int = PD_HW, n_threads: int = 1):
+    """dmx_rowhits' contract on the host (no GPU), on rowpairdist_host: (pair, d, rev) as
+    Context.rowhits."""
+    L = load()
+    masks, off, qa, ta, _, _ = _rowpair_args(rows, q, t, None, None)
+    ha = _rowhits_cap(cap, qa)
+    n = ctypes.c_size_t(0)
+    room = len(qa)
+    pair, d = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint32)
+    rev = np.zeros(room, dtype=np.uint8)
+    rc = L.dmx_rowhits_host(int(mode), len(off) - 1, masks.ctypes.data, off.ctypes.data,
+                            qa.ctypes.data, ta.ctypes.data, ha.ctypes.data, len(qa),
+                            pair.ctypes.data, d.ctypes.data, rev.ctypes.data, room,
+                            ctypes.byref(n), int(n_threads))
+    if rc < 0:
+        msg = L.dmx_last_error(None)
+        raise DmxError(f"dmx_rowhits_host failed ({rc}): {msg.decode() if msg else ''}")
+    return pair[:n.value], d[:n.value], rev[:n.value]
 
 
 def _edge_arrays(a, b):

@@ -5,10 +5,12 @@ identity lines, restated from scripts/auxiliary_code/amplicon_sorter.py (:550-62
 
 similarity() stops at the similarity lines (`i:j:iden`, `i:j:iden:reverse`); gene_groups() goes
 on to what update_list (:983-1034) and merge_groups (:1058-1087) make of them, the gene groups,
-on dmx_pairhits / dmx_hitgroups, without forming the lines.  NOT replaced:
-comp_consensus_groups (:1206, which samples 50 reads of a group at random) and everything after
-it, the species groups (SSG / Estimate) and the .group files.  The random selection modes
-(-ra, -a) are out of scope.  Alphabet: A, C, G, T, N (a read with any other byte is refused;
+on dmx_pairhits / dmx_hitgroups, without forming the lines.
+comp_consensus_groups() and compare_consensus() restate the two merge loops (:1231-1334,
+:1857-1958) on dmx_rowhits (consensus against consensus, HW, both strands), with
+the first reads of a group in index order where the reference samples at random.  NOT replaced:
+that random sampling, finetune, the species groups (SSG / Estimate) and the .group files.  The
+random selection modes (-ra, -a) are out of scope.  Alphabet: A, C, G, T, N (a read with any other byte is refused;
 the reference would compare such bytes literally).
 
 consensus() restates create_consensus (:358-428) for many groups at once on top of
@@ -485,6 +487,144 @@ def assign(ctx, reads, unassigned, consensuses, similar: float, n_threads: int =
     return lines, best, [b for b in best if b[2] >= similar]
 
 
+def compare_consensuses(ctx, consensuses, length_diff: float = 8.0, threshold: float = 0.60,
+                        n_threads: int = 16) -> list:
+    """The pair loop of comp_consensus_groups / compare_consensus (:1276-1296, :1869-1889) with
+    iden_consensus (:1140-1159) on dmx_rowhits: the lines (y, z, iden) of the
+    consensus pairs whose larger identity over both strands is >= threshold, in pair-generation
+    order (y-major, z ascending; the reference's order is its workers' interleaving).
+    consensuses: A/C/G/T/N strings or bytes, or uint8 mask rows (lib.mask_row: gap and IUPAC
+    columns allowed; two columns are equal iff their masks intersect).
+    Pairs: y < z, dropped where len(A1) * ldc < len(A2) or len(A2) * ldc < len(A1) with
+    ldc = length_diff / 100 + 1 in double arithmetic.  The query is the shorter consensus (y's
+    on equal lengths), the target the longer; HW; the other strand is the target's reverse
+    complement (the reference turns z's consensus, which gives the same distance).
+    iden = round(1 - d / len(longer), 3) with d the smaller distance, decided as
+    d <= identity_cap(len(longer), threshold).  ctx: a Context, or None for lib.rowhits_host."""
+    rows = [np.ascontiguousarray(c, dtype=np.uint8).reshape(-1) if isinstance(c, np.ndarray)
+            else lib.mask_row(_clean([c], "consensus")[0]) for c in consensuses]
+    ln = np.array([len(r) for r in rows], dtype=np.int64)
+    if len(ln) and (int(ln.min()) < 1 or int(ln.max()) > lib.PD_MAX_LEN):
+        raise DmxError(f"compare_consensuses: consensuses of 1..{lib.PD_MAX_LEN} columns")
+    n = len(rows)
+    if n < 2:
+        return []
+    ldc = length_diff / 100 + 1
+    y, z = np.triu_indices(n, 1)               # y-major, z ascending
+    la, lb = ln[y].astype(np.float64), ln[z].astype(np.float64)
+    keep = ~((la * ldc < lb) | (lb * ldc < la))
+    y, z = y[keep], z[keep]
+    if not len(y):
+        return []
+    swap = ln[y] > ln[z]                       # the query is the shorter, y's on equal lengths
+    q, t = np.where(swap, z, y), np.where(swap, y, z)
+    lt = ln[t]
+    caps = {int(L): identity_cap(int(L), threshold) for L in np.unique(lt)}
+    cap = np.array([caps[int(L)] for L in lt], dtype=np.int32)
+    if ctx is not None:
+        pair, d, _ = ctx.rowhits(rows, q, t, cap, lib.PD_HW)
+    else:
+        pair, d, _ = lib.rowhits_host(rows, q, t, cap, lib.PD_HW, n_threads=n_threads)
+    return [(int(y[k]), int(z[k]), identity(int(dk), int(lt[k]))) for k, dk in zip(pair, d)]
+
+
+def merge_by_consensus(groups, consensuses, lines, threshold: float) -> list:
+    """What comp_consensus_groups (:1305-1330) and compare_consensus (:1898-1914) make of the
+    lines, then merge_groups (:1058-1087), restated literally.  Group k is the set of its read
+    tokens (the decimal strings of groups[k]) plus its consensus string.  Per line (y, z, iden)
+    with iden >= threshold, in the order given: y is followed while its set has exactly one
+    element (that element is a pointer "=k"); S[y] |= S[z]; S[z] = {"=y"}.  z is not followed:
+    a z that is already a pointer hands its pointer token to y (the reference does the same, and
+    the two groups then meet through that token in the merge below).  Then the sets of at most
+    one element are dropped and sets that share any element (a read, a pointer token, an equal
+    consensus string) are merged, pass after pass in the reference's double loop, until a pass
+    merges nothing; a surviving group stands at its earliest position.  Only the read indices
+    are kept.  Returns ascending int64 index arrays.  A group without reads is a ValueError.
+    The result depends on the order of the lines where the reference's does: ours is
+    pair-generation order, the reference's the interleaving of its workers."""
+    if len(groups) != len(consensuses):
+        raise ValueError("merge_by_consensus: one consensus per group")
+    sets = []
+    for k, (g, c) in enumerate(zip(groups, consensuses)):
+        g = np.asarray(g, dtype=np.int64).reshape(-1)
+        if not len(g):
+            raise ValueError(f"merge_by_consensus: group {k} has no reads")
+        c = c.decode("ascii") if isinstance(c, (bytes, bytearray)) else str(c)
+        sets.append({str(int(x)) for x in g} | {c})
+    for y, z, iden in lines:
+        if not float(iden) >= threshold:
+            continue
+        y, z = int(y), int(z)
+        while len(sets[y]) == 1:
+            y = int(next(iter(sets[y])).replace("=", ""))
+        sets[y].update(sets[z])
+        sets[z] = {"=" + str(y)}
+    sets = [s for s in sets if len(s) > 1]
+    a1, a2 = len(sets) + 1, len(sets)
+    while a1 > a2:
+        a1 = len(sets)
+        for i in range(len(sets) - 1):
+            for j in range(i + 1, len(sets)):
+                if not sets[i].isdisjoint(sets[j]):
+                    sets[i] = sets[i] | sets[j]
+                    sets[j].clear()
+        sets = [s for s in sets if s]
+        a2 = len(sets)
+    return [np.array(sorted(int(x) for x in s if x.isdigit()), dtype=np.int64) for s in sets]
+
+
+def _group_consensuses(ctx, reads, groups, sample, n_threads):
+    """make_consensus of every group's first `sample` reads in index order."""
+    return [c for c in make_consensus(ctx, reads, [np.sort(np.asarray(g, dtype=np.int64))[:sample]
+                                                   for g in groups], n_threads=n_threads)]
+
+
+def comp_consensus_groups(ctx, reads, groups, length_diff: float = 8.0, sample: int = 50,
+                          min_reads: int = 6, n_threads: int = 16) -> list:
+    """The merge loop of comp_consensus_groups (:1231-1334): while the number of groups falls,
+    a consensus per group (make_consensus of its first `sample` reads in index order; the
+    reference samples that many at random, the difference documented for --consensus),
+    compare_consensuses at 0.60, and merge_by_consensus with threshold 0.80 when
+    length_diff / 100 + 1 > 1.08 and 0.60 otherwise.  Then the groups with at least min_reads
+    reads are kept (:1334).  groups: index arrays into reads.  ctx: a Context, or None for the
+    host twins.  Returns ascending index arrays."""
+    groups = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+    ldc = length_diff / 100 + 1
+    a1, a2 = len(groups), 0
+    while a1 > a2:
+        a1 = len(groups)
+        if not a1:
+            break
+        cons = _group_consensuses(ctx, reads, groups, sample, n_threads)
+        lines = compare_consensuses(ctx, cons, length_diff, 0.60, n_threads)
+        groups = merge_by_consensus(groups, cons, lines, 0.80 if ldc > 1.08 else 0.60)
+        a2 = len(groups)
+    return [g for g in groups if len(g) >= min_reads]
+
+
+def compare_consensus(ctx, reads, groups, consensuses, similar_consensus: float = 96.0,
+                      length_diff: float = 8.0, sample: int = 200, n_threads: int = 16):
+    """The loop of compare_consensus (:1857-1958): at most 3 cycles, while the number of groups
+    falls; a cycle compares the consensuses (lines at 0.60), merges at similar_consensus / 100
+    and makes fresh consensuses of every group's first `sample` reads in index order (random in
+    the reference).  Returns (groups, consensuses)."""
+    groups = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+    cons = [c.decode("ascii") if isinstance(c, (bytes, bytearray)) else str(c)
+            for c in consensuses]
+    if len(groups) != len(cons):
+        raise ValueError("compare_consensus: one consensus per group")
+    if len(groups) > 1:
+        a1, a2, b = len(groups), 0, 0
+        while a1 > a2 and b < 3:
+            a1 = len(groups)
+            lines = compare_consensuses(ctx, cons, length_diff, 0.60, n_threads)
+            groups = merge_by_consensus(groups, cons, lines, similar_consensus / 100)
+            cons = _group_consensuses(ctx, reads, groups, sample, n_threads)
+            a2 = len(groups)
+            b += 1
+    return groups, cons
+
+
 def _clean(reads, what: str = "read") -> list:
     out = []
     for i, r in enumerate(reads):
@@ -631,9 +771,11 @@ def main(argv=None) -> int:
         prog="dmx-similarity",
         description="The similarity pass of amplicon_sorter.py (pairwise identities of one "
                     "bin's reads) on the GPU, and with --groups the gene groups of its best "
-                    "hits, and with --consensus a consensus per gene group; "
-                    "comp_consensus_groups' sampling and merge loop and everything after stay "
-                    "with the reference.")
+                    "hits, with --consensus a consensus per gene group, and with "
+                    "--merged-groups the groups after comp_consensus_groups' merge loop "
+                    "(consensuses compared on the GPU, dmx_rowhits); the random sampling, "
+                    "finetune, the species groups and the .group files stay with the "
+                    "reference.")
     ap.add_argument("-i", "--input", required=True, help="bin in FASTQ/FASTA, optionally .gz")
     ap.add_argument("-o", "--output", default=None,
                     help="similarity lines (i:j:iden[:reverse]); optional with --groups")
@@ -648,6 +790,15 @@ def main(argv=None) -> int:
     ap.add_argument("--consensus-reads", type=int, default=50, metavar="N",
                     help="reads per group that make its consensus (default 50, the reference's "
                          "sample size)")
+    ap.add_argument("--merged-groups", default=None, metavar="FILE",
+                    help="with --groups: the groups after comp_consensus_groups' merge loop "
+                         "(consensus of the first --consensus-reads reads of every group, "
+                         "consensuses compared in HW mode on both strands, groups merged, "
+                         "repeated while their number falls; groups of fewer than 6 reads "
+                         "dropped), one per line like --groups")
+    ap.add_argument("-ldc", "--length_diff_consensus", type=float, default=8.0,
+                    help="length difference (%%) allowed between two compared consensuses "
+                         "(default 8.0)")
     ap.add_argument("-min", "--minlength", type=int, default=300)
     ap.add_argument("-max", "--maxlength", type=int, default=None)
     ap.add_argument("-maxr", "--maxreads", type=int, default=10000)
@@ -659,6 +810,8 @@ def main(argv=None) -> int:
         ap.error("the following arguments are required: -o/--output")
     if a.consensus is not None and a.groups is None:
         ap.error("--consensus needs --groups")
+    if a.merged_groups is not None and a.groups is None:
+        ap.error("--merged-groups needs --groups")
     if a.consensus_reads < 2:
         ap.error("--consensus-reads must be at least 2")
     try:
@@ -685,6 +838,15 @@ def main(argv=None) -> int:
                         f.write("".join(f">group_{k}({len(g)})\n{c}\n"
                                         for k, (g, c) in enumerate(zip(groups, cons))))
                     print(f"dmx-similarity: {len(cons)} consensus sequences -> {a.consensus}",
+                          file=sys.stderr)
+                if a.merged_groups is not None:
+                    kept = [reads[i] for i in usable([len(s) for s in reads], a.minlength,
+                                                     a.maxlength)]
+                    merged = comp_consensus_groups(ctx, kept, groups, a.length_diff_consensus,
+                                                   sample=a.consensus_reads)
+                    with open(a.merged_groups, "w") as f:
+                        f.write("".join(" ".join(str(int(x)) for x in g) + "\n" for g in merged))
+                    print(f"dmx-similarity: {len(merged)} merged groups -> {a.merged_groups}",
                           file=sys.stderr)
     except (DmxError, OSError, ValueError) as e:
         print(f"dmx-similarity: {e}", file=sys.stderr)
