@@ -92,6 +92,17 @@ int dmx_set_mode(dmx_ctx* ctx, int mode);
 int dmx_panel_pieces(const char* const* seqs, const int* lens, int n_adapters, double max_errors,
                      int min_overlap, int flags, int32_t* out, int n_out, uint64_t* entries,
                      int cap);
+/* Host only (no GPU; tests): the lookup tables of that piece screen as the kernels hold them.
+ * pair[4096]: row r (a 6-nt core, 12 bits) has bit a set iff the 8-mer r << 4 | a is sampled and
+ * bit 16 + b iff the 8-mer b << 12 | r is, so 20 bits K of codes answer the 8-mers at nt 0 and
+ * nt 2 from row K[4:16].  rank_base[1024]: low-half bits set in the rows before row 4 i; the key
+ * index of a sampled 8-mer k is rank_base[k >> 6] + the low-half bits of rows (k >> 4 & ~3) ..
+ * (k >> 4) - 1 + the bits below k & 15 of row k >> 4.  keys (up to cap, may be NULL): key i =
+ * first entry | count << 16 into dmx_panel_pieces' entries, by increasing 8-mer (out[2] keys).
+ * All zero when the screen is off. */
+int dmx_panel_piece_pairs(const char* const* seqs, const int* lens, int n_adapters,
+                          double max_errors, int min_overlap, int flags, uint32_t* pair,
+                          uint16_t* rank_base, uint32_t* keys, int cap);
 /* Host only (no GPU; tests): how far the kernels' gathers reach around a read view for the
  * panel dmx_set_panel (wheres == NULL) or dmx_set_panel_mixed (wheres, flags & DMX_RC) would
  * build from these arguments, in nt: out[0] before view position 0 as the kernels' warm-up

@@ -523,15 +523,12 @@ static void build_pieces(const Ctx* c, const char* const* seqs, const int* lens,
     for (size_t e = 0; e < ents.size(); ++e) {
         if (e == 0 || ents[e].first != ents[e - 1].first) {
             Q.key[nk++] = (uint32_t)e;
-            Q.bitmap[ents[e].first >> 5] |= 1u << (ents[e].first & 31);
+            piece_pair_add(Q.pair, ents[e].first);
         }
         Q.key[nk - 1] += 1u << 16;
         Q.entry[e] = ents[e].second;
     }
-    for (int w = 0, r = 0; w < kPieceBitmapWords; ++w) {
-        Q.rank_base[w] = (uint16_t)r;
-        r += __builtin_popcount(Q.bitmap[w]);
-    }
+    piece_rank_fill(Q);
     int reach = 0;   // FRONT: alignments entering at column 0 (rows skipped) end before it
     if (hp.ad[0].where == kFront)
         for (int a = 0; a < n; ++a)
@@ -948,6 +945,26 @@ int dmx_panel_pieces(const char* const* seqs, const int* lens, int n, double max
     for (int i = 0; i < 8; ++i) out[i] = v[i];
     if (entries)
         for (int e = 0; e < Q.n_entries && e < cap; ++e) entries[e] = Q.entry[e];
+    return DMX_OK;
+}
+
+int dmx_panel_piece_pairs(const char* const* seqs, const int* lens, int n, double max_errors,
+                          int min_overlap, int flags, uint32_t* pair, uint16_t* rank_base,
+                          uint32_t* keys, int cap) {
+    if (!pair || !rank_base) return DMX_E_INVALID;
+    Ctx tmp;   // never opened, as in dmx_panel_pieces
+    const char* np = std::getenv("DMX_NO_PIECES");
+    tmp.no_pieces = np && np[0] == '1';
+    HostPanel hp;
+    DevPanel dp;
+    const int rc = build_panel(&tmp, seqs, lens, nullptr, n, max_errors, min_overlap, flags, hp,
+                               dp);
+    if (rc != DMX_OK) return rc;
+    const DevPieces& Q = hp.pieces;
+    for (int r = 0; r < kPiecePairWords; ++r) pair[r] = Q.pair[r];
+    for (int r = 0; r < kPieceRankWords; ++r) rank_base[r] = Q.rank_base[r];
+    if (keys)
+        for (int k = 0; k < Q.n_keys && k < cap; ++k) keys[k] = Q.key[k];
     return DMX_OK;
 }
 

@@ -131,8 +131,17 @@ enum ShardList { kShWin = 0, kShWin2 = 2, kShTasks = 4, kShCand = 6, kShFtask = 
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxPieces = 1024;         // distinct (piece, orientation) records
 constexpr int kMaxPieceEntries = 2048;   // (sampled 8-mer, piece, offset) entries
-constexpr int kPieceK = 8;               // sampled k-mer length (a 64 Ki-bit LDS bitmap)
-constexpr int kPieceBitmapWords = 1 << (2 * kPieceK - 5);
+constexpr int kPieceK = 8;               // sampled k-mer length (a 64 Ki-bit set of 8-mers)
+// The set of sampled 8-mers as a pair table: 4096 rows, one per 6-nt core r (12 bits).  The low
+// half of a row holds the 8-mers that END with the core, by their 2 leading nt a (8-mer r << 4 | a,
+// bit a), the high half those that START with it, by their 2 trailing nt b (8-mer b << 12 | r,
+// bit 16 + b).  Two sampled 8-mers 2 nt apart share their core, so the 20 bits K of codes from the
+// first one's start answer both from row K[4:16]: bit K[0:4] and bit 16 + K[16:20].  Both halves
+// index the same set: 8-mer k is sampled iff bit k & 15 of pair[k >> 4] iff bit 16 + (k >> 12) of
+// pair[k & 0xFFF].
+constexpr int kPiecePairWords = 1 << (2 * kPieceK - 4);
+constexpr int kPieceRankRows = 4;        // rows per rank base (one aligned 16-byte LDS read)
+constexpr int kPieceRankWords = kPiecePairWords / kPieceRankRows;
 
 // An entry of the piece table (one per (piece, sampled offset)), packed in 64 bits: the piece's
 // 2-bit codes in view-0 read order (nt i at bits 2i; orientation 1: the reverse complement),
@@ -156,13 +165,28 @@ struct DevPieces {
     int32_t lo_off;        // min over orientation-0 pieces of len + dlo - 1 (>= 0)
     int32_t dlo_min;       // min over orientation-1 pieces of dlo
     int32_t pad[3];
-    // the LDS image (pscreen_kernel copies it whole): bitmap, rank base, keys, entries
-    uint32_t bitmap[kPieceBitmapWords];       // bit K: some entry samples the 8-mer K
-    uint16_t rank_base[kPieceBitmapWords];    // set bits before each word: 8-mer -> key index
+    // the LDS image (pscreen_kernel copies it whole): pair table, rank base, keys, entries
+    uint32_t pair[kPiecePairWords];           // the sampled 8-mers (above)
+    uint16_t rank_base[kPieceRankWords];      // low-half bits set before row 4 i: 8-mer -> key index
     uint32_t key[kMaxPieceEntries];           // key r (increasing 8-mer): first entry | count << 16
     uint64_t entry[kMaxPieceEntries];         // piece_entry(), grouped by key
 };
-constexpr int kPieceLdsFixed = kPieceBitmapWords * 6;   // bitmap + rank base, bytes
+constexpr int kPieceLdsFixed = kPiecePairWords * 4 + kPieceRankWords * 2;   // pair + rank, bytes
+// the largest image (every key and entry slot used) and a scan block's own LDS fit one block
+static_assert(kPieceLdsFixed + 12 * kMaxPieceEntries + 12 * 1024 <= 64 * 1024, "piece LDS image");
+
+// Host: add the sampled 8-mer k to a pair table; then, once, the rank bases.  The keys are numbered
+// by increasing 8-mer, which is row-major order of the low halves.
+inline void piece_pair_add(uint32_t* pair, uint32_t k) {
+    pair[k >> 4] |= 1u << (k & 15u);
+    pair[k & 0xFFFu] |= 1u << (16u + (k >> 12));
+}
+inline void piece_rank_fill(DevPieces& Q) {
+    for (int r = 0, n = 0; r < kPiecePairWords; ++r) {
+        if (r % kPieceRankRows == 0) Q.rank_base[r / kPieceRankRows] = (uint16_t)n;
+        n += __builtin_popcount(Q.pair[r] & 0xFFFFu);
+    }
+}
 
 // One filter task of the piece screen: view positions [p0, p0 + span) of (item, o); columns
 // p0 + hoff + 1 .. are reported (the positions before are the restricted-start warm-up); fresh:

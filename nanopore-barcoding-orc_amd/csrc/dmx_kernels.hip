@@ -1657,7 +1657,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
 // ---------------------------------------------------------------------------------------------
 // Piece screen: one lane per (item, part) of the item's orientation-0 view.  The
 // lane samples an 8-mer every S positions of the part's codes (view order) and looks it up in an
-// LDS bitmap of the panel's sampled piece 8-mers (both orientations: a piece of orientation 1 is
+// LDS table of the panel's sampled piece 8-mers (both orientations: a piece of orientation 1 is
 // stored reverse complemented, so one pass over the read serves both views).  A hit is checked
 // against every (piece, offset) entry of its 8-mer on the codes held in registers; an exact copy
 // marks the 16-position cells of the view where an alignment containing it can end.  Runs of
@@ -1675,6 +1675,15 @@ constexpr uint32_t kPieceGrid = DMX_PIECE_GRID;   // resident blocks (persistent
 #define DMX_SCAN_GRID (256 * 8)
 #endif
 constexpr uint32_t kScanGrid = DMX_SCAN_GRID;     // the flat scan: 8 waves per SIMD
+// The flat scan's own block: the 18 KB pair table and rank base, the keys and the entries are
+// shared by 8 waves, so four blocks (about 34 KB each with the M13 tables) keep 8 waves per SIMD
+// inside the CU's 160 KiB; at 256 threads the same image would leave 5 blocks, 5 waves per SIMD.
+#ifndef DMX_PSCAN_BLOCK
+#define DMX_PSCAN_BLOCK 512
+#endif
+constexpr int kPScanBlock = DMX_PSCAN_BLOCK;
+static_assert(kPScanBlock % 64 == 0 && kPScanBlock >= 64 && kPScanBlock <= 1024, "scan block");
+constexpr uint32_t kPScanGrid = kScanGrid * kScanBlock / kPScanBlock;   // the same waves
 
 __device__ __forceinline__ uint32_t ps_view_len(const RoundArgs& R, uint32_t item) {
     if (R.items) {
@@ -1819,10 +1828,10 @@ __device__ __forceinline__ void ps_lastcol(const RoundArgs& R, Window* wbuf, uin
     }
 }
 
-// The panel's piece tables -> LDS (dynamic: the fixed bitmap + rank base, then the keys and
+// The panel's piece tables -> LDS (dynamic: the fixed pair table + rank base, then the keys and
 // entries); returns the entry array.
 struct PsTables {
-    uint32_t* bm;
+    uint32_t* pr;
     uint16_t* rk;
     uint32_t* key;
     uint64_t* ent;
@@ -1830,28 +1839,59 @@ struct PsTables {
 __device__ __forceinline__ PsTables ps_load_tables(const DevPieces* Q, uint8_t* dyn) {
     PsTables t;
     const int nk = Q->n_keys, ne = Q->n_entries;
-    t.bm = reinterpret_cast<uint32_t*>(dyn);
-    t.rk = reinterpret_cast<uint16_t*>(dyn + 4 * kPieceBitmapWords);
+    t.pr = reinterpret_cast<uint32_t*>(dyn);
+    t.rk = reinterpret_cast<uint16_t*>(dyn + 4 * kPiecePairWords);
     t.key = reinterpret_cast<uint32_t*>(dyn + kPieceLdsFixed);
     t.ent = reinterpret_cast<uint64_t*>(dyn + kPieceLdsFixed + 8 * ((nk + 1) / 2));
-    for (int x = threadIdx.x; x < kPieceBitmapWords; x += blockDim.x) {
-        t.bm[x] = Q->bitmap[x];
-        t.rk[x] = Q->rank_base[x];
-    }
+    for (int x = threadIdx.x; x < kPiecePairWords; x += blockDim.x) t.pr[x] = Q->pair[x];
+    for (int x = threadIdx.x; x < kPieceRankWords; x += blockDim.x) t.rk[x] = Q->rank_base[x];
     for (int x = threadIdx.x; x < nk; x += blockDim.x) t.key[x] = Q->key[x];
     for (int x = threadIdx.x; x < ne; x += blockDim.x) t.ent[x] = Q->entry[x];
     return t;
 }
-// The entries of 8-mer K (which the bitmap holds): [first, first + count) of t.ent
+// The entries of 8-mer K (which the table holds): [first, first + count) of t.ent.  The key index
+// is the number of smaller sampled 8-mers: the rank base of the row's group of four, the low halves
+// of the group's rows before the row (one 16-byte read) and the row's bits below K & 15.  Runs once
+// per hit, not per sample.
 __device__ __forceinline__ uint32_t ps_key(const PsTables& t, uint32_t K) {
-    const uint32_t wi = K >> 5;
-    const uint32_t rank = (uint32_t)t.rk[wi] + (uint32_t)__popc(t.bm[wi] & ((1u << (K & 31u)) - 1u));
+    static_assert(kPieceRankRows == 4, "one uint4 per rank group");
+    const uint32_t r = K >> 4, j = r & 3u;
+    const uint4 g = reinterpret_cast<const uint4*>(t.pr)[r >> 2];
+    const uint32_t below = (1u << (K & 15u)) - 1u;
+    const uint32_t rank = (uint32_t)t.rk[r >> 2] +
+                          (uint32_t)__popc(g.x & (j > 0u ? 0xFFFFu : below)) +
+                          (uint32_t)__popc(g.y & (j > 1u ? 0xFFFFu : j == 1u ? below : 0u)) +
+                          (uint32_t)__popc(g.z & (j > 2u ? 0xFFFFu : j == 2u ? below : 0u)) +
+                          (uint32_t)__popc(g.w & (j == 3u ? below : 0u));
     return t.key[rank];
 }
-// 8-mer lookups of one 64-position step: w0..w5 = positions [C - 16, C + 80), samples C + qS
+// Both halves of a pair-table row shifted right, each by its own count: the low half by s[0:4],
+// the high half by s[16:20] (one v_pk_lshrrev_b16).  With s = the codes K of a pair of samples,
+// bit 0 is the first sample's hit and bit 16 the second's.
+__device__ __forceinline__ uint32_t ps_row_bits(uint32_t row, uint32_t s) {
+    uint32_t r;   // the instruction reads 4 bits of each count; plain C++ would mask them first
+    asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(r) : "v"(s), "v"(row));
+    return r;
+}
+// Bits 0..15 of x to the even bits, bits 16..31 to the odd ones (an outer perfect shuffle).
+__device__ __forceinline__ uint32_t ps_interleave(uint32_t x) {
+    uint32_t t;
+    t = (x ^ (x >> 8)) & 0x0000FF00u, x ^= t ^ (t << 8);
+    t = (x ^ (x >> 4)) & 0x00F000F0u, x ^= t ^ (t << 4);
+    t = (x ^ (x >> 2)) & 0x0C0C0C0Cu, x ^= t ^ (t << 2);
+    t = (x ^ (x >> 1)) & 0x22222222u, x ^= t ^ (t << 1);
+    return x;
+}
+// 8-mer lookups of one 64-position step: w0..w5 = positions [C - 16, C + 80), samples C + qS;
+// bit q of the result = sample q.  Two samples 2 nt apart take ONE LDS read (dmx_device.h, the
+// pair table): the codes K from the first one's start pick row K[4:16], and ps_row_bits brings
+// both hits to bits 0 and 16.  Pair p's two bits go to bits p and 16 + p of an accumulator, which
+// is interleaved once per step.  S = 2: samples 2p and 2p + 1.  S = 1: samples 4g + j and
+// 4g + j + 2, one accumulator per j.  S = 4: neighbours share 4 nt only; one read per sample, from
+// the low half.
 template <int S>
 __device__ __forceinline__ typename std::conditional<S == 1, uint64_t, uint32_t>::type
-ps_lookups(const uint32_t* bm, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4,
+ps_lookups(const uint32_t* pr, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4,
            uint32_t w5) {
     using HitT = typename std::conditional<S == 1, uint64_t, uint32_t>::type;
     HitT hits = 0;
@@ -1859,12 +1899,36 @@ ps_lookups(const uint32_t* bm, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w
     asm volatile("" ::"v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(w4), "v"(w5));
 #else
     const uint32_t wv6[6] = {w0, w1, w2, w3, w4, w5};
+    const auto row = [&](int u, uint32_t& K) __attribute__((always_inline)) {
+        K = align32(wv6[(u >> 4) + 1], wv6[u >> 4], 2u * (u & 15));
+        return pr[(K >> 4) & (uint32_t)(kPiecePairWords - 1)];
+    };
+    if constexpr (S == 4) {
 #pragma unroll
-    for (int q = 0; q < 64 / S; ++q) {
-        const int u = q * S + 16;
-        const uint32_t K = align32(wv6[(u >> 4) + 1], wv6[u >> 4], 2u * (u & 15));
-        const uint32_t word = bm[(K >> 5) & (uint32_t)(kPieceBitmapWords - 1)];
-        hits |= (HitT)__builtin_amdgcn_ubfe(word, K & 31u, 1) << q;
+        for (int q = 0; q < 16; ++q) {
+            uint32_t K;
+            const uint32_t word = row(4 * q + 16, K);
+            hits |= __builtin_amdgcn_ubfe(word, K & 15u, 1) << q;
+        }
+    } else {
+        uint32_t acc[2] = {0u, 0u};
+#pragma unroll
+        for (int p = 0; p < 16; ++p) {
+#pragma unroll
+            for (int j = 0; j < 2 / S; ++j) {
+                uint32_t K;
+                const uint32_t word = row(4 * p + j + 16, K);
+                acc[j] |= (ps_row_bits(word, K) & 0x00010001u) << p;
+            }
+        }
+        if constexpr (S == 2) {
+            hits = ps_interleave(acc[0]);
+        } else {   // bit i of acc[j] interleaved = sample 2i + j: interleave the two once more
+            const uint32_t e0 = ps_interleave(acc[0]), e1 = ps_interleave(acc[1]);
+            const uint32_t lo = ps_interleave((e0 & 0xFFFFu) | (e1 << 16));
+            const uint32_t hi = ps_interleave((e0 >> 16) | (e1 & 0xFFFF0000u));
+            hits = ((uint64_t)hi << 32) | lo;
+        }
     }
 #endif
 #if defined(DMX_PS_AB) && (DMX_PS_AB == 1 || DMX_PS_AB == 2)   // timing A/B: no checks
@@ -1984,7 +2048,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
                     w3 = vc[1];
                     w4 = vc[2];
                     w5 = vc[3];
-                    auto hits = ps_lookups<S>(tb_.bm, w0, w1, w2, w3, w4, w5);
+                    auto hits = ps_lookups<S>(tb_.pr, w0, w1, w2, w3, w4, w5);
                     using HitT = decltype(hits);
                     {
                         const int lim = xe - (a + 64 * k);     // sampled positions < xe
@@ -2148,11 +2212,11 @@ __device__ __forceinline__ void flat_check(const RoundArgs& R, const CellPtrs& c
 }
 
 template <int S>
-__global__ __launch_bounds__(kScanBlock) void pscan_kernel(RoundArgs R) {
+__global__ __launch_bounds__(kPScanBlock) void pscan_kernel(RoundArgs R) {
     static_assert(S == 1 || S == 2 || S == 4, "sampling stride: 64 positions per step");
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
-    __shared__ __attribute__((aligned(16))) uint32_t s_sb[kScanBlock / 64][kSbWords];
-    __shared__ uint16_t s_q[kScanBlock / 64][64];
+    __shared__ __attribute__((aligned(16))) uint32_t s_sb[kPScanBlock / 64][kSbWords];
+    __shared__ uint16_t s_q[kPScanBlock / 64][64];
     const PsTables tb = ps_load_tables(R.pieces, s_dyn);
     __syncthreads();
     const CellPtrs cp(R);
@@ -2160,8 +2224,8 @@ __global__ __launch_bounds__(kScanBlock) void pscan_kernel(RoundArgs R) {
     uint32_t* const sbw = s_sb[threadIdx.x >> 6];   // [4 + k]: word k of the superblock
     uint16_t* const q = s_q[threadIdx.x >> 6];
     const uint4* sp = reinterpret_cast<const uint4*>(R.pk.seq);
-    const uint32_t nw = gridDim.x * (kScanBlock / 64);
-    for (uint32_t sb = blockIdx.x * (kScanBlock / 64) + (threadIdx.x >> 6); sb < R.nsb; sb += nw) {
+    const uint32_t nw = gridDim.x * (kPScanBlock / 64);
+    for (uint32_t sb = blockIdx.x * (kPScanBlock / 64) + (threadIdx.x >> 6); sb < R.nsb; sb += nw) {
         const int64_t wd = (int64_t)sb * (kSuperNt / 16) + 4 * lane;   // the lane's first word
         const bool live = wd < (int64_t)R.n_words;
         uint4 c = {0u, 0u, 0u, 0u};
@@ -2169,7 +2233,7 @@ __global__ __launch_bounds__(kScanBlock) void pscan_kernel(RoundArgs R) {
         uint32_t w0 = __shfl_up(c.w, 1u, 64), w5 = __shfl_down(c.x, 1u, 64);
         if (lane == 0) w0 = R.pk.seq[wd - 1];         // (the device guard covers word -1)
         if (lane == 63) w5 = live ? R.pk.seq[wd + 4] : 0u;
-        auto hits = ps_lookups<S>(tb.bm, w0, c.x, c.y, c.z, c.w, w5);
+        auto hits = ps_lookups<S>(tb.pr, w0, c.x, c.y, c.z, c.w, w5);
         using HitT = decltype(hits);
         if (!live) hits = 0;
         reinterpret_cast<uint4*>(sbw)[1 + lane] = c;
@@ -4665,15 +4729,12 @@ int prepare_flat(Ctx* c, hipStream_t st) {
         for (size_t e = 0; e < ents.size(); ++e) {
             if (e == 0 || ents[e].first != ents[e - 1].first) {
                 T->key[nk++] = (uint32_t)e;
-                T->bitmap[ents[e].first >> 5] |= 1u << (ents[e].first & 31);
+                piece_pair_add(T->pair, ents[e].first);
             }
             T->key[nk - 1] += 1u << 16;
             T->entry[e] = ents[e].second;
         }
-        for (int w = 0, rk = 0; w < kPieceBitmapWords; ++w) {
-            T->rank_base[w] = (uint16_t)rk;
-            rk += __builtin_popcount(T->bitmap[w]);
-        }
+        piece_rank_fill(*T);
         T->on = 1;
         T->step = step;
         T->n_pieces = npc;
@@ -4785,16 +4846,17 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
             if (R.cells[i]) hipMemsetAsync(c->d_cells[i], 0, 4 * c->cells_words, st);
         RoundArgs S = R;
         S.pieces = c->d_pieces_flat;
-        const uint32_t sgrid = std::min<uint32_t>((R.nsb + 3) / 4, kScanGrid);
+        constexpr uint32_t wpb = kPScanBlock / 64;   // superblocks per block step
+        const uint32_t sgrid = std::min<uint32_t>((R.nsb + wpb - 1) / wpb, kPScanGrid);
         const size_t lds = c->flat_lds;
         set_kid(S.pk.bd, kKerPieces);
         if (sgrid > 0) {
             if (c->flat_step == 4)
-                hipLaunchKernelGGL(pscan_kernel<4>, dim3(sgrid), dim3(kScanBlock), lds, st, S);
+                hipLaunchKernelGGL(pscan_kernel<4>, dim3(sgrid), dim3(kPScanBlock), lds, st, S);
             else if (c->flat_step == 2)
-                hipLaunchKernelGGL(pscan_kernel<2>, dim3(sgrid), dim3(kScanBlock), lds, st, S);
+                hipLaunchKernelGGL(pscan_kernel<2>, dim3(sgrid), dim3(kPScanBlock), lds, st, S);
             else
-                hipLaunchKernelGGL(pscan_kernel<1>, dim3(sgrid), dim3(kScanBlock), lds, st, S);
+                hipLaunchKernelGGL(pscan_kernel<1>, dim3(sgrid), dim3(kPScanBlock), lds, st, S);
         }
         DMX_DBG_SYNC("pscan_kernel");
     }
@@ -4807,7 +4869,7 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
                     hipLaunchKernelGGL(pcompact_kernel, dim3(cgrid), dim3(kScanBlock), 0, st, R);
                 DMX_DBG_SYNC("pcompact_kernel");
             } else {   // the per-part screen
-                const DevPieces& Q = hp.pieces;   // LDS image: bitmap + rank base, keys, entries
+                const DevPieces& Q = hp.pieces;   // LDS image: pair table + rank base, keys, entries
                 const size_t lds = (size_t)kPieceLdsFixed + 8 * ((Q.n_keys + 1) / 2) +
                                    8 * (size_t)Q.n_entries;
                 const uint32_t pgrid =

@@ -47,7 +47,7 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_rowdist", "dmx_rowdist_host", "dmx_edgegroups", "dmx_edgegroups_host",
            "dmx_pairhits", "dmx_pairhits_fetch", "dmx_hitgroups", "dmx_pairhits_host",
            "dmx_hitgroups_host", "dmx_hitgroups_stats", "dmx_rowpairdist", "dmx_rowpairdist_host",
-           "dmx_rowhits", "dmx_rowhits_host"]
+           "dmx_rowhits", "dmx_rowhits_host", "dmx_panel_piece_pairs"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -151,6 +151,10 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "dmx_panel_pieces"):
         L.dmx_panel_pieces.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_int),
                                        c_int, ctypes.c_double, c_int, c_int, P, c_int, P, c_int]
+    if hasattr(L, "dmx_panel_piece_pairs"):
+        L.dmx_panel_piece_pairs.argtypes = [ctypes.POINTER(ctypes.c_char_p),
+                                            ctypes.POINTER(c_int), c_int, ctypes.c_double, c_int,
+                                            c_int, P, P, P, c_int]
     if hasattr(L, "dmx_pairdist"):
         L.dmx_pairdist.argtypes = [P, c_int, P, P, P, P, c_size, P]
         L.dmx_pairdist_host.argtypes = [c_int, P, P, c_u64p, P, c_size, P, P, P, P, c_size, P,
@@ -1103,6 +1107,22 @@ def panel_pieces(seqs, flags: int, max_errors: float = 0.1, min_overlap: int = 3
                      "off": (v >> 38) & 3, "dlo": ((v >> 40) & 255) - 128,
                      "dhi": ((v >> 48) & 255) - 128})
     return rc, info, ents
+
+
+def panel_piece_pairs(seqs, flags: int, max_errors: float = 0.1, min_overlap: int = 3):
+    """Host only: (status, pair, rank_base, keys) of that piece screen (include/dmx.h
+    dmx_panel_piece_pairs): the 4096-word pair table of the sampled 8-mers, the rank base per four
+    rows, and per key (increasing 8-mer) first entry | count << 16 into panel_pieces' entries."""
+    L = load()
+    arr = (ctypes.c_char_p * len(seqs))(*[s.encode("ascii") for s in seqs])
+    lens = (ctypes.c_int * len(seqs))(*[len(s) for s in seqs])
+    pair = np.zeros(4096, dtype=np.uint32)
+    rank = np.zeros(1024, dtype=np.uint16)
+    keys = np.zeros(2048, dtype=np.uint32)
+    rc = L.dmx_panel_piece_pairs(arr, lens, len(seqs), float(max_errors), int(min_overlap),
+                                 int(flags), pair.ctypes.data, rank.ctypes.data, keys.ctypes.data,
+                                 len(keys))
+    return rc, pair, rank, keys
 
 
 def host_register(arrays) -> list:
