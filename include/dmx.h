@@ -499,8 +499,9 @@ float dmx_rowdist_ms(dmx_ctx* ctx);  /* device time of the last dmx_rowdist (HIP
  * per longer read j the lines of the largest identity, ties kept; then greedy groups) and
  * merge_groups() (:1058-1087: merged until nothing moves).  Every kept line i:j is an edge
  * {i, j}, and the groups are the connected components of the edges.  Only a label per read
- * leaves the device.  Not replaced: comp_consensus_groups (:1206, random sampling) onward, the
- * species groups and the .group files. */
+ * leaves the device.  The species groups (SSG / Estimate, read_indexes) are the section after
+ * this one.  Not replaced: the random sampling of comp_consensus_groups (:1206) onward, finetune,
+ * and the .group and results files. */
 #define DMX_LG_NONE 0xFFFFFFFFu  /* a node on no edge; a read with no hit; a pair with no outcome */
 #define DMX_LG_REV 0x80000000u   /* an outcome's reverse bit (the host twins' outcome words)      */
 #define DMX_LG_MAX_PAIRS 0x7FFFFFFFu /* pairs per dmx_pairhits, edges per dmx_edgegroups: places
@@ -561,8 +562,58 @@ int dmx_hitgroups_host(const uint32_t* q, const uint32_t* t, const uint32_t* out
 /* Device time (ms, HIP events; first n_ms written): ms[0] the distance launches of the last
  * dmx_pairhits, ms[1] the last compaction (dmx_pairhits_fetch, dmx_hitgroups), ms[2] the last
  * components run (dmx_edgegroups, dmx_hitgroups; first kernel to last, the flag's trips to the
- * host between the rounds included).  Returns that run's hooking rounds. */
+ * host between the rounds included), ms[3] the last dmx_hithist.  Returns that run's hooking
+ * rounds. */
 int dmx_hitgroups_stats(dmx_ctx* ctx, float* ms, int n_ms);
+
+/* ---- Species groups: identity histogram, cross hits, per-group components ------
+ * Replaces: SSG() of amplicon_sorter.py (:810-836, the histogram of all similarity lines behind
+ * the estimated species threshold) and the first half of read_indexes() (:1363-1411: per gene
+ * group the lines at that threshold with a read in the group, the best per longer read, greedy
+ * groups, merge_groups).  All three work on the outcomes of the last dmx_pairhits and leave
+ * them, best[] and dmx_pairhits_fetch as they are; all are DMX_E_INVALID without valid outcomes.
+ * Not replaced: finetune, the random sampling, the .group and results files.
+ *
+ * dmx_hithist: for every hit (forward or reverse) with distance d and target t,
+ * hist[bins[bin_off[t] + d]] += 1: the caller's table maps a distance to a class (the sorter:
+ * thousandths of identity by the reference's own rounding, a row per distinct target length).
+ * bin_off has one entry per resident read, bins n_bins entries, hist n_classes <= 1024 counters
+ * that the call adds to.  A target outside the reads, bin_off[t] + d >= n_bins or a class >=
+ * n_classes is detected on the device in every build and not followed: the call is
+ * DMX_E_INVALID naming the kind, and hist is left untouched.  A block counts in LDS and adds its
+ * counters to the global ones once. */
+int dmx_hithist(dmx_ctx* ctx, const uint32_t* bin_off, const uint16_t* bins, size_t n_bins,
+                uint32_t n_classes, uint64_t* hist);
+/* label[r] (one per resident read) = the read's gene group, or DMX_LG_NONE; cap2[r] = the largest
+ * distance whose identity is still >= the species threshold at r's length, -1 for none.
+ * The cross hits: the hits with cap2[t] >= 0, d <= cap2[t] and label[q] != label[t] (so at least
+ * one of the two is in a group), in ascending place, by dmx_pairhits_fetch's compaction with
+ * this predicate.  pair, d, rev, cap and *n as dmx_pairhits_fetch's: *n is always the count; with
+ * cap below it nothing is written and the call is DMX_E_INVALID. */
+int dmx_pairhits_cross(dmx_ctx* ctx, const uint32_t* label, const int32_t* cap2, uint32_t* pair,
+                       uint32_t* d, uint8_t* rev, size_t cap, size_t* n);
+/* Components over n_nodes >= n_reads nodes (the resident reads first, then the caller's own).
+ * Edges: the hits {q, t} with label[q] == label[t] != DMX_LG_NONE and d <= tie2[t], where
+ * tie2[t] == DMX_LG_NONE means no edge for t; and the n_extra edges {xa[e], xb[e]}, which are
+ * written behind the compacted hits, so that one components run sees both.  labels_out (n_nodes)
+ * as dmx_edgegroups'.  An endpoint >= n_nodes or n_nodes < n_reads is DMX_E_INVALID before
+ * anything is launched. */
+int dmx_hitgroups_within(dmx_ctx* ctx, const uint32_t* tie2, const uint32_t* label,
+                         const uint32_t* xa, const uint32_t* xb, size_t n_extra, uint32_t n_nodes,
+                         uint32_t* labels_out);
+/* Host only (no GPU; tests, ctx=None of dmx.sorter): the three on the state of dmx_pairhits_host
+ * (its pair list and outcome words).  Errors: dmx_last_error(NULL). */
+int dmx_hithist_host(const uint32_t* t, const uint32_t* outcome, size_t n_pairs, size_t n_reads,
+                     const uint32_t* bin_off, const uint16_t* bins, size_t n_bins,
+                     uint32_t n_classes, uint64_t* hist);
+int dmx_pairhits_cross_host(const uint32_t* q, const uint32_t* t, const uint32_t* outcome,
+                            size_t n_pairs, size_t n_reads, const uint32_t* label,
+                            const int32_t* cap2, uint32_t* pair, uint32_t* d, uint8_t* rev,
+                            size_t cap, size_t* n);
+int dmx_hitgroups_within_host(const uint32_t* q, const uint32_t* t, const uint32_t* outcome,
+                              size_t n_pairs, size_t n_reads, const uint32_t* tie2,
+                              const uint32_t* label, const uint32_t* xa, const uint32_t* xb,
+                              size_t n_extra, uint32_t n_nodes, uint32_t* labels_out);
 
 /* ---- Rows of masks against rows of masks ----------------------------------------
  * The comparisons of iden_consensus() (amplicon_sorter.py:1140-1159) as the pair loops of

@@ -18,6 +18,9 @@
 //               nothing; a last pass writes labels.  parent[v] <= v always holds, so there are no
 //               cycles, a root is the smallest node of its tree, and the result (the smallest
 //               node of the component) does not depend on the order the atomics land in.
+// The species groups (dmx_hithist, dmx_pairhits_cross, dmx_hitgroups_within; DESIGN.md §8k;
+// amplicon_sorter.py SSG :810-836, read_indexes :1363-1411) read the same outcomes: a histogram
+// of the hits' identity classes (lg_hist_kernel), and the compaction with two more predicates.
 // The forward pass itself is dmx_pairdist's (dmx_pairdist.hip dmx_pairhits).
 #include <cstring>
 #include <numeric>
@@ -46,8 +49,14 @@ struct LgState {
     DevBuf<uint8_t> sel_rev;
     // components
     DevBuf<uint32_t> parent, labels, tie, flag;
+    // species groups: per read its gene group and second cap; the histogram's table and counters
+    DevBuf<uint32_t> label, bin_off, hbad;
+    DevBuf<int32_t> cap2;
+    DevBuf<uint16_t> bins;
+    DevBuf<unsigned long long> hist;
     hipEvent_t ev[2] = {};
-    float ms[3] = {0.f, 0.f, 0.f};   // dmx_pairhits' forward launches, compaction, components
+    // dmx_pairhits' forward launches, compaction, components, histogram
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};
     int rounds = 0;                  // hooking rounds of the last components run
     ~LgState() {
         for (auto& e : ev)
@@ -123,7 +132,9 @@ struct LgCompact {
     const uint32_t* outc;
     const uint32_t* q;
     const uint32_t* t;
-    const uint32_t* tie;     // edges: per read, the largest distance kept
+    const uint32_t* tie;     // edges: per read, the largest distance kept (within: NONE = no edge)
+    const uint32_t* label;   // cross, within: per read, its gene group or DMX_LG_NONE
+    const int32_t* cap2;     // cross: per read, the largest distance of the second threshold
     uint32_t n_pairs, n_reads;
     uint32_t* blk;           // [block]: its count, then its offset; [n_blocks]: the total
     uint32_t* out_a;         // hits: the pair's place in the input; edges: q
@@ -132,15 +143,34 @@ struct LgCompact {
     uint32_t out_cap;
 };
 
-// Is pair i kept?  Hits: every pair with an outcome.  Edges: those with d <= tie[t].
-template <bool kEdges>
+// What a compaction keeps, and what it writes: hits and cross hits (place, d, reverse bit), edges
+// and within-group edges (q, t).
+enum LgKind : int { kLgHits = 0, kLgEdges = 1, kLgCross = 2, kLgWithin = 3 };
+constexpr bool lg_writes_edges(int kind) { return kind == kLgEdges || kind == kLgWithin; }
+
+// Is pair i kept?  Hits: every pair with an outcome.  Edges: those with d <= tie[t].  Cross: the
+// hits within the second threshold of their target (cap2[t] >= 0, d <= cap2[t]) whose ends carry
+// different labels (so one of the two is a group).  Within: the hits whose ends carry the same
+// group and d <= tie[t], where tie[t] = DMX_LG_NONE keeps nothing.  Every read index is tested
+// against n_reads before it indexes a per-read table.
+template <int kKind>
 __device__ __forceinline__ bool lg_keep(const LgCompact& A, uint32_t i) {
     if (i >= A.n_pairs) return false;
     const uint32_t o = A.outc[i];
     if (o == DMX_LG_NONE) return false;
-    if constexpr (kEdges) {
+    if constexpr (kKind == kLgEdges) {
         const uint32_t r = A.t[i];
         return r < A.n_reads && (o & kLgDist) <= A.tie[r];
+    } else if constexpr (kKind == kLgCross) {
+        const uint32_t x = A.q[i], r = A.t[i];
+        if (x >= A.n_reads || r >= A.n_reads) return false;
+        const int64_t c2 = A.cap2[r];
+        return c2 >= 0 && (int64_t)(o & kLgDist) <= c2 && A.label[x] != A.label[r];
+    } else if constexpr (kKind == kLgWithin) {
+        const uint32_t x = A.q[i], r = A.t[i];
+        if (x >= A.n_reads || r >= A.n_reads) return false;
+        const uint32_t lr = A.label[r], tr = A.tie[r];
+        return lr != DMX_LG_NONE && A.label[x] == lr && tr != DMX_LG_NONE && (o & kLgDist) <= tr;
     } else {
         return true;
     }
@@ -164,10 +194,10 @@ __device__ __forceinline__ uint32_t lg_block_rank(bool f, uint32_t* total) {
     return before;
 }
 
-template <bool kEdges>
+template <int kKind>
 __global__ __launch_bounds__(kLgBlock) void lg_count_kernel(LgCompact A) {
     uint32_t tot;
-    lg_block_rank(lg_keep<kEdges>(A, blockIdx.x * kLgBlock + threadIdx.x), &tot);
+    lg_block_rank(lg_keep<kKind>(A, blockIdx.x * kLgBlock + threadIdx.x), &tot);
     if (threadIdx.x == 0) A.blk[blockIdx.x] = tot;
 }
 
@@ -200,14 +230,14 @@ __global__ __launch_bounds__(kLgBlock) void lg_scan_kernel(uint32_t* blk, uint32
     if (threadIdx.x == 0) blk[nb] = carry;
 }
 
-template <bool kEdges>
+template <int kKind>
 __global__ __launch_bounds__(kLgBlock) void lg_scatter_kernel(LgCompact A) {
     const uint32_t i = blockIdx.x * kLgBlock + threadIdx.x;
-    const bool f = lg_keep<kEdges>(A, i);
+    const bool f = lg_keep<kKind>(A, i);
     uint32_t tot;
     const uint32_t pos = A.blk[blockIdx.x] + lg_block_rank(f, &tot);
     if (!f || pos >= A.out_cap) return;
-    if constexpr (kEdges) {
+    if constexpr (lg_writes_edges(kKind)) {
         A.out_a[pos] = A.q[i];
         A.out_b[pos] = A.t[i];
     } else {
@@ -216,6 +246,81 @@ __global__ __launch_bounds__(kLgBlock) void lg_scatter_kernel(LgCompact A) {
         A.out_b[pos] = o & kLgDist;
         A.out_rev[pos] = (uint8_t)(o >> 31);
     }
+}
+
+// ---- identity histogram ------------------------------------------------------------------------
+
+constexpr uint32_t kLgHistClasses = 1024;   // the most classes: the block's LDS counters
+constexpr uint32_t kLgHistBlocks = 1024;    // the most blocks of a launch (grid-stride beyond)
+// DMX_HIST_WAVE_AGG=1 (make variant): the lanes of a wave that hold the same class add once.
+// Measured on the bins of profiles/speciesgroups_bench.json; the record says which is built.
+#ifndef DMX_HIST_WAVE_AGG
+#define DMX_HIST_WAVE_AGG 0
+#endif
+enum LgHistBad : uint32_t { kLgBadRead = 1, kLgBadBin = 2, kLgBadClass = 4 };
+
+struct LgHist {
+    const uint32_t* outc;
+    const uint32_t* t;
+    const uint32_t* bin_off;   // per read: where its length's row of the table starts
+    const uint16_t* bins;      // the table: the class of distance d at bins[bin_off[t] + d]
+    uint64_t n_bins;
+    uint32_t n_pairs, n_reads, n_classes;
+    unsigned long long* hist;  // n_classes counters, zeroed before the launch
+    uint32_t* bad;             // LgHistBad bits: an index formed from data was outside its extent
+    Bounds bd;
+};
+
+// hist[class of the hit] += 1 over the hits of the outcomes: a thread per pair, grid-stride; the
+// block counts in LDS and adds its nonzero counters to the global ones once.  A block sees fewer
+// than 2^31 pairs, so its 32-bit counters cannot wrap.  A target outside the reads, a table index
+// outside the bins or a class outside the classes is not followed: it sets its bit of *bad and
+// the host discards the counts.
+__global__ __launch_bounds__(kLgBlock) void lg_hist_kernel(LgHist A) {
+    __shared__ uint32_t h[kLgHistClasses];
+    for (uint32_t k = threadIdx.x; k < kLgHistClasses; k += kLgBlock) h[k] = 0u;
+    __syncthreads();
+    uint32_t bad = 0u;
+    const uint32_t stride = gridDim.x * kLgBlock;
+    // every lane of a wave runs the same number of rounds: the ballots below see whole waves
+    for (uint32_t base = blockIdx.x * kLgBlock; base < A.n_pairs; base += stride) {
+        const uint32_t i = base + threadIdx.x;
+        uint32_t cls = DMX_LG_NONE;
+        if (i < A.n_pairs) {
+            const uint32_t o = A.outc[i];
+            if (o != DMX_LG_NONE) {
+                const uint32_t r = A.t[i];
+                if (r >= A.n_reads) {
+                    bad |= kLgBadRead;
+                } else {
+                    const uint64_t at = (uint64_t)A.bin_off[r] + (o & kLgDist);
+                    if (at >= A.n_bins) {
+                        bad |= kLgBadBin;
+                    } else if (bchk(A.bd, (int64_t)at, 0, (int64_t)A.n_bins, kBufHistBins)) {
+                        const uint32_t x = A.bins[at];
+                        if (x >= A.n_classes || x >= kLgHistClasses) bad |= kLgBadClass;
+                        else cls = x;
+                    }
+                }
+            }
+        }
+#if DMX_HIST_WAVE_AGG
+        uint64_t todo = __ballot(cls != DMX_LG_NONE);
+        while (todo) {
+            const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
+            const uint32_t x = (uint32_t)__shfl((int)cls, (int)lead);
+            const uint64_t same = __ballot(cls == x);
+            if ((threadIdx.x & 63u) == lead) atomicAdd(&h[x], (uint32_t)__popcll(same));
+            todo &= ~same;
+        }
+#else
+        if (cls != DMX_LG_NONE) atomicAdd(&h[cls], 1u);
+#endif
+    }
+    if (bad) atomicOr(A.bad, bad);
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < A.n_classes && k < kLgHistClasses; k += kLgBlock)
+        if (h[k]) atomicAdd(&A.hist[k], (unsigned long long)h[k]);
 }
 
 // ---- components --------------------------------------------------------------------------------
@@ -311,7 +416,7 @@ int lg_state(Ctx* c, const char* who) {
 
 // The compaction of the last dmx_pairhits' outcomes into sel_a / sel_b (/ sel_rev), room for
 // `cap` entries; *total = how many are kept.  Synchronises; ms[1] = its device time.
-template <bool kEdges>
+template <int kKind>
 int lg_compact(Ctx* c, const char* who, size_t cap, uint32_t* total) {
     LgState* s = c->lg;
     hipStream_t st = c->stream;
@@ -322,16 +427,17 @@ int lg_compact(Ctx* c, const char* who, size_t cap, uint32_t* total) {
     LG_CK(who, s->blk.reserve((size_t)nb + 1));
     LG_CK(who, s->sel_a.reserve(cap));
     LG_CK(who, s->sel_b.reserve(cap));
-    if (!kEdges) LG_CK(who, s->sel_rev.reserve(cap));
+    if (!lg_writes_edges(kKind)) LG_CK(who, s->sel_rev.reserve(cap));
     LgCompact A;
     A.outc = s->outc.p, A.q = s->q.p, A.t = s->t.p, A.tie = s->tie.p;
+    A.label = s->label.p, A.cap2 = s->cap2.p;
     A.n_pairs = (uint32_t)s->n_pairs, A.n_reads = (uint32_t)s->n_reads;
     A.blk = s->blk.p, A.out_a = s->sel_a.p, A.out_b = s->sel_b.p, A.out_rev = s->sel_rev.p;
     A.out_cap = (uint32_t)cap;
     LG_CK(who, hipEventRecord(s->ev[0], st));
-    hipLaunchKernelGGL(lg_count_kernel<kEdges>, dim3(nb), dim3(kLgBlock), 0, st, A);
+    hipLaunchKernelGGL(lg_count_kernel<kKind>, dim3(nb), dim3(kLgBlock), 0, st, A);
     hipLaunchKernelGGL(lg_scan_kernel, dim3(1), dim3(kLgBlock), 0, st, s->blk.p, nb);
-    hipLaunchKernelGGL(lg_scatter_kernel<kEdges>, dim3(nb), dim3(kLgBlock), 0, st, A);
+    hipLaunchKernelGGL(lg_scatter_kernel<kKind>, dim3(nb), dim3(kLgBlock), 0, st, A);
     LG_CK(who, hipGetLastError());
     LG_CK(who, hipEventRecord(s->ev[1], st));
     LG_CK(who, hipMemcpyAsync(total, s->blk.p + nb, 4, hipMemcpyDeviceToHost, st));
@@ -528,14 +634,15 @@ int lg_compact_outcomes(Ctx* c, const char* who, const uint32_t* d_outc, size_t 
     LG_CK(who, s->sel_rev.reserve(room));
     LgCompact A;
     A.outc = d_outc, A.q = nullptr, A.t = nullptr, A.tie = nullptr;   // hits: the outcomes alone
+    A.label = nullptr, A.cap2 = nullptr;
     A.n_pairs = (uint32_t)n_pairs, A.n_reads = 0;
     A.blk = s->blk.p, A.out_a = s->sel_a.p, A.out_b = s->sel_b.p, A.out_rev = s->sel_rev.p;
     A.out_cap = (uint32_t)room;
     uint32_t total = 0;
     LG_CK(who, hipEventRecord(s->ev[0], st));
-    hipLaunchKernelGGL(lg_count_kernel<false>, dim3(nb), dim3(kLgBlock), 0, st, A);
+    hipLaunchKernelGGL(lg_count_kernel<kLgHits>, dim3(nb), dim3(kLgBlock), 0, st, A);
     hipLaunchKernelGGL(lg_scan_kernel, dim3(1), dim3(kLgBlock), 0, st, s->blk.p, nb);
-    hipLaunchKernelGGL(lg_scatter_kernel<false>, dim3(nb), dim3(kLgBlock), 0, st, A);
+    hipLaunchKernelGGL(lg_scatter_kernel<kLgHits>, dim3(nb), dim3(kLgBlock), 0, st, A);
     LG_CK(who, hipGetLastError());
     LG_CK(who, hipEventRecord(s->ev[1], st));
     LG_CK(who, hipMemcpyAsync(&total, s->blk.p + nb, 4, hipMemcpyDeviceToHost, st));
@@ -705,7 +812,7 @@ extern "C" int dmx_pairhits_fetch(dmx_ctx* c, uint32_t* pair, uint32_t* d, uint8
     }
     LG_CK(who, hipSetDevice(c->device));
     uint32_t total = 0;
-    if (const int rc = lg_compact<false>(c, who, (size_t)s->n_hits, &total)) return rc;
+    if (const int rc = lg_compact<kLgHits>(c, who, (size_t)s->n_hits, &total)) return rc;
     if (total != s->n_hits) {
         c->err = "dmx_pairhits_fetch: the compaction kept " + std::to_string(total) + " of " +
                  std::to_string(s->n_hits) + " hits";
@@ -734,7 +841,7 @@ extern "C" int dmx_hitgroups(dmx_ctx* c, const uint32_t* tie, uint32_t* labels) 
     LG_CK(who, s->tie.reserve(s->n_reads));
     LG_CK(who, hipMemcpyAsync(s->tie.p, tie, s->n_reads * 4, hipMemcpyHostToDevice, c->stream));
     uint32_t n_edges = 0;
-    if (const int rc = lg_compact<true>(c, who, (size_t)s->n_hits, &n_edges)) return rc;
+    if (const int rc = lg_compact<kLgEdges>(c, who, (size_t)s->n_hits, &n_edges)) return rc;
     if (n_edges > s->n_hits) {
         c->err = "dmx_hitgroups: the compaction kept more edges than there are hits";
         return DMX_E_STATE;
@@ -745,8 +852,290 @@ extern "C" int dmx_hitgroups(dmx_ctx* c, const uint32_t* tie, uint32_t* labels) 
     return DMX_OK;
 }
 
+// ---- species groups -------------------------------------------------------------
+
+namespace {
+
+const char* lg_hist_bad_name(uint32_t bad) {
+    return (bad & kLgBadRead)  ? "a target outside the reads"
+           : (bad & kLgBadBin) ? "a table index (bin_off[t] + d) outside the n_bins entries"
+                               : "a class outside n_classes";
+}
+
+// The first hit of the outcomes that the histogram cannot follow, as LgHistBad (0: none).
+uint32_t lg_hist_host_bad(const uint32_t* t, const uint32_t* outcome, size_t n_pairs,
+                          size_t n_reads, const uint32_t* bin_off, const uint16_t* bins,
+                          size_t n_bins, uint32_t n_classes, size_t* where) {
+    for (size_t i = 0; i < n_pairs; ++i) {
+        if (outcome[i] == DMX_LG_NONE) continue;
+        *where = i;
+        if (t[i] >= n_reads) return kLgBadRead;
+        const uint64_t at = (uint64_t)bin_off[t[i]] + (outcome[i] & kLgDist);
+        if (at >= n_bins) return kLgBadBin;
+        if (bins[at] >= n_classes) return kLgBadClass;
+    }
+    return 0;
+}
+
+// 0, or DMX_E_INVALID: the arguments every species-group call checks before it does anything.
+int lg_within_args(const char* who, size_t n_reads, const uint32_t* xa, const uint32_t* xb,
+                   size_t n_extra, uint32_t n_nodes, std::string* err) {
+    if (n_nodes < n_reads) {
+        *err = std::string(who) + ": " + std::to_string(n_nodes) + " nodes for " +
+               std::to_string(n_reads) + " reads";
+        return DMX_E_INVALID;
+    }
+    if (n_extra && (!xa || !xb)) {
+        *err = std::string(who) + ": null extra edges";
+        return DMX_E_INVALID;
+    }
+    return lg_validate_edges(who, xa, xb, n_extra, n_nodes, err);
+}
+
+}  // namespace
+
+extern "C" int dmx_hithist_host(const uint32_t* t, const uint32_t* outcome, size_t n_pairs,
+                                size_t n_reads, const uint32_t* bin_off, const uint16_t* bins,
+                                size_t n_bins, uint32_t n_classes, uint64_t* hist) {
+    const char* const who = "dmx_hithist_host";
+    if ((n_pairs && (!t || !outcome)) || (n_reads && !bin_off) || (n_bins && !bins) || !hist ||
+        !n_classes || n_classes > kLgHistClasses) {
+        set_process_error(std::string(who) + ": null argument, or n_classes outside 1.." +
+                          std::to_string(kLgHistClasses));
+        return DMX_E_INVALID;
+    }
+    size_t where = 0;
+    if (const uint32_t bad = lg_hist_host_bad(t, outcome, n_pairs, n_reads, bin_off, bins, n_bins,
+                                              n_classes, &where)) {
+        set_process_error(std::string(who) + ": pair " + std::to_string(where) + ": " +
+                          lg_hist_bad_name(bad));
+        return DMX_E_INVALID;
+    }
+    for (size_t i = 0; i < n_pairs; ++i)
+        if (outcome[i] != DMX_LG_NONE) ++hist[bins[(uint64_t)bin_off[t[i]] + (outcome[i] & kLgDist)]];
+    return DMX_OK;
+}
+
+extern "C" int dmx_hithist(dmx_ctx* c, const uint32_t* bin_off, const uint16_t* bins, size_t n_bins,
+                           uint32_t n_classes, uint64_t* hist) {
+    const char* const who = "dmx_hithist";
+    if (!c) return DMX_E_INVALID;
+    if (!c->lg || !c->lg->valid) {
+        c->err = "dmx_hithist: no dmx_pairhits since the last dmx_load";
+        return DMX_E_INVALID;
+    }
+    LgState* s = c->lg;
+    s->ms[3] = 0.f;
+    if (!hist || !n_classes || n_classes > kLgHistClasses || (s->n_reads && !bin_off) ||
+        (n_bins && !bins)) {
+        c->err = "dmx_hithist: null argument, or n_classes outside 1.." +
+                 std::to_string(kLgHistClasses);
+        return DMX_E_INVALID;
+    }
+    if (!s->n_pairs || !s->n_hits) return DMX_OK;
+    hipStream_t st = c->stream;
+    LG_CK(who, hipSetDevice(c->device));
+    LG_CK(who, s->bin_off.reserve(s->n_reads));
+    LG_CK(who, s->bins.reserve(n_bins));
+    LG_CK(who, s->hist.reserve(n_classes));
+    LG_CK(who, s->hbad.reserve(1));
+    LG_CK(who, hipMemcpyAsync(s->bin_off.p, bin_off, s->n_reads * 4, hipMemcpyHostToDevice, st));
+    if (n_bins)
+        LG_CK(who, hipMemcpyAsync(s->bins.p, bins, n_bins * 2, hipMemcpyHostToDevice, st));
+    LG_CK(who, hipMemsetAsync(s->hist.p, 0, (size_t)n_classes * sizeof(unsigned long long), st));
+    LG_CK(who, hipMemsetAsync(s->hbad.p, 0, 4, st));
+    LG_CK(who, bounds_reset(c, st));
+    LgHist A;
+    A.outc = s->outc.p, A.t = s->t.p, A.bin_off = s->bin_off.p, A.bins = s->bins.p;
+    A.n_bins = n_bins, A.n_pairs = (uint32_t)s->n_pairs, A.n_reads = (uint32_t)s->n_reads;
+    A.n_classes = n_classes, A.hist = s->hist.p, A.bad = s->hbad.p;
+    A.bd = make_bounds(c, kKerHithist);
+    const uint32_t nb = std::min(lg_blocks(s->n_pairs), kLgHistBlocks);
+    LG_CK(who, hipEventRecord(s->ev[0], st));
+    hipLaunchKernelGGL(lg_hist_kernel, dim3(nb), dim3(kLgBlock), 0, st, A);
+    LG_CK(who, hipGetLastError());
+    LG_CK(who, hipEventRecord(s->ev[1], st));
+    std::vector<unsigned long long> got(n_classes);
+    uint32_t bad = 0;
+    LG_CK(who, hipMemcpyAsync(got.data(), s->hist.p, (size_t)n_classes * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, st));
+    LG_CK(who, hipMemcpyAsync(&bad, s->hbad.p, 4, hipMemcpyDeviceToHost, st));
+    LG_CK(who, hipStreamSynchronize(st));
+    hipEventElapsedTime(&s->ms[3], s->ev[0], s->ev[1]);
+    if (bad) {
+        c->err = std::string(who) + ": " + lg_hist_bad_name(bad);
+        return DMX_E_INVALID;
+    }
+    if (const int brc = bounds_check(c, who)) return brc;
+    for (uint32_t k = 0; k < n_classes; ++k) hist[k] += got[k];
+    return DMX_OK;
+}
+
+extern "C" int dmx_pairhits_cross_host(const uint32_t* q, const uint32_t* t,
+                                       const uint32_t* outcome, size_t n_pairs, size_t n_reads,
+                                       const uint32_t* label, const int32_t* cap2, uint32_t* pair,
+                                       uint32_t* d, uint8_t* rev, size_t cap, size_t* n) {
+    const char* const who = "dmx_pairhits_cross_host";
+    if (!n || (n_pairs && (!q || !t || !outcome)) || (n_reads && (!label || !cap2))) {
+        set_process_error(std::string(who) + ": null argument");
+        return DMX_E_INVALID;
+    }
+    *n = 0;
+    std::string err;
+    if (const int rc = lg_validate_edges(who, q, t, n_pairs, (uint32_t)std::min<size_t>(
+                                             n_reads, DMX_LG_NONE), &err)) {
+        set_process_error(err);
+        return rc;
+    }
+    std::vector<size_t> keep;
+    for (size_t i = 0; i < n_pairs; ++i) {
+        if (outcome[i] == DMX_LG_NONE) continue;
+        const int64_t c2 = cap2[t[i]];
+        if (c2 >= 0 && (int64_t)(outcome[i] & kLgDist) <= c2 && label[q[i]] != label[t[i]])
+            keep.push_back(i);
+    }
+    *n = keep.size();
+    if (keep.empty()) return DMX_OK;
+    if (cap < keep.size() || !pair || !d || !rev) {
+        set_process_error(std::string(who) + ": room for " + std::to_string(cap) + " hits, " +
+                          std::to_string(keep.size()) + " to return");
+        return DMX_E_INVALID;
+    }
+    for (size_t k = 0; k < keep.size(); ++k) {
+        pair[k] = (uint32_t)keep[k];
+        d[k] = outcome[keep[k]] & kLgDist;
+        rev[k] = (uint8_t)(outcome[keep[k]] >> 31);
+    }
+    return DMX_OK;
+}
+
+extern "C" int dmx_pairhits_cross(dmx_ctx* c, const uint32_t* label, const int32_t* cap2,
+                                  uint32_t* pair, uint32_t* d, uint8_t* rev, size_t cap, size_t* n) {
+    const char* const who = "dmx_pairhits_cross";
+    if (!c) return DMX_E_INVALID;
+    if (!n) {
+        c->err = "dmx_pairhits_cross: null count";
+        return DMX_E_INVALID;
+    }
+    *n = 0;
+    if (!c->lg || !c->lg->valid) {
+        c->err = "dmx_pairhits_cross: no dmx_pairhits since the last dmx_load";
+        return DMX_E_INVALID;
+    }
+    LgState* s = c->lg;
+    if (s->n_reads && (!label || !cap2)) {
+        c->err = "dmx_pairhits_cross: null label or cap table";
+        return DMX_E_INVALID;
+    }
+    if (!s->n_hits) return DMX_OK;
+    hipStream_t st = c->stream;
+    LG_CK(who, hipSetDevice(c->device));
+    LG_CK(who, s->label.reserve(s->n_reads));
+    LG_CK(who, s->cap2.reserve(s->n_reads));
+    LG_CK(who, hipMemcpyAsync(s->label.p, label, s->n_reads * 4, hipMemcpyHostToDevice, st));
+    LG_CK(who, hipMemcpyAsync(s->cap2.p, cap2, s->n_reads * 4, hipMemcpyHostToDevice, st));
+    // the scatter writes no place at or past the room; the count is of all that are kept
+    const size_t room = std::min<size_t>(cap, (size_t)s->n_hits);
+    uint32_t total = 0;
+    if (const int rc = lg_compact<kLgCross>(c, who, room, &total)) return rc;
+    *n = total;
+    if (!total) return DMX_OK;
+    if (cap < total || !pair || !d || !rev) {
+        c->err = "dmx_pairhits_cross: room for " + std::to_string(cap) + " hits, " +
+                 std::to_string(total) + " to return";
+        return DMX_E_INVALID;
+    }
+    LG_CK(who, hipMemcpy(pair, s->sel_a.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    LG_CK(who, hipMemcpy(d, s->sel_b.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    LG_CK(who, hipMemcpy(rev, s->sel_rev.p, (size_t)total, hipMemcpyDeviceToHost));
+    return DMX_OK;
+}
+
+extern "C" int dmx_hitgroups_within_host(const uint32_t* q, const uint32_t* t,
+                                         const uint32_t* outcome, size_t n_pairs, size_t n_reads,
+                                         const uint32_t* tie2, const uint32_t* label,
+                                         const uint32_t* xa, const uint32_t* xb, size_t n_extra,
+                                         uint32_t n_nodes, uint32_t* labels_out) {
+    const char* const who = "dmx_hitgroups_within_host";
+    if ((n_pairs && (!q || !t || !outcome)) || (n_reads && (!tie2 || !label)) ||
+        (n_nodes && !labels_out)) {
+        set_process_error(std::string(who) + ": null argument (no dmx_pairhits_host outcomes?)");
+        return DMX_E_INVALID;
+    }
+    std::string err;
+    int rc = lg_within_args(who, n_reads, xa, xb, n_extra, n_nodes, &err);
+    if (!rc) rc = lg_validate_edges(who, q, t, n_pairs, (uint32_t)n_reads, &err);
+    if (rc) {
+        set_process_error(err);
+        return rc;
+    }
+    std::vector<uint32_t> a, b;
+    for (size_t i = 0; i < n_pairs; ++i) {
+        if (outcome[i] == DMX_LG_NONE) continue;
+        const uint32_t lr = label[t[i]], tr = tie2[t[i]];
+        if (lr != DMX_LG_NONE && label[q[i]] == lr && tr != DMX_LG_NONE &&
+            (outcome[i] & kLgDist) <= tr) {
+            a.push_back(q[i]);
+            b.push_back(t[i]);
+        }
+    }
+    a.insert(a.end(), xa, xa + n_extra);
+    b.insert(b.end(), xb, xb + n_extra);
+    lg_host_labels(a.data(), b.data(), a.size(), n_nodes, labels_out);
+    return DMX_OK;
+}
+
+extern "C" int dmx_hitgroups_within(dmx_ctx* c, const uint32_t* tie2, const uint32_t* label,
+                                    const uint32_t* xa, const uint32_t* xb, size_t n_extra,
+                                    uint32_t n_nodes, uint32_t* labels_out) {
+    const char* const who = "dmx_hitgroups_within";
+    if (!c) return DMX_E_INVALID;
+    if (!c->lg || !c->lg->valid) {
+        c->err = "dmx_hitgroups_within: no dmx_pairhits since the last dmx_load";
+        return DMX_E_INVALID;
+    }
+    LgState* s = c->lg;
+    if (const int rc = lg_within_args(who, s->n_reads, xa, xb, n_extra, n_nodes, &c->err)) return rc;
+    if (!n_nodes) return DMX_OK;
+    if ((s->n_reads && (!tie2 || !label)) || !labels_out) {
+        c->err = "dmx_hitgroups_within: null tie table, labels or output";
+        return DMX_E_INVALID;
+    }
+    if (s->n_hits + n_extra > DMX_LG_MAX_PAIRS) {
+        c->err = "dmx_hitgroups_within: at most " + std::to_string(DMX_LG_MAX_PAIRS) + " edges";
+        return DMX_E_UNSUPPORTED;
+    }
+    hipStream_t st = c->stream;
+    LG_CK(who, hipSetDevice(c->device));
+    if (s->n_reads) {
+        LG_CK(who, s->tie.reserve(s->n_reads));
+        LG_CK(who, s->label.reserve(s->n_reads));
+        LG_CK(who, hipMemcpyAsync(s->tie.p, tie2, s->n_reads * 4, hipMemcpyHostToDevice, st));
+        LG_CK(who, hipMemcpyAsync(s->label.p, label, s->n_reads * 4, hipMemcpyHostToDevice, st));
+    }
+    // one edge buffer: the kept hits first, the caller's edges behind them
+    const size_t room = (size_t)s->n_hits + n_extra;
+    LG_CK(who, s->sel_a.reserve(room));
+    LG_CK(who, s->sel_b.reserve(room));
+    uint32_t n_edges = 0;
+    if (const int rc = lg_compact<kLgWithin>(c, who, room, &n_edges)) return rc;
+    if (n_edges > s->n_hits) {
+        c->err = "dmx_hitgroups_within: the compaction kept more edges than there are hits";
+        return DMX_E_STATE;
+    }
+    if (n_extra) {
+        LG_CK(who, hipMemcpyAsync(s->sel_a.p + n_edges, xa, n_extra * 4, hipMemcpyHostToDevice, st));
+        LG_CK(who, hipMemcpyAsync(s->sel_b.p + n_edges, xb, n_extra * 4, hipMemcpyHostToDevice, st));
+    }
+    if (const int rc = lg_components(c, who, s->sel_a.p, s->sel_b.p, n_edges + (uint32_t)n_extra,
+                                     n_nodes))
+        return rc;
+    LG_CK(who, hipMemcpy(labels_out, s->labels.p, (size_t)n_nodes * 4, hipMemcpyDeviceToHost));
+    return DMX_OK;
+}
+
 extern "C" int dmx_hitgroups_stats(dmx_ctx* c, float* ms, int n_ms) {
     if (!c) return DMX_E_INVALID;
-    for (int k = 0; k < n_ms && k < 3 && ms; ++k) ms[k] = c->lg ? c->lg->ms[k] : 0.f;
+    for (int k = 0; k < n_ms && k < 4 && ms; ++k) ms[k] = c->lg ? c->lg->ms[k] : 0.f;
     return c->lg ? c->lg->rounds : 0;
 }

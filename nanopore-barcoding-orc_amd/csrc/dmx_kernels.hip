@@ -4617,12 +4617,13 @@ int bounds_check(Ctx* c, const char* where) {
         "finalize2_linked_kernel", "chop_kernel", "chop_big_kernel", "chop_start",
         "bounds_selftest_kernel", "pscreen_kernel", "pairdist_kernel", "pairalign_kernel",
         "pairalign_traceback_kernel", "groupalign_kernel", "groupalign_traceback_kernel",
-        "groupalign_merge_kernel", "rowdist_kernel", "rowpair_kernel", "rowpair_rc_kernel"};
+        "groupalign_merge_kernel", "rowdist_kernel", "rowpair_kernel", "rowpair_rc_kernel",
+        "lg_hist_kernel"};
     static const char* const kBuf[] = {"?", "seq", "nmask", "winner slots", "items", "results",
                                        "counts", "reads", "linked keys", "candidates", "chop",
                                        "pairdist scratch", "pairalign trace", "pairalign ops",
                                        "groupalign columns", "rowdist columns",
-                                       "rowpair columns"};
+                                       "rowpair columns", "identity table"};
     uint32_t rec[4];
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess)

@@ -47,7 +47,9 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_rowdist", "dmx_rowdist_host", "dmx_edgegroups", "dmx_edgegroups_host",
            "dmx_pairhits", "dmx_pairhits_fetch", "dmx_hitgroups", "dmx_pairhits_host",
            "dmx_hitgroups_host", "dmx_hitgroups_stats", "dmx_rowpairdist", "dmx_rowpairdist_host",
-           "dmx_rowhits", "dmx_rowhits_host", "dmx_panel_piece_pairs"]
+           "dmx_rowhits", "dmx_rowhits_host", "dmx_panel_piece_pairs", "dmx_hithist",
+           "dmx_pairhits_cross", "dmx_hitgroups_within", "dmx_hithist_host",
+           "dmx_pairhits_cross_host", "dmx_hitgroups_within_host"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -196,6 +198,15 @@ def load() -> ctypes.CDLL:
                                         ctypes.POINTER(ctypes.c_uint64), c_int]
         L.dmx_hitgroups_host.argtypes = [P, P, P, c_size, P, c_size, P]
         L.dmx_hitgroups_stats.argtypes = [P, ctypes.POINTER(ctypes.c_float), c_int]
+    if hasattr(L, "dmx_hithist"):
+        L.dmx_hithist.argtypes = [P, P, P, c_size, ctypes.c_uint32, P]
+        L.dmx_pairhits_cross.argtypes = [P, P, P, P, P, P, c_size, ctypes.POINTER(c_size)]
+        L.dmx_hitgroups_within.argtypes = [P, P, P, P, P, c_size, ctypes.c_uint32, P]
+        L.dmx_hithist_host.argtypes = [P, P, c_size, c_size, P, P, c_size, ctypes.c_uint32, P]
+        L.dmx_pairhits_cross_host.argtypes = [P, P, P, c_size, c_size, P, P, P, P, P, c_size,
+                                              ctypes.POINTER(c_size)]
+        L.dmx_hitgroups_within_host.argtypes = [P, P, P, c_size, c_size, P, P, P, P, c_size,
+                                                ctypes.c_uint32, P]
     if hasattr(L, "dmx_rowpairdist"):
         rr = [c_int, c_size, P, c_u64p, P, P]   # mode, n_rows, masks, row_off, q, t
         L.dmx_rowpairdist.argtypes = [P] + rr + [P, P, c_size, P]
@@ -617,11 +628,51 @@ class Context:
 
     def hitgroups_stats(self) -> dict:
         """Device time (ms): the distance launches of the last pairhits, the last compaction, the
-        last components run; and that run's hooking rounds."""
-        ms = (ctypes.c_float * 3)()
-        n = self._check(self._L.dmx_hitgroups_stats(self._h, ms, 3), "dmx_hitgroups_stats")
+        last components run, the last hithist; and the components run's hooking rounds."""
+        ms = (ctypes.c_float * 4)()
+        n = self._check(self._L.dmx_hitgroups_stats(self._h, ms, 4), "dmx_hitgroups_stats")
         return {"forward": float(ms[0]), "compact": float(ms[1]), "components": float(ms[2]),
-                "rounds": int(n)}
+                "hist": float(ms[3]), "rounds": int(n)}
+
+    # ---- species groups (include/dmx.h dmx_hithist .. dmx_hitgroups_within; DESIGN.md §8k) -------
+    def hithist(self, bin_off, bins, n_classes: int) -> np.ndarray:
+        """The histogram of the last pairhits' hits: hist[bins[bin_off[t] + d]] += 1 per hit with
+        distance d and target t (bin_off: uint32 per resident read; bins: uint16 classes below
+        n_classes <= 1024).  Returns uint64 counts, one per class."""
+        oa, ba = _hist_arrays(bin_off, bins, int(getattr(self, "_n_loaded", 0)))
+        hist = np.zeros(int(n_classes), dtype=np.uint64)
+        self._check(self._L.dmx_hithist(self._h, oa.ctypes.data, ba.ctypes.data, len(ba),
+                                        int(n_classes), hist.ctypes.data), "dmx_hithist")
+        return hist
+
+    def pairhits_cross(self, label, cap2):
+        """The hits of the last pairhits with d <= cap2[t] (int32 per read, -1: none) whose two
+        reads carry different labels (uint32 per read, LG_NONE: in no group), in ascending
+        place: (pair uint32, d uint32, rev uint8)."""
+        la, ca = _label_arrays(label, cap2, int(getattr(self, "_n_loaded", 0)))
+        n = ctypes.c_size_t(0)
+        cap = int(getattr(self, "_n_hits", 0))
+        pair, d = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        rev = np.zeros(cap, dtype=np.uint8)
+        self._check(self._L.dmx_pairhits_cross(self._h, la.ctypes.data, ca.ctypes.data,
+                                               pair.ctypes.data, d.ctypes.data, rev.ctypes.data,
+                                               cap, ctypes.byref(n)), "dmx_pairhits_cross")
+        return pair[:n.value].copy(), d[:n.value].copy(), rev[:n.value].copy()
+
+    def hitgroups_within(self, tie2, label, xa=(), xb=(), n_nodes=None) -> np.ndarray:
+        """Components over n_nodes nodes (default: the resident reads) of the last pairhits' hits
+        with label[q] == label[t] != LG_NONE and d <= tie2[t] (LG_NONE: no edge for t), plus the
+        caller's edges {xa, xb}: per node the smallest node of its component, LG_NONE on none."""
+        n_reads = int(getattr(self, "_n_loaded", 0))
+        ta, _ = _label_arrays(tie2, None, n_reads)
+        la, _ = _label_arrays(label, None, n_reads)
+        aa, ba = _edge_arrays(xa, xb)
+        n_nodes = n_reads if n_nodes is None else int(n_nodes)
+        labels = np.zeros(max(n_nodes, 0), dtype=np.uint32)
+        self._check(self._L.dmx_hitgroups_within(self._h, ta.ctypes.data, la.ctypes.data,
+                                                 aa.ctypes.data, ba.ctypes.data, len(aa), n_nodes,
+                                                 labels.ctypes.data), "dmx_hitgroups_within")
+        return labels
 
     def n_counts(self) -> int:
         a1 = 0 if self.mode == MODE_SINGLE else self.panel_sizes[1]
@@ -1042,6 +1093,65 @@ def hitgroups_host(hits, tie) -> np.ndarray:
     _host_check(L, L.dmx_hitgroups_host(hits.q.ctypes.data, hits.t.ctypes.data,
                                         hits.outcome.ctypes.data, len(hits.q), ta.ctypes.data,
                                         hits.n_reads, labels.ctypes.data), "dmx_hitgroups_host")
+    return labels
+
+
+def _hist_arrays(bin_off, bins, n_reads):
+    oa = np.ascontiguousarray(bin_off, dtype=np.uint32)
+    ba = np.ascontiguousarray(bins, dtype=np.uint16)
+    if oa.shape != (n_reads,) or ba.ndim != 1:
+        raise DmxError("hithist: bin_off must have one entry per read, bins one dimension")
+    return oa, ba
+
+
+def _label_arrays(label, cap2, n_reads):
+    la = np.ascontiguousarray(label, dtype=np.uint32)
+    ca = None if cap2 is None else np.ascontiguousarray(cap2, dtype=np.int32)
+    if la.shape != (n_reads,) or (ca is not None and ca.shape != (n_reads,)):
+        raise DmxError("species groups: the per-read tables must have one entry per read")
+    return la, ca
+
+
+def hithist_host(hits, bin_off, bins, n_classes: int) -> np.ndarray:
+    """dmx_hithist's contract on the host, on the state of pairhits_host."""
+    L = load()
+    oa, ba = _hist_arrays(bin_off, bins, hits.n_reads)
+    hist = np.zeros(int(n_classes), dtype=np.uint64)
+    _host_check(L, L.dmx_hithist_host(hits.t.ctypes.data, hits.outcome.ctypes.data, len(hits.t),
+                                      hits.n_reads, oa.ctypes.data, ba.ctypes.data, len(ba),
+                                      int(n_classes), hist.ctypes.data), "dmx_hithist_host")
+    return hist
+
+
+def pairhits_cross_host(hits, label, cap2):
+    """dmx_pairhits_cross' contract on the host, on the state of pairhits_host."""
+    L = load()
+    la, ca = _label_arrays(label, cap2, hits.n_reads)
+    cap = int((hits.outcome != LG_NONE).sum())
+    pair, d = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+    rev = np.zeros(cap, dtype=np.uint8)
+    n = ctypes.c_size_t(0)
+    _host_check(L, L.dmx_pairhits_cross_host(hits.q.ctypes.data, hits.t.ctypes.data,
+                                             hits.outcome.ctypes.data, len(hits.q), hits.n_reads,
+                                             la.ctypes.data, ca.ctypes.data, pair.ctypes.data,
+                                             d.ctypes.data, rev.ctypes.data, cap,
+                                             ctypes.byref(n)), "dmx_pairhits_cross_host")
+    return pair[:n.value].copy(), d[:n.value].copy(), rev[:n.value].copy()
+
+
+def hitgroups_within_host(hits, tie2, label, xa=(), xb=(), n_nodes=None) -> np.ndarray:
+    """dmx_hitgroups_within's contract on the host, on the state of pairhits_host."""
+    L = load()
+    ta, _ = _label_arrays(tie2, None, hits.n_reads)
+    la, _ = _label_arrays(label, None, hits.n_reads)
+    aa, ba = _edge_arrays(xa, xb)
+    n_nodes = hits.n_reads if n_nodes is None else int(n_nodes)
+    labels = np.zeros(max(n_nodes, 0), dtype=np.uint32)
+    _host_check(L, L.dmx_hitgroups_within_host(hits.q.ctypes.data, hits.t.ctypes.data,
+                                               hits.outcome.ctypes.data, len(hits.q),
+                                               hits.n_reads, ta.ctypes.data, la.ctypes.data,
+                                               aa.ctypes.data, ba.ctypes.data, len(aa), n_nodes,
+                                               labels.ctypes.data), "dmx_hitgroups_within_host")
     return labels
 
 

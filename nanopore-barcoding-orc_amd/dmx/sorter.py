@@ -8,8 +8,10 @@ on to what update_list (:983-1034) and merge_groups (:1058-1087) make of them, t
 on dmx_pairhits / dmx_hitgroups, without forming the lines.
 comp_consensus_groups() and compare_consensus() restate the two merge loops (:1231-1334,
 :1857-1958) on dmx_rowhits (consensus against consensus, HW, both strands), with
-the first reads of a group in index order where the reference samples at random.  NOT replaced:
-that random sampling, finetune, the species groups (SSG / Estimate) and the .group files.  The
+the first reads of a group in index order where the reference samples at random.
+estimate_ssg() and species_groups() restate SSG (:810-836) and the first half of read_indexes
+(:1363-1411) on dmx_hithist / dmx_pairhits_cross / dmx_hitgroups_within.  NOT
+replaced: that random sampling, finetune and the .group / results files.  The
 random selection modes (-ra, -a) are out of scope.  Alphabet: A, C, G, T, N (a read with any other byte is refused;
 the reference would compare such bytes literally).
 
@@ -755,6 +757,180 @@ def gene_groups(ctx, reads, similar_genes: float = 80.0, minlength: int = 300, m
     return [np.array(members[g], dtype=np.int64) for g in order]
 
 
+N_CLASSES = 1001   # identity classes of the histogram: thousandths, 0.000 .. 1.000
+
+
+def _run_pairhits(ctx, p, q, t, cap_sg, cap_half, n_threads):
+    """pairhits on the plan's batch: (best, hits) with hits the host state, or None on a ctx."""
+    if ctx is not None:
+        ctx.load(p)
+        return ctx.pairhits(q, t, cap_sg, cap_half)[0], None
+    hits = lib.pairhits_host(p, q, t, cap_sg, cap_half, n_threads=n_threads)
+    return hits.best, hits
+
+
+def _identity_table(ln, t, cap_sg):
+    """dmx_hithist's table: per distinct length L of a longer read one row of cap + 1 entries,
+    row[d] = the identity of distance d at L in thousandths, by identity() itself (cap = the
+    hit cap at L: no hit has a larger distance).  Returns (bin_off per read, bins)."""
+    bin_off = np.zeros(len(ln), dtype=np.uint32)
+    rows, at = [], 0
+    lens, first = np.unique(ln[t], return_index=True)
+    for L, k in zip(lens, first):
+        cap = int(cap_sg[k])
+        if cap < 0:
+            continue
+        rows.append(np.array([int(round(identity(d, int(L)) * 1000)) for d in range(cap + 1)],
+                             dtype=np.uint16))
+        bin_off[ln == L] = at
+        at += cap + 1
+    return bin_off, np.concatenate(rows + [np.zeros(0, dtype=np.uint16)])
+
+
+def identity_histogram(ctx, reads, similar_genes: float = 80.0, minlength: int = 300,
+                       maxlength=None, maxreads: int = 10000, allreads: bool = False,
+                       n_threads: int = 16) -> np.ndarray:
+    """How many similarity lines (forward and reverse) of similarity()'s pass carry each
+    identity: hist[k] = the lines with iden == k / 1000, k = 0 .. 1000 (uint64), without the
+    lines: dmx_pairhits, then dmx_hithist over a table of identity() per (length, distance)
+    (DESIGN.md §8k).  ctx: a Context, or None for the host twins."""
+    p, ln, q, t, cap_sg, cap_half = _similarity_plan(reads, similar_genes, minlength, maxlength,
+                                                     maxreads, allreads)
+    if not len(q):
+        return np.zeros(N_CLASSES, dtype=np.uint64)
+    _, hits = _run_pairhits(ctx, p, q, t, cap_sg, cap_half, n_threads)
+    bin_off, bins = _identity_table(ln, t, cap_sg)
+    if ctx is not None:
+        return ctx.hithist(bin_off, bins, N_CLASSES)
+    return lib.hithist_host(hits, bin_off, bins, N_CLASSES)
+
+
+def ssg_from_histogram(hist) -> int:
+    """SSG (:810-836) on the histogram of identities in thousandths, in integers: the total
+    T = sum k * c_k stands for totalsimil = T / 1000, b = int(totalsimil * 0.06) is
+    T * 6 // 100000, and the walk down the identities that occur stops at the first k whose
+    running sum of k * c_k reaches 1000 * b.  Returns int(k / 1000 * 100) in double, as the
+    reference evaluates int(x * 100) (k / 1000 is the double the reference parses from the
+    line).  No line at all (the reference returns None and fails later) raises DmxError."""
+    c = [int(x) for x in np.asarray(hist).reshape(-1)]
+    if not any(c):
+        raise DmxError("estimate_ssg: no similarity line, nothing to estimate the ssg from")
+    total = sum(k * n for k, n in enumerate(c))
+    b = total * 6 // 100000
+    run = 0
+    for k in range(len(c) - 1, -1, -1):
+        if c[k]:
+            run += k * c[k]
+            if run >= 1000 * b:
+                return int((k / 1000) * 100)
+    raise DmxError("estimate_ssg: the histogram's walk did not end")   # run ends at total >= 1000 b
+
+
+def estimate_ssg(ctx, reads, similar_genes: float = 80.0, minlength: int = 300, maxlength=None,
+                 maxreads: int = 10000, allreads: bool = False, n_threads: int = 16) -> int:
+    """The species threshold the reference estimates when -ssg is not given (SSG, :810-836,
+    'N6'): identity_histogram(), then ssg_from_histogram() in exact integer arithmetic.  The
+    reference adds the identities as doubles in the order its workers wrote the lines, so at a
+    razor edge (totalsimil * 0.06 within rounding of an integer, or the running sum within
+    rounding of b) its answer depends on that order and there is no single reference value;
+    away from such an edge both agree.  ctx: a Context, or None for the host twins."""
+    return ssg_from_histogram(identity_histogram(ctx, reads, similar_genes, minlength, maxlength,
+                                                 maxreads, allreads, n_threads))
+
+
+def species_groups(ctx, reads, groups, ssg, similar_genes: float = 80.0, minlength: int = 300,
+                   maxlength=None, maxreads: int = 10000, allreads: bool = False,
+                   n_threads: int = 16) -> list:
+    """The species groups of every gene group: the first half of read_indexes (:1363-1411) for
+    all groups at once.  `groups` are gene groups as gene_groups() /
+    comp_consensus_groups() return them (index arrays into the length-filtered reads, disjoint);
+    `ssg` the species threshold in percent.  Per gene group g the reference takes the similarity
+    lines with iden >= ssg / 100 and at least one read in g, keeps per longer read the best
+    ones (ties kept, as in gene_groups), groups them and keeps the groups of more than 3 reads.
+    Here: one pairhits call; the lines inside a group are filtered and joined on the device
+    (dmx_hitgroups_within), the few lines that leave a group (dmx_pairhits_cross) are filtered
+    in numpy, and a read pulled into a foreign group g enters the graph as a clone node (g, read),
+    so that one components run gives every group's graph.  Returns per gene group the list of
+    its species groups as ascending index arrays, by falling best identity, then smallest
+    member.  No group (the reference's nogroup file) gives no species group.  ctx: a Context, or
+    None for the host twins."""
+    p, ln, q, t, cap_sg, cap_half = _similarity_plan(reads, similar_genes, minlength, maxlength,
+                                                     maxreads, allreads)
+    NONE = lib.LG_NONE
+    n = len(ln)
+    label = np.full(n, NONE, dtype=np.uint32)
+    for k, g in enumerate(groups):
+        g = np.asarray(g, dtype=np.int64).reshape(-1)
+        if len(g) and (int(g.min()) < 0 or int(g.max()) >= n):
+            raise DmxError(f"species_groups: group {k} names a read outside the reads")
+        if (label[g] != NONE).any() or len(np.unique(g)) != len(g):
+            raise DmxError(f"species_groups: group {k} shares a read with another group")
+        label[g] = k
+    out = [[] for _ in groups]
+    if not len(q) or not len(groups):
+        return out
+    best, hits = _run_pairhits(ctx, p, q, t, cap_sg, cap_half, n_threads)
+    thr = float(ssg) / 100
+    cap_of = {int(L): identity_cap(int(L), thr) for L in np.unique(ln)}
+    cap2 = np.array([cap_of[int(L)] for L in ln], dtype=np.int32)
+    # 1. inside its own group a longer read keeps the lines of its global best identity
+    tie2 = np.full(n, NONE, dtype=np.uint32)
+    for r in np.flatnonzero((best != NONE) & (best.astype(np.int64) <= cap2)):
+        tie2[r] = identity_tie(int(best[r]), int(ln[r]))
+    # 2. the lines that leave a group
+    pair, d, _ = (ctx.pairhits_cross(label, cap2) if ctx is not None
+                  else lib.pairhits_cross_host(hits, label, cap2))
+    d = d.astype(np.int64)
+    cq, ct = q[pair].astype(np.int64), t[pair].astype(np.int64)
+    # 3. per line and per valid group of its two reads: (group, read inside, read outside, kept)
+    # the longer read inside: its best is the global one
+    a = label[ct] != NONE
+    keep_a = a & (tie2[ct] != NONE) & (d <= tie2[ct].astype(np.int64))
+    # the longer read outside: its best among the lines whose shorter read is in that group
+    b = np.flatnonzero(label[cq] != NONE)
+    key = label[cq[b]].astype(np.int64) * n + ct[b]
+    _, first, inv = np.unique(key, return_index=True, return_inverse=True)
+    least = np.full(len(first), np.iinfo(np.int64).max)
+    np.minimum.at(least, inv, d[b])
+    tie_b = np.array([identity_tie(int(least[i]), int(ln[ct[b[first[i]]]]))
+                      for i in range(len(first))], dtype=np.int64)
+    keep_b = b[d[b] <= tie_b[inv]]
+    ka = np.flatnonzero(keep_a)
+    grp = np.concatenate([label[ct[ka]], label[cq[keep_b]]]).astype(np.int64)
+    inside = np.concatenate([ct[ka], cq[keep_b]])
+    outside = np.concatenate([cq[ka], ct[keep_b]])
+    line_d = np.concatenate([d[ka], d[keep_b]])
+    line_t = np.concatenate([ct[ka], ct[keep_b]])
+    # 4. one clone node per distinct (group, read outside it)
+    ckey, cidx = np.unique(grp * n + outside, return_inverse=True)
+    clone_read = ckey % n
+    n_nodes = n + len(ckey)
+    xa, xb = inside.astype(np.uint32), (n + cidx).astype(np.uint32)
+    # 5. one components run
+    labels = (ctx.hitgroups_within(tie2, label, xa, xb, n_nodes) if ctx is not None
+              else lib.hitgroups_within_host(hits, tie2, label, xa, xb, n_nodes))
+    node_read = np.concatenate([np.arange(n, dtype=np.int64), clone_read])
+    # the identity a node's kept lines carry (a longer read's lines all carry one identity)
+    iden = np.full(n_nodes, -1.0)
+    for r in np.flatnonzero(tie2 != NONE):
+        iden[r] = identity(int(best[r]), int(ln[r]))
+    for k in range(len(line_d)):
+        node = int(line_t[k]) if label[line_t[k]] == grp[k] else int(n + cidx[k])
+        iden[node] = max(iden[node], identity(int(line_d[k]), int(ln[line_t[k]])))
+    comps = {}
+    for v in np.flatnonzero(labels != NONE):
+        comps.setdefault(int(labels[v]), []).append(int(v))
+    found = [[] for _ in groups]
+    for root, nodes in comps.items():
+        # a component's smallest node is a read of the group: a clone hangs on one
+        members = np.unique(node_read[nodes])
+        if len(members) > 3:
+            found[int(label[root])].append((-float(iden[nodes].max()), int(members[0]), members))
+    for k, f in enumerate(found):
+        out[k] = [m for _, _, m in sorted(f, key=lambda x: x[:2])]
+    return out
+
+
 def read_sequences(path: str) -> list:
     """Every record's sequence of a FASTQ/FASTA(.gz) file, through the native reader."""
     from . import nio
@@ -773,9 +949,10 @@ def main(argv=None) -> int:
                     "bin's reads) on the GPU, and with --groups the gene groups of its best "
                     "hits, with --consensus a consensus per gene group, and with "
                     "--merged-groups the groups after comp_consensus_groups' merge loop "
-                    "(consensuses compared on the GPU, dmx_rowhits); the random sampling, "
-                    "finetune, the species groups and the .group files stay with the "
-                    "reference.")
+                    "(consensuses compared on the GPU, dmx_rowhits), and with "
+                    "--species-groups the species groups of every group at the estimated or "
+                    "given ssg; the random sampling, finetune and the .group / results files "
+                    "stay with the reference.")
     ap.add_argument("-i", "--input", required=True, help="bin in FASTQ/FASTA, optionally .gz")
     ap.add_argument("-o", "--output", default=None,
                     help="similarity lines (i:j:iden[:reverse]); optional with --groups")
@@ -796,6 +973,15 @@ def main(argv=None) -> int:
                          "consensuses compared in HW mode on both strands, groups merged, "
                          "repeated while their number falls; groups of fewer than 6 reads "
                          "dropped), one per line like --groups")
+    ap.add_argument("--species-groups", default=None, metavar="FILE",
+                    help="with --groups: the species groups (more than 3 reads) of every "
+                         "merged group when --merged-groups is given, else of every gene group; "
+                         "first line '# ssg N estimated' or '# ssg N given', then one line per "
+                         "species group: '<group index>:' and the space-separated read indices")
+    ap.add_argument("-ssg", "--similar_species_groups", type=float, default=None, metavar="N",
+                    help="species threshold in percent for --species-groups (default: "
+                         "estimated from the identities of all similarity lines, as the "
+                         "reference's 'Estimate')")
     ap.add_argument("-ldc", "--length_diff_consensus", type=float, default=8.0,
                     help="length difference (%%) allowed between two compared consensuses "
                          "(default 8.0)")
@@ -812,6 +998,8 @@ def main(argv=None) -> int:
         ap.error("--consensus needs --groups")
     if a.merged_groups is not None and a.groups is None:
         ap.error("--merged-groups needs --groups")
+    if a.species_groups is not None and a.groups is None:
+        ap.error("--species-groups needs --groups")
     if a.consensus_reads < 2:
         ap.error("--consensus-reads must be at least 2")
     try:
@@ -848,6 +1036,20 @@ def main(argv=None) -> int:
                         f.write("".join(" ".join(str(int(x)) for x in g) + "\n" for g in merged))
                     print(f"dmx-similarity: {len(merged)} merged groups -> {a.merged_groups}",
                           file=sys.stderr)
+                if a.species_groups is not None:
+                    plan = (a.similar_genes, a.minlength, a.maxlength, a.maxreads, a.allreads)
+                    ssg, how = a.similar_species_groups, "given"
+                    if ssg is None:
+                        ssg, how = estimate_ssg(ctx, reads, *plan), "estimated"
+                        print(f"estimated ssg = {ssg}", file=sys.stderr)
+                    of = merged if a.merged_groups is not None else groups
+                    species = species_groups(ctx, reads, of, ssg, *plan)
+                    with open(a.species_groups, "w") as f:
+                        f.write(f"# ssg {ssg:g} {how}\n")
+                        f.write("".join(f"{k}: " + " ".join(str(int(x)) for x in m) + "\n"
+                                        for k, sp in enumerate(species) for m in sp))
+                    print(f"dmx-similarity: {sum(len(sp) for sp in species)} species groups -> "
+                          f"{a.species_groups}", file=sys.stderr)
     except (DmxError, OSError, ValueError) as e:
         print(f"dmx-similarity: {e}", file=sys.stderr)
         return 1
