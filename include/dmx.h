@@ -113,6 +113,18 @@ int dmx_panel_piece_pairs(const char* const* seqs, const int* lens, int n_adapte
  * panel with out[3] or out[4] > out[5] (DMX_E_UNSUPPORTED, out still filled). */
 int dmx_panel_reach(const char* const* seqs, const int* lens, const int* wheres, int n_adapters,
                     double max_errors, int min_overlap, int flags, int32_t* out, int n_out);
+/* Host only (no GPU; tests): the near-start columns of that panel that only its first adapter
+ * scans.  A 5' panel whose adapters share a suffix S keeps, at the read start, partial matches
+ * that lie wholly inside S; they are the same match for every adapter, and the first adapter
+ * wins ties.  out[0] = the last such column (|S| - out[3]), or -1 where every adapter scans
+ * every column: a 3' or mixed panel, no shared suffix block, |S| <= out[3], acceptance limits
+ * that differ among the adapters for overlaps <= |S|, or DMX_NEAR_ALL=1 in the environment (A/B
+ * and tests).  out[1] = |S| as the filter uses it (0 = off), out[2] = the first column whose
+ * matches contain a whole index block (0 without the index screen), out[3] = the largest
+ * number of errors any match of the panel may have.  n_out >= 4. */
+int dmx_panel_near_shared(const char* const* seqs, const int* lens, const int* wheres,
+                          int n_adapters, double max_errors, int min_overlap, int flags,
+                          int32_t* out, int n_out);
 
 /* Host-side packer (no GPU needed): ASCII reads -> 2-bit codes (A=0,C=1,G=2,T=3, 16 nt per
  * little-endian u32 word) + 1-bit "no-match" mask (any non-ACGT byte, e.g. N).  Reads are laid

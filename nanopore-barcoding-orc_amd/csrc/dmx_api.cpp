@@ -327,6 +327,8 @@ int dmx_open(int device, dmx_ctx** out) {
     c->no_screen = ns && ns[0] == '1';               // window scan
     const char* s1 = std::getenv("DMX_SCREEN_V1");   // A/B: the unpacked index screen
     c->screen_v1 = s1 && s1[0] == '1';
+    const char* na = std::getenv("DMX_NEAR_ALL");    // A/B: near pieces scan every column for
+    c->near_all = na && na[0] == '1';                // every adapter (DevPanel::near_shared = -1)
     if (hipSetDevice(device) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
@@ -553,8 +555,8 @@ static void build_pieces(const Ctx* c, const char* const* seqs, const int* lens,
 }
 
 // The host and device forms of a panel (parser.py / adapters.py rules above), the filter /
-// verification / screen blocks and the reach check; uses only c->err, c->no_filter, c->no_verify
-// (dmx_panel_reach runs it on a context that was never opened).
+// verification / screen blocks and the reach check; uses only c->err, c->no_filter, c->no_verify,
+// c->no_pieces, c->near_all (dmx_panel_reach runs it on a context that was never opened).
 static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const int* wheres, int n,
                        double max_errors, int min_overlap, int flags, HostPanel& hp,
                        DevPanel& dp) {
@@ -645,6 +647,7 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
     dp.where = hp.ad[0].where;
     for (int a = 1; a < n; ++a)
         if (hp.ad[a].where != hp.ad[0].where) dp.where = 0;
+    dp.near_shared = -1;
     // Shared-suffix filter block: the longest suffix common to every adapter (<= 32 chars).
     int common = lens[0];
     for (int a = 1; a < n; ++a) {
@@ -706,6 +709,25 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
             reach = std::max(reach, (int)hp.ad[a].m + std::max((int)hp.ad[a].k + 1, 7));
         reach = (reach + 15) / 16 * 16;
         dp.clean_reach = reach <= 128 && !std::getenv("DMX_NO_CLEAN") ? reach : 0;
+        // Near-start cells inside the shared suffix.  A FRONT last-row cell
+        // (m_a, j) of cost d <= kk_a with j + kf <= flen < m_a: every alignment of that cost ending
+        // there starts at column 0 and covers at most j + d <= flen rows, the last rows of the
+        // adapter, all of them rows of S (a start in row 0 needs j >= m_a - d).  D, the band's
+        // score and its aligned length are then the same for every adapter, and the acceptance
+        // lookups pacc[min(m, j + d)], acc[j - d], acc[rows] stay at indices <= flen.  Where the
+        // tables agree there, every adapter accepts the cell alike and the lowest index wins the
+        // slot (make_key_o): adapters > 0 skip the columns j <= near_shared of a near piece.
+        {
+            const int js = flen - kf;
+            bool same = dp.where == kFront && js >= 1 && !c->near_all;
+            for (int a = 0; a < n && same; ++a) {
+                same &= lens[a] > flen;
+                for (int L = 0; L <= flen; ++L)
+                    same &= hp.ad[a].acc[L] == hp.ad[0].acc[L] &&
+                            hp.ad[a].pacc[L] == hp.ad[0].pacc[L];
+            }
+            if (same) dp.near_shared = js;
+        }
 
         // shared prefix for the verification pass
         int pre = lens[0];
@@ -991,6 +1013,32 @@ int dmx_panel_reach(const char* const* seqs, const int* lens, const int* wheres,
     const int32_t v[6] = {r.pre_raw, r.pre, r.post, r.need_pre, r.need_post, kGuardNt};
     for (int i = 0; i < 6; ++i) out[i] = v[i];
     return rc;
+}
+
+int dmx_panel_near_shared(const char* const* seqs, const int* lens, const int* wheres, int n,
+                          double max_errors, int min_overlap, int flags, int32_t* out, int n_out) {
+    if (!out || n_out < 4) return DMX_E_INVALID;
+    if (wheres) {   // dmx_set_panel_mixed's form
+        for (int a = 0; a < n; ++a)
+            if (wheres[a] != DMX_FRONT && wheres[a] != DMX_BACK) return DMX_E_INVALID;
+        flags = DMX_FRONT | (flags & DMX_RC);
+    }
+    Ctx tmp;   // never opened, as in dmx_panel_reach
+    const char* nf = std::getenv("DMX_NO_FILTER");
+    tmp.no_filter = nf && nf[0] == '1';
+    const char* nv = std::getenv("DMX_NO_VERIFY");
+    tmp.no_verify = nv && nv[0] == '1';
+    const char* na = std::getenv("DMX_NEAR_ALL");
+    tmp.near_all = na && na[0] == '1';
+    HostPanel hp;
+    DevPanel dp;
+    const int rc = build_panel(&tmp, seqs, lens, wheres, n, max_errors, min_overlap, flags, hp, dp);
+    if (rc != DMX_OK) return rc;
+    int kk = -1;
+    for (int a = 0; a < n; ++a) kk = std::max(kk, (int)hp.ad[a].kk);
+    const int32_t v[4] = {dp.near_shared, dp.filter_len, dp.jsplit, kk};
+    for (int i = 0; i < 4; ++i) out[i] = v[i];
+    return DMX_OK;
 }
 
 int dmx_debug_bounds_selftest(dmx_ctx* c, uint32_t* out3) {

@@ -82,9 +82,18 @@ struct DevPanel {
     int32_t jsplit;      // FRONT: a last-row cell at column j >= jsplit contains every row of I_a
     int32_t pshared;     // acceptance tables agree on rows <= pre_len for every adapter, so a
                          // 3' last-column cell inside P is identical for all adapters
+    // FRONT: a last-row cell at column j <= near_shared = filter_len - kf lies inside the shared
+    // suffix with every alignment of cost <= kf that ends there, and the acceptance tables agree
+    // on lengths <= filter_len, so it is the same cell for every adapter and the lowest index
+    // wins it: only adapter 0 scans those columns of a near piece.  -1 = every adapter does
+    int32_t near_shared;
+    int32_t pad0;
     uint32_t pre_peq[8];
     DevAdapter ad[kMaxAdapters];
 };
+static_assert(offsetof(DevPanel, pre_peq) == 168 && offsetof(DevPanel, ad) == 200 &&
+                  sizeof(DevPanel) == 200 + kMaxAdapters * sizeof(DevAdapter),
+              "DevPanel layout");
 
 // A column range of one (item, orientation) that the per-adapter window scan must cover.
 // info (set by verify, read by the index screen): bits 0-7 = a lower bound of the shared-prefix

@@ -164,6 +164,7 @@ struct Ctx {
     size_t cells_words = 0;
     bool no_screen = false;              // DMX_NO_SCREEN=1: every window runs every adapter
     bool screen_v1 = false;              // DMX_SCREEN_V1=1: one lane per (window, adapter) screen
+    bool near_all = false;               // DMX_NEAR_ALL=1: near pieces keep every adapter's columns
     size_t n_counts = 0;
     hipEvent_t ev[17] = {};   // [3r..3r+2] round r stages, [6+r] finalize, [8] start,
                               // [9+2r] after filter, [10+2r] after verify, [13+r] after screen,

@@ -2725,6 +2725,7 @@ __global__ __launch_bounds__(kScanBlock) void iscreen_kernel(RoundArgs R) {
     const uint32_t total = nwin * (uint32_t)A;    // host: win_cap * A < 2^32
     const bool front = P->where == kFront;
     const int jsplit = front ? P->jsplit : 0;
+    const int near_sh = front ? P->near_shared : -1;
     const bool pshared = P->pshared != 0;
 
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -2741,10 +2742,12 @@ __global__ __launch_bounds__(kScanBlock) void iscreen_kernel(RoundArgs R) {
             const int dP = (int)(w.info & 255u), dPe = (int)((w.info >> 8) & 255u);
             const int dPn = (int)(w.info >> 24);
             const bool lastc = !front && w.lastcol;
-            // the near piece [j1, min(j2, jsplit - 1)] keeps every adapter
+            // the near piece [j1, min(j2, jsplit - 1)] keeps every adapter; its columns
+            // j <= near_shared are adapter 0's alone (DevPanel::near_shared)
             if (j1 < jsplit) {
                 const int jh = min(j2, jsplit - 1);
-                st.push(make_task(w, (uint32_t)j1, (uint32_t)jh, false, a));
+                const int jl = a == 0 ? j1 : max(j1, near_sh + 1);
+                if (jl <= jh) st.push(make_task(w, (uint32_t)jl, (uint32_t)jh, false, a));
             }
             const int jr = max(j1, jsplit);               // far piece: last-row cells [jr, j2]
             const int thr = kk - bm - dP;                 // (bm = 255: no hit column, no rows)
@@ -3129,6 +3132,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
     const uint32_t total = nwin * (uint32_t)Q;
     const bool front = P->where == kFront;
     const int jsplit = front ? P->jsplit : 0;
+    const int near_sh = front ? P->near_shared : -1;
     const bool pshared = P->pshared != 0;
 
     // FRONT panels: a wave costs its longest lane, and near pieces (no scan) and wide windows
@@ -3192,7 +3196,10 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
             const int dPn = (int)(w.info >> 24);
             const bool lastc = !front && w.lastcol;
             const uint32_t valid = A - 4 * q >= 4 ? 0xFu : ((1u << (A - 4 * q)) - 1u);
-            if (j1 < jsplit) near_m = valid;                 // the near piece keeps every adapter
+            // the near piece keeps every adapter; its columns j <= near_shared are adapter 0's
+            // alone (DevPanel::near_shared), so a piece that ends there is one task
+            if (j1 < jsplit)
+                near_m = min(j2, jsplit - 1) > near_sh ? valid : (q == 0 ? 1u : 0u);
             const int jr = max(j1, jsplit);
             const bool rows_base = bm != 255 && jr <= j2;
             // per adapter: thresholds, first column of the band, which tests apply
@@ -3366,7 +3373,8 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
             __builtin_amdgcn_wave_barrier();
             if (st.count() > kScreenCap - 64) st.flush();
             if ((near_m >> k) & 1u)
-                st.push(make_task(w, w.j1, (uint32_t)min((int)w.j2, jsplit - 1), false, 4 * q + k));
+                st.push(make_task(w, 4 * q + k == 0 ? w.j1 : max(w.j1, (uint32_t)(near_sh + 1)),
+                                  (uint32_t)min((int)w.j2, jsplit - 1), false, 4 * q + k));
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {

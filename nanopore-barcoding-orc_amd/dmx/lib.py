@@ -49,7 +49,7 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_hitgroups_host", "dmx_hitgroups_stats", "dmx_rowpairdist", "dmx_rowpairdist_host",
            "dmx_rowhits", "dmx_rowhits_host", "dmx_panel_piece_pairs", "dmx_hithist",
            "dmx_pairhits_cross", "dmx_hitgroups_within", "dmx_hithist_host",
-           "dmx_pairhits_cross_host", "dmx_hitgroups_within_host"]
+           "dmx_pairhits_cross_host", "dmx_hitgroups_within_host", "dmx_panel_near_shared"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -150,6 +150,8 @@ def load() -> ctypes.CDLL:
         L.dmx_panel_reach.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_int), P,
                                       c_int, ctypes.c_double, c_int, c_int, P, c_int]
         L.dmx_debug_bounds_selftest.argtypes = [P, P]
+    if hasattr(L, "dmx_panel_near_shared"):
+        L.dmx_panel_near_shared.argtypes = L.dmx_panel_reach.argtypes
     if hasattr(L, "dmx_panel_pieces"):
         L.dmx_panel_pieces.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_int),
                                        c_int, ctypes.c_double, c_int, c_int, P, c_int, P, c_int]
@@ -1194,6 +1196,20 @@ def panel_reach(seqs, flags: int, max_errors: float = 0.1, min_overlap: int = 3,
                            int(flags), out.ctypes.data, 6)
     return rc, dict(zip(["pre_raw", "pre", "post", "need_pre", "need_post", "guard"],
                         out.tolist()))
+
+
+def panel_near_shared(seqs, flags: int, max_errors: float = 0.1, min_overlap: int = 3,
+                      wheres=None):
+    """Host only: (status, info) of the near-start columns that only the first adapter of the
+    panel dmx_set_panel would build scans (include/dmx.h dmx_panel_near_shared)."""
+    L = load()
+    arr = (ctypes.c_char_p * len(seqs))(*[s.encode("ascii") for s in seqs])
+    lens = (ctypes.c_int * len(seqs))(*[len(s) for s in seqs])
+    wh = (ctypes.c_int * len(seqs))(*wheres) if wheres is not None else None
+    out = np.zeros(4, dtype=np.int32)
+    rc = L.dmx_panel_near_shared(arr, lens, wh, len(seqs), float(max_errors), int(min_overlap),
+                                 int(flags), out.ctypes.data, 4)
+    return rc, dict(zip(["near_shared", "filter_len", "jsplit", "kk"], out.tolist()))
 
 
 PIECE_FIELDS = ["step", "pieces", "keys", "entries", "front_reach", "part_max", "lo_off",
