@@ -506,6 +506,68 @@ int dmx_rowdist_host(const uint32_t* seq2b, const uint32_t* nmask, const uint64_
                      const uint32_t* caps, size_t n_pairs, uint32_t* out, int n_threads);
 float dmx_rowdist_ms(dmx_ctx* ctx);  /* device time of the last dmx_rowdist (HIP events) */
 
+/* ---- Reads assigned to rows of masks: the best row per read ---------------------
+ * One pass of process_consensuslist() / similarity_species() and the best-hit filter of
+ * update_groups() (amplicon_sorter.py:1628-1755) with the pair generation, the decision and the
+ * reduction inside the call: one record per read leaves it, not a distance per pair.
+ * Rows: dmx_rowdist's (n_rows, masks, row_off; the same equality; bits 5..7 refused).
+ * Reads: reads[0 .. n_sel), resident read indices in the caller's order.  A read may be named
+ * twice; each place k is an entry of its own.
+ * Tables indexed by the longer length L = max(length of the read, length of the row), n_len
+ * entries each: cap_hit[L], cap_half[L] (-1 = none; below -1 is refused) and bin_off[L]; the
+ * identity class of distance d at length L is bins[bin_off[L] + d] (n_bins entries), as
+ * dmx_hithist takes them.
+ * Pairs: for k ascending and row g ascending, pair (k, g) is compared unless
+ * (double)la * 1.05 < (double)lb || (double)lb * 1.05 < (double)la, with la the read's and lb
+ * the row's length (:1664; the same IEEE products as Python's).  After the last row of place k,
+ * if floor(pairs so far / chunk) == max_chunks, no later place is compared (:1669-1676).  The
+ * test is for equality: a place that takes the quotient past max_chunks does not stop anything,
+ * as in the reference.
+ * Per pair: df = the NW distance of the read against the row, capped at
+ * max(cap_hit[L], cap_half[L], 0).  df <= cap_hit[L] is a forward line with d = df.  Otherwise,
+ * when cap_hit[L] >= 0 and df > cap_half[L], dr = the distance against the row's reverse
+ * complement (the row backwards, bits A <-> T and C <-> G swapped, N and gap columns fixed:
+ * dmx_rowpairdist's definition), capped at cap_hit[L]; dr <= cap_hit[L] is a reverse line with
+ * d = dr.  Otherwise the pair has no line.
+ * Best per place: among the lines of place k the one with the largest (class, g): the largest
+ * identity class, and among equal classes the largest row index (update_groups' "the last of
+ * equal identities wins", in pair-generation order).
+ * Out: best_row[k] (DMX_LG_NONE where place k has no line; best_d and best_class are then
+ * DMX_LG_NONE and 0), best_d[k] (d, or d | DMX_LG_REV), best_class[k]; *n_pairs = the pairs
+ * compared (the reference's "comparisons to calculate"), *n_lines = the lines.
+ * Everything is checked on the host before anything is launched, naming the place, row or
+ * length: DMX_E_INVALID for a null argument, chunk == 0, a read outside the batch, decreasing
+ * offsets, a mask byte with bits 5..7 set, a cap below -1, L >= n_len for a pair that occurs,
+ * bin_off[L] + max(cap_hit[L], 0) >= n_bins for a length that occurs; DMX_E_UNSUPPORTED for a
+ * compared read or row of 0 or more than DMX_PD_MAX_LEN entries, more than 2^31 rows (the key
+ * below holds 31 bits of row) and more than DMX_LG_MAX_PAIRS pairs.  A refused call launches
+ * nothing, leaves the outputs untouched, dmx_rowassign_ms at 0 and the context usable.
+ * n_sel == 0 or n_rows == 0 is a valid call that launches nothing (*n_pairs = *n_lines = 0).
+ * Device: the rows are uploaded once per call and their reverse complements written beside them
+ * on the device when some pair asks for one; the distances are dmx_rowdist's launches (chunks of
+ * DMX_PD_CHUNK pairs) and stay on the device; per chunk a decision kernel does one 64-bit
+ * atomicMax per line on the place's key (class, g, reverse bit, d) and only a bitmap of the pairs
+ * to retry comes back; the retries run as launches of their own.  The result depends neither on
+ * the order the atomics land in nor on DMX_PD_CHUNK.  The call leaves the resident batch and the
+ * outcomes of dmx_pairhits as they are.  Synchronous. */
+int dmx_rowassign(dmx_ctx* ctx, size_t n_rows, const uint8_t* masks, const uint64_t* row_off,
+                  const uint32_t* reads, size_t n_sel, const int32_t* cap_hit,
+                  const int32_t* cap_half, const uint32_t* bin_off, size_t n_len,
+                  const uint16_t* bins, size_t n_bins, uint64_t chunk, uint64_t max_chunks,
+                  uint32_t* best_row, uint32_t* best_d, uint16_t* best_class, uint64_t* n_pairs,
+                  uint64_t* n_lines);
+/* Host only (no GPU; tests, ctx=None of dmx.sorter.assign_best): the same contract on a dmx_pack
+ * layout, on dmx_rowdist_host (full-matrix DP, n_threads) with the decision and the reduction in
+ * plain sequential C++.  Errors: dmx_last_error(NULL). */
+int dmx_rowassign_host(const uint32_t* seq2b, const uint32_t* nmask, const uint64_t* offsets,
+                       const uint32_t* lens, size_t n_reads, size_t n_rows, const uint8_t* masks,
+                       const uint64_t* row_off, const uint32_t* reads, size_t n_sel,
+                       const int32_t* cap_hit, const int32_t* cap_half, const uint32_t* bin_off,
+                       size_t n_len, const uint16_t* bins, size_t n_bins, uint64_t chunk,
+                       uint64_t max_chunks, uint32_t* best_row, uint32_t* best_d,
+                       uint16_t* best_class, uint64_t* n_pairs, uint64_t* n_lines, int n_threads);
+float dmx_rowassign_ms(dmx_ctx* ctx);  /* device time of the last dmx_rowassign (HIP events) */
+
 /* ---- Gene groups: best-hit links and their connected components -----------------
  * Replaces: what update_list() of amplicon_sorter.py does with the similarity lines (:983-1034:
  * per longer read j the lines of the largest identity, ties kept; then greedy groups) and

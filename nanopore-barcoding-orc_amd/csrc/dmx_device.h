@@ -370,14 +370,15 @@ enum BoundsBuf : uint32_t {
     kBufSeq = 1, kBufMask = 2, kBufSlot = 3, kBufItem = 4, kBufRes = 5, kBufCount = 6,
     kBufRead = 7, kBufLinked = 8, kBufCand = 9, kBufChop = 10, kBufPd = 11,
     kBufPaTrace = 12, kBufPaOps = 13, kBufGaCols = 14, kBufRdCols = 15, kBufRrCols = 16,
-    kBufHistBins = 17
+    kBufHistBins = 17, kBufRaCols = 18, kBufRaTable = 19, kBufRaBest = 20
 };
 enum BoundsKernel : int32_t {
     kKerFilter = 1, kKerVerify, kKerScreen, kKerScreen4, kKerWscan, kKerScan, kKerBand0,
     kKerBand1, kKerResolve, kKerSelect, kKerFin0, kKerFin1, kKerFin0L, kKerFin1L,
     kKerFin2L, kKerChop, kKerChopBig, kKerChopStart, kKerSelfTest, kKerPieces, kKerPairdist,
     kKerPairalign, kKerPairalignTb, kKerGroupalign, kKerGroupalignTb, kKerGroupalignMerge,
-    kKerRowdist, kKerRowpair, kKerRowpairRc, kKerHithist
+    kKerRowdist, kKerRowpair, kKerRowpairRc, kKerHithist, kKerRowassign,
+    kKerRowassignDecide, kKerRowassignFinish
 };
 constexpr int kBoundsRec = 24;     // d_counters[24..27]: kernel id + 1, buffer, index lo / hi
 

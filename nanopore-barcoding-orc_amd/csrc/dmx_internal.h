@@ -19,6 +19,7 @@ struct PaState;     // pairwise alignment with edit path (dmx_pairdist.hip)
 struct GaState;     // progressive alignment of read groups (dmx_pairdist.hip)
 struct RdState;     // read distance against rows of masks (dmx_pairdist.hip)
 struct RrState;     // distance between rows of masks, their hits (dmx_pairdist.hip)
+struct RaState;     // reads assigned to rows of masks, best row per read (dmx_pairdist.hip)
 struct LgState;     // hits of dmx_pairhits, link groups (dmx_groups.hip)
 
 // A device buffer that grows on demand, never shrinks, and is freed with its owner.
@@ -176,6 +177,7 @@ struct Ctx {
     GaState* ga = nullptr;       // dmx_groupalign buffers, created by its first call
     RdState* rd = nullptr;       // dmx_rowdist buffers, created by its first call
     RrState* rr = nullptr;       // dmx_rowpairdist / dmx_rowhits buffers, created by the first call
+    RaState* ra = nullptr;       // dmx_rowassign buffers, created by its first call
     LgState* lg = nullptr;       // dmx_pairhits' outcomes and the link-group buffers
 
     // RCCL communicator for the per-bin count exchange (dmx_comm.cpp)

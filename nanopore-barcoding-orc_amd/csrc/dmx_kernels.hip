@@ -4626,12 +4626,15 @@ int bounds_check(Ctx* c, const char* where) {
         "bounds_selftest_kernel", "pscreen_kernel", "pairdist_kernel", "pairalign_kernel",
         "pairalign_traceback_kernel", "groupalign_kernel", "groupalign_traceback_kernel",
         "groupalign_merge_kernel", "rowdist_kernel", "rowpair_kernel", "rowpair_rc_kernel",
-        "lg_hist_kernel"};
+        "lg_hist_kernel", "rowassign_kernel", "rowassign_decide_kernel",
+        "rowassign_finish_kernel"};
     static const char* const kBuf[] = {"?", "seq", "nmask", "winner slots", "items", "results",
                                        "counts", "reads", "linked keys", "candidates", "chop",
                                        "pairdist scratch", "pairalign trace", "pairalign ops",
                                        "groupalign columns", "rowdist columns",
-                                       "rowpair columns", "identity table"};
+                                       "rowpair columns", "identity table",
+                                       "rowassign columns", "rowassign tables",
+                                       "rowassign places"};
     uint32_t rec[4];
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess)

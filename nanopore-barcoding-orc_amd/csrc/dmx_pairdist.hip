@@ -99,6 +99,14 @@ struct RrPair : PdPair {
     uint32_t pad;
 };
 static_assert(sizeof(RrPair) == 56, "the row-pair form uploads 56 bytes per pair");
+// dmx_rowassign's record: dmx_rowdist's, and the place in the call's read list whose best line
+// the pair may become (the decision kernel reads it; the forward pass does not).
+struct RaPair : PdPair {
+    uint64_t row;                // first column of the row in the device mask array
+    uint32_t n;                  // the row's length
+    uint32_t k;                  // the place of PdPair::q in the call's reads
+};
+static_assert(sizeof(RaPair) == 40, "the assign form uploads 40 bytes per pair");
 struct PdWave {
     uint32_t first, count, G, steps;   // pairs[first .. first + count), one group of G lanes each
 };
@@ -157,6 +165,14 @@ struct RdArgs : PdHead<RdPair> {
     const uint8_t* mask;         // per column: the equality mask, every row padded to 16 columns
     uint64_t cols;               // columns of mask
     uint32_t* out;               // per pair: the distance
+};
+
+// dmx_rowassign: dmx_rowdist's arguments over its own record.  out is indexed by
+// the pair's place in the launch, where the decision kernel finds it beside the record.
+struct RaArgs : PdHead<RaPair> {
+    const uint8_t* mask;         // the rows, then their reverse complements when a pair retries
+    uint64_t cols;               // columns of mask
+    uint32_t* out;               // per pair of the launch: the distance
 };
 
 // dmx_rowpairdist / dmx_rowhits: the distance form's arguments with the mode, and the call's rows
@@ -225,6 +241,19 @@ struct RrState : PdBufs<RrPair> {   // DESIGN.md §8j; PdBufs::out holds the who
     DevBuf<int32_t> cap;         // dmx_rowhits: the caller's caps
     float ms = 0.f;
 };
+struct RaState : PdBufs<RaPair> {   // DESIGN.md §8l; PdBufs::out holds one launch's distances
+    DevBuf<uint8_t> mask;        // the rows of the last call, then their reverse complements
+    DevBuf<RrRow> rows;          // the uploaded rows (rowpair_rc_kernel)
+    DevBuf<int32_t> cap_hit, cap_half;   // the caller's tables, by the longer length
+    DevBuf<uint32_t> bin_off;
+    DevBuf<uint16_t> bins;
+    DevBuf<unsigned long long> best;     // per place: the key of its best line, 0 = none
+    DevBuf<unsigned long long> cnt;      // lines
+    DevBuf<uint32_t> need;       // per launch: the retry bitmap
+    DevBuf<uint32_t> o_row, o_d; // per place: what the finish kernel unpacks
+    DevBuf<uint16_t> o_class;
+    float ms = 0.f;
+};
 
 void pd_release(Ctx* c) {
     delete c->pd;
@@ -232,6 +261,8 @@ void pd_release(Ctx* c) {
     delete c->ga;
     delete c->rd;
     delete c->rr;
+    delete c->ra;
+    c->ra = nullptr;
     c->pd = nullptr;
     c->pa = nullptr;
     c->ga = nullptr;
@@ -333,7 +364,7 @@ __device__ __forceinline__ void pd_masks_row(const Bounds& bd, const uint8_t* ma
 // row, dmx_rowdist's and dmx_rowpairdist's given row).
 template <class Pair>
 constexpr bool kPdRowPair = std::is_same<Pair, GaPair>::value || std::is_same<Pair, RdPair>::value ||
-                            std::is_same<Pair, RrPair>::value;
+                            std::is_same<Pair, RrPair>::value || std::is_same<Pair, RaPair>::value;
 template <class Pair>
 __device__ __forceinline__ bool pd_target_ok(const Bounds& bd, const Pair& P) {
     if constexpr (kPdRowPair<Pair>) return true;   // P.t is a group or a row, not a read
@@ -377,12 +408,14 @@ __device__ __forceinline__ uint64_t pd_target_off(const uint64_t* offs, const Pa
 // they are (compare the assembly of all of them before and after).
 template <class Args>
 __device__ __forceinline__ void pd_forward(const Args& A) {
-    constexpr bool kRd = std::is_same<Args, RdArgs>::value;
+    constexpr bool kRa = std::is_same<Args, RaArgs>::value;      // RdArgs over its own record
+    constexpr bool kRd = std::is_same<Args, RdArgs>::value || kRa;
     constexpr bool kRr = std::is_same<Args, RrArgs>::value;
     constexpr bool kGa = std::is_base_of<GaArgs, Args>::value;   // GaArgs or GaStrandArgs
     constexpr bool kRow = kGa || kRd || kRr;
     constexpr bool kTrace = std::is_same<Args, PaArgs>::value || kGa;
-    constexpr uint32_t kColsBuf = kRr ? kBufRrCols : kRd ? kBufRdCols : kBufGaCols;
+    constexpr uint32_t kColsBuf = kRr ? kBufRrCols : kRa ? kBufRaCols : kRd ? kBufRdCols
+                                                                          : kBufGaCols;
     const uint32_t wave = blockIdx.x * kPdWavesPerBlock + (threadIdx.x >> 6);
     if (wave >= A.n_waves) return;   // whole waves leave: the shift below sees full waves
     const uint32_t lane = threadIdx.x & 63u;
@@ -557,6 +590,7 @@ __global__ __launch_bounds__(64 * kPdWavesPerBlock) void groupalign_strands_kern
     pd_forward(A);
 }
 __global__ __launch_bounds__(64 * kPdWavesPerBlock) void rowpair_kernel(RrArgs A) { pd_forward(A); }
+__global__ __launch_bounds__(64 * kPdWavesPerBlock) void rowassign_kernel(RaArgs A) { pd_forward(A); }
 
 // The reverse complement of every uploaded row, written `half` columns after the row itself (the
 // second half of the mask array, padded as the first): column i of the copy is the complement
@@ -608,6 +642,91 @@ __global__ __launch_bounds__(kRrRcBlock) void rowhits_decide_kernel(RrDecide A) 
     const uint32_t d = rev ? dr : df;
     const int32_t cap = A.cap[i];
     A.outc[i] = (cap >= 0 && d <= (uint32_t)cap) ? (d | (rev ? DMX_LG_REV : 0u)) : DMX_LG_NONE;
+}
+
+// dmx_rowassign's decision on one launch's distances.  The key of a line orders
+// the lines of a place as update_groups does in pair-generation order, the largest wins:
+//   bit 63      set (0 is "no line": the places start there)
+//   bits 47..62 the identity class of d at the pair's longer length L (the caller's table)
+//   bits 16..46 the row
+//   bit 15      the reverse bit
+//   bits 0..14  d (<= DMX_PD_MAX_LEN = 2^14)
+// A pair makes at most one line and a place meets a row once, so no two lines of a place agree
+// in (class, row): the maximum does not depend on the order the atomics land in, nor on which
+// launch a pair fell into.  Pass 0 (forward): d is clamped at max(cap_hit, cap_half, 0) + 1, so it
+// compares against both caps as the exact distance would; d <= cap_hit is a line, otherwise
+// cap_hit >= 0 and d > cap_half sets the pair's bit in `need`.  Pass 1 (the retries against the
+// reversed rows, clamped at cap_hit + 1): d <= cap_hit is a line with the reverse bit.
+constexpr int kRaClassShift = 47, kRaRowShift = 16;
+constexpr uint64_t kRaRowMax = 1ull << 31;   // rows a key holds
+constexpr uint64_t kRaValid = 1ull << 63;
+constexpr uint32_t kRaRevBit = 1u << 15, kRaDistMask = kRaRevBit - 1u;
+static_assert(DMX_PD_MAX_LEN <= kRaDistMask, "a distance must fit below the reverse bit");
+struct RaDecide {
+    Bounds bd;
+    const RaPair* pairs;         // the launch's records, in the order they ran
+    const uint32_t* dist;        // their distances
+    const uint32_t* lens;        // the resident reads' lengths
+    uint32_t np, pass;
+    const int32_t* cap_hit;
+    const int32_t* cap_half;
+    const uint32_t* bin_off;
+    const uint16_t* bins;
+    uint32_t n_len, n_sel;
+    uint64_t n_bins;
+    unsigned long long* best;
+    uint32_t* need;
+    uint32_t need_words;
+    unsigned long long* cnt;
+};
+__global__ __launch_bounds__(kRrRcBlock) void rowassign_decide_kernel(RaDecide A) {
+    const uint32_t i = blockIdx.x * kRrRcBlock + threadIdx.x;
+    bool line = false;
+    if (i < A.np) {
+        const RaPair P = A.pairs[i];
+        if (DMX_BOUND(A.bd, reads, P.q, kBufRead)) {
+            const uint32_t L = max(A.lens[P.q], P.n);
+            if (L < A.n_len && bchk(A.bd, (int64_t)L, 0, (int64_t)A.n_len, kBufRaTable)) {
+                const int64_t d = A.dist[i], ch = A.cap_hit[L], chalf = A.cap_half[L];
+                const bool hit = d <= ch;
+                if (A.pass == 0 && !hit && ch >= 0 && d > chalf) {
+                    if ((i >> 5) < A.need_words) atomicOr(&A.need[i >> 5], 1u << (i & 31u));
+                }
+                const uint64_t at = (uint64_t)A.bin_off[L] + (uint64_t)d;
+                if (hit && at < A.n_bins && P.k < A.n_sel &&
+                    bchk(A.bd, (int64_t)at, 0, (int64_t)A.n_bins, kBufRaTable) &&
+                    bchk(A.bd, (int64_t)P.k, 0, (int64_t)A.n_sel, kBufRaBest)) {
+                    const uint64_t key = kRaValid | ((uint64_t)A.bins[at] << kRaClassShift) |
+                                         ((uint64_t)P.t << kRaRowShift) |
+                                         (A.pass ? kRaRevBit : 0u) | ((uint32_t)d & kRaDistMask);
+                    atomicMax(&A.best[P.k], (unsigned long long)key);
+                    line = true;
+                }
+            }
+        }
+    }
+    const uint64_t bal = __ballot(line);   // every lane of the wave is here
+    if ((threadIdx.x & 63u) == 0 && bal) atomicAdd(A.cnt, (unsigned long long)__popcll(bal));
+}
+
+// The keys unpacked into the call's three outputs, one place per lane.
+struct RaFinish {
+    Bounds bd;
+    const unsigned long long* best;
+    uint32_t n_sel;
+    uint32_t* row;
+    uint32_t* d;
+    uint16_t* cls;
+};
+__global__ __launch_bounds__(kRrRcBlock) void rowassign_finish_kernel(RaFinish A) {
+    const uint32_t k = blockIdx.x * kRrRcBlock + threadIdx.x;
+    if (k >= A.n_sel || !bchk(A.bd, (int64_t)k, 0, (int64_t)A.n_sel, kBufRaBest)) return;
+    const uint64_t key = A.best[k];
+    const bool has = (key & kRaValid) != 0;
+    const uint32_t lo = (uint32_t)key;
+    A.row[k] = has ? (uint32_t)((key >> kRaRowShift) & (kRaRowMax - 1ull)) : DMX_LG_NONE;
+    A.d[k] = has ? ((lo & kRaDistMask) | ((lo & kRaRevBit) ? DMX_LG_REV : 0u)) : DMX_LG_NONE;
+    A.cls[k] = has ? (uint16_t)((key >> kRaClassShift) & 0xFFFFu) : (uint16_t)0;
 }
 
 // dmx_pairalign's traceback: one lane per pair walks back from (m, n), preferring up (INSERT),
@@ -2334,4 +2453,409 @@ extern "C" int dmx_rowhits(dmx_ctx* c, int mode, size_t n_rows, const uint8_t* m
                                        &ms_compact);
     if (rc == DMX_OK || rc == DMX_E_INVALID) s->ms = ms + ms_decide + ms_compact;
     return rc;
+}
+
+// ---- dmx_rowassign: the best row per read, decided on the device ----------------
+
+namespace {
+
+// The call's pairs in generation order: place[i] in the read list, row[i], and the pair's longer
+// length.  Filled by ra_prepare after every check has passed.
+struct RaPairs {
+    std::vector<uint32_t> place, row, q, tn, L;
+    std::vector<uint32_t> rowlen;   // per row of the call, clamped at DMX_PD_MAX_LEN + 1
+};
+
+// Every argument check of both entry points, then the pair generation: the 5 % rule with the
+// reference's double products (:1664) and the stop after the place at whose end max_chunks full
+// chunks have been made (:1669-1676; equality, tested once per place).  Names the place, row or
+// length.  0, or the code with *err set.
+int ra_prepare(const char* who, const uint32_t* lens, size_t n_reads, size_t n_rows,
+               const uint8_t* masks, const uint64_t* row_off, const uint32_t* reads, size_t n_sel,
+               const int32_t* cap_hit, const int32_t* cap_half, const uint32_t* bin_off,
+               size_t n_len, size_t n_bins, uint64_t chunk, uint64_t max_chunks, RaPairs& ps,
+               std::string* err) {
+    const std::string name = std::string(who) + ": ";
+    if (!chunk) {
+        *err = name + "chunk must be at least 1";
+        return DMX_E_INVALID;
+    }
+    if (n_rows > kRaRowMax) {
+        *err = name + "at most " + std::to_string(kRaRowMax) + " rows supported";
+        return DMX_E_UNSUPPORTED;
+    }
+    ps.rowlen.assign(n_rows, 0);
+    for (size_t g = 0; g < n_rows; ++g) {
+        if (row_off[g + 1] < row_off[g]) {
+            *err = name + "row " + std::to_string(g) + ": offsets must not decrease";
+            return DMX_E_INVALID;
+        }
+        for (uint64_t x = row_off[g]; x < row_off[g + 1]; ++x)
+            if (masks[x] & 0xE0u) {
+                *err = name + "row " + std::to_string(g) + ": column " +
+                       std::to_string(x - row_off[g]) + " has a mask bit above the five symbols";
+                return DMX_E_INVALID;
+            }
+        ps.rowlen[g] = (uint32_t)std::min<uint64_t>(row_off[g + 1] - row_off[g], DMX_PD_MAX_LEN + 1u);
+    }
+    for (size_t k = 0; k < n_sel; ++k)
+        if (reads[k] >= n_reads) {
+            *err = name + "place " + std::to_string(k) + " names a read outside the batch";
+            return DMX_E_INVALID;
+        }
+    for (size_t L = 0; L < n_len; ++L)
+        if (cap_hit[L] < -1 || cap_half[L] < -1) {
+            *err = name + "length " + std::to_string(L) + ": a cap is a distance, or -1 for none";
+            return DMX_E_INVALID;
+        }
+    ps.place.clear(), ps.row.clear(), ps.q.clear(), ps.tn.clear(), ps.L.clear();
+    uint64_t made = 0;
+    for (size_t k = 0; k < n_sel; ++k) {
+        const uint32_t m = lens[reads[k]];
+        const double la = (double)m;
+        for (size_t g = 0; g < n_rows; ++g) {
+            const uint64_t n64 = row_off[g + 1] - row_off[g];
+            const double lb = (double)n64;
+            if (la * 1.05 < lb || lb * 1.05 < la) continue;
+            if (m < 1 || m > DMX_PD_MAX_LEN) {
+                *err = name + "place " + std::to_string(k) + ": reads of 1.." +
+                       std::to_string(DMX_PD_MAX_LEN) + " nt supported";
+                return DMX_E_UNSUPPORTED;
+            }
+            if (n64 < 1 || n64 > DMX_PD_MAX_LEN) {
+                *err = name + "place " + std::to_string(k) + ": row " + std::to_string(g) +
+                       " has " + std::to_string(n64) + " columns (1.." +
+                       std::to_string(DMX_PD_MAX_LEN) + " supported)";
+                return DMX_E_UNSUPPORTED;
+            }
+            const uint32_t n = (uint32_t)n64, L = std::max(m, n);
+            if (L >= n_len) {
+                *err = name + "place " + std::to_string(k) + ", row " + std::to_string(g) +
+                       ": length " + std::to_string(L) + " is outside the " +
+                       std::to_string(n_len) + " entries of the tables";
+                return DMX_E_INVALID;
+            }
+            if ((uint64_t)bin_off[L] + (uint64_t)std::max(cap_hit[L], 0) >= n_bins) {
+                *err = name + "length " + std::to_string(L) + ": its classes end outside the " +
+                       std::to_string(n_bins) + " entries of bins";
+                return DMX_E_INVALID;
+            }
+            if (made >= DMX_LG_MAX_PAIRS) {
+                *err = name + "at most " + std::to_string(DMX_LG_MAX_PAIRS) + " pairs supported";
+                return DMX_E_UNSUPPORTED;
+            }
+            ps.place.push_back((uint32_t)k);
+            ps.row.push_back((uint32_t)g);
+            ps.q.push_back(reads[k]);
+            ps.tn.push_back(n);
+            ps.L.push_back(L);
+            ++made;
+        }
+        if (made / chunk == max_chunks) break;
+    }
+    return DMX_OK;
+}
+
+void ra_fill_none(size_t n_sel, uint32_t* best_row, uint32_t* best_d, uint16_t* best_class) {
+    for (size_t k = 0; k < n_sel; ++k) {
+        best_row[k] = DMX_LG_NONE;
+        best_d[k] = DMX_LG_NONE;
+        best_class[k] = 0;
+    }
+}
+
+}  // namespace
+
+extern "C" float dmx_rowassign_ms(dmx_ctx* c) { return c && c->ra ? c->ra->ms : 0.f; }
+
+extern "C" int dmx_rowassign_host(const uint32_t* seq2b, const uint32_t* nmask,
+                                  const uint64_t* offsets, const uint32_t* lens, size_t n_reads,
+                                  size_t n_rows, const uint8_t* masks, const uint64_t* row_off,
+                                  const uint32_t* reads, size_t n_sel, const int32_t* cap_hit,
+                                  const int32_t* cap_half, const uint32_t* bin_off, size_t n_len,
+                                  const uint16_t* bins, size_t n_bins, uint64_t chunk,
+                                  uint64_t max_chunks, uint32_t* best_row, uint32_t* best_d,
+                                  uint16_t* best_class, uint64_t* n_pairs, uint64_t* n_lines,
+                                  int n_threads) {
+    const char* const who = "dmx_rowassign_host";
+    if (!n_pairs || !n_lines || (n_sel && (!reads || !best_row || !best_d || !best_class)) ||
+        (n_sel && n_rows &&
+         (!masks || !row_off || !cap_hit || !cap_half || !bin_off || !bins || !seq2b || !nmask ||
+          !offsets || !lens))) {
+        set_process_error(std::string(who) + ": null argument");
+        return DMX_E_INVALID;
+    }
+    RaPairs ps;
+    if (n_sel && n_rows) {
+        std::string err;
+        if (const int rc = ra_prepare(who, lens, n_reads, n_rows, masks, row_off, reads, n_sel,
+                                      cap_hit, cap_half, bin_off, n_len, n_bins, chunk, max_chunks,
+                                      ps, &err)) {
+            set_process_error(err);
+            return rc;
+        }
+    }
+    *n_pairs = ps.place.size();
+    *n_lines = 0;
+    ra_fill_none(n_sel, best_row, best_d, best_class);
+    const size_t n = ps.place.size();
+    if (!n) return DMX_OK;
+    std::vector<uint32_t> fcap(n), df(n);
+    for (size_t i = 0; i < n; ++i)
+        fcap[i] = (uint32_t)std::max(std::max(cap_hit[ps.L[i]], cap_half[ps.L[i]]), 0);
+    if (const int rc = dmx_rowdist_host(seq2b, nmask, offsets, lens, n_reads, n_rows, masks, row_off,
+                                        ps.q.data(), ps.row.data(), fcap.data(), n, df.data(),
+                                        n_threads))
+        return rc;
+    // the retries, against the reverse complements as rows of their own
+    std::vector<uint32_t> again, q2, r2, cap2, dr;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t d = df[i], ch = cap_hit[ps.L[i]], chalf = cap_half[ps.L[i]];
+        if (!(d <= ch) && ch >= 0 && d > chalf) {
+            again.push_back((uint32_t)i);
+            q2.push_back(ps.q[i]);
+            r2.push_back(ps.row[i]);
+            cap2.push_back((uint32_t)ch);
+        }
+    }
+    if (!again.empty()) {
+        std::vector<uint8_t> rmasks(row_off[n_rows] ? row_off[n_rows] : 1), one;
+        for (size_t g = 0; g < n_rows; ++g) {
+            rr_mask_rc(masks + row_off[g], (size_t)(row_off[g + 1] - row_off[g]), one);
+            std::copy(one.begin(), one.end(), rmasks.begin() + row_off[g]);
+        }
+        dr.resize(again.size());
+        if (const int rc = dmx_rowdist_host(seq2b, nmask, offsets, lens, n_reads, n_rows,
+                                            rmasks.data(), row_off, q2.data(), r2.data(),
+                                            cap2.data(), again.size(), dr.data(), n_threads))
+            return rc;
+    }
+    // the lines in pair-generation order; a later line replaces the kept one iff its class is
+    // at least the kept one's (update_groups)
+    uint64_t lines = 0;
+    size_t a = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t L = ps.L[i];
+        const int64_t ch = cap_hit[L];
+        uint32_t d = df[i], rev = 0;
+        bool line = (int64_t)d <= ch;
+        if (a < again.size() && again[a] == i) {
+            d = dr[a++];
+            rev = DMX_LG_REV;
+            line = (int64_t)d <= ch;
+        }
+        if (!line) continue;
+        ++lines;
+        const uint16_t cls = bins[(size_t)bin_off[L] + d];
+        const uint32_t k = ps.place[i];
+        if (best_row[k] == DMX_LG_NONE || cls >= best_class[k]) {
+            best_row[k] = ps.row[i];
+            best_d[k] = d | rev;
+            best_class[k] = cls;
+        }
+    }
+    *n_lines = lines;
+    return DMX_OK;
+}
+
+extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
+                             const uint64_t* row_off, const uint32_t* reads, size_t n_sel,
+                             const int32_t* cap_hit, const int32_t* cap_half,
+                             const uint32_t* bin_off, size_t n_len, const uint16_t* bins,
+                             size_t n_bins, uint64_t chunk, uint64_t max_chunks,
+                             uint32_t* best_row, uint32_t* best_d, uint16_t* best_class,
+                             uint64_t* n_pairs, uint64_t* n_lines) {
+    const char* const who = "dmx_rowassign";
+    if (!c) return DMX_E_INVALID;
+    if (c->ra) c->ra->ms = 0.f;
+    if (!n_pairs || !n_lines || (n_sel && (!reads || !best_row || !best_d || !best_class)) ||
+        (n_sel && n_rows && (!masks || !row_off || !cap_hit || !cap_half || !bin_off || !bins))) {
+        c->err = "dmx_rowassign: null rows, reads, tables or output";
+        return DMX_E_INVALID;
+    }
+    RaPairs ps;
+    std::vector<uint32_t> lens;
+    if (n_sel && n_rows) {
+        if (const int rc = pd_fetch_lens(c, who, 1, lens)) return rc;
+        if (const int rc = ra_prepare(who, lens.data(), lens.size(), n_rows, masks, row_off, reads,
+                                      n_sel, cap_hit, cap_half, bin_off, n_len, n_bins, chunk,
+                                      max_chunks, ps, &c->err))
+            return rc;
+    }
+    const size_t n = ps.place.size();
+    *n_pairs = n;
+    *n_lines = 0;
+    if (!n) {
+        ra_fill_none(n_sel, best_row, best_d, best_class);
+        return DMX_OK;
+    }
+    PD_CK(who, hipSetDevice(c->device));
+    if (const int rc = pd_state(c, who, c->ra)) return rc;
+    RaState* s = c->ra;
+    hipStream_t st = c->stream;
+    const size_t chunk_pairs = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+
+    // the rows some pair names closed up, each padded to 16 columns; room for their reverse
+    // complements behind them, written only when a pair retries
+    std::vector<uint64_t> goff(n_rows, ~(uint64_t)0);
+    std::vector<RrRow> used;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t g = ps.row[i];
+        if (goff[g] == ~(uint64_t)0) {
+            goff[g] = total;
+            used.push_back(RrRow{total, ps.rowlen[g], 0u});
+            total += ((uint64_t)ps.rowlen[g] + 15u) & ~(uint64_t)15u;
+        }
+    }
+    std::vector<uint8_t> rows(total, 0);
+    for (size_t g = 0; g < n_rows; ++g)
+        if (goff[g] != ~(uint64_t)0) std::memcpy(rows.data() + goff[g], masks + row_off[g], ps.rowlen[g]);
+    PD_CK(who, s->mask.reserve(2 * total));
+    PD_CK(who, s->cap_hit.reserve(n_len));
+    PD_CK(who, s->cap_half.reserve(n_len));
+    PD_CK(who, s->bin_off.reserve(n_len));
+    PD_CK(who, s->bins.reserve(n_bins));
+    PD_CK(who, s->best.reserve(n_sel));
+    PD_CK(who, s->cnt.reserve(1));
+    PD_CK(who, s->o_row.reserve(n_sel));
+    PD_CK(who, s->o_d.reserve(n_sel));
+    PD_CK(who, s->o_class.reserve(n_sel));
+    PD_CK(who, hipMemcpyAsync(s->mask.p, rows.data(), total, hipMemcpyHostToDevice, st));
+    PD_CK(who, hipMemcpyAsync(s->cap_hit.p, cap_hit, n_len * 4, hipMemcpyHostToDevice, st));
+    PD_CK(who, hipMemcpyAsync(s->cap_half.p, cap_half, n_len * 4, hipMemcpyHostToDevice, st));
+    PD_CK(who, hipMemcpyAsync(s->bin_off.p, bin_off, n_len * 4, hipMemcpyHostToDevice, st));
+    PD_CK(who, hipMemcpyAsync(s->bins.p, bins, n_bins * 2, hipMemcpyHostToDevice, st));
+    PD_CK(who, hipMemsetAsync(s->best.p, 0, n_sel * sizeof(unsigned long long), st));
+    PD_CK(who, hipMemsetAsync(s->cnt.p, 0, sizeof(unsigned long long), st));
+    PD_CK(who, hipStreamSynchronize(st));   // `rows` and the caller's tables are pageable
+
+    PdPlan<RaPair> pl;
+    std::vector<uint32_t> need;
+    float total_ms = 0.f;
+    // one launch of pairs[lo .. ) of a list and its decision; in[i]: the list's pair i among the
+    // call's pairs; pass 0 brings the launch's retry bitmap back (bit b: sorted pair b)
+    auto launch = [&](const uint32_t* lq, const uint32_t* lr, const uint32_t* lcap,
+                      const uint32_t* ltn, size_t cnt, size_t lo, const uint32_t* in, int pass,
+                      size_t* end) -> int {
+        const size_t hi = pd_plan(pl, lens.data(), lq, lr, nullptr, lcap, cnt, lo, chunk_pairs,
+                                  kPdNoBudget, ltn);
+        const size_t np = hi - lo, words = (np + 31) / 32;
+        for (size_t k = 0; k < np; ++k) {
+            RaPair& P = pl.pairs[k];
+            const size_t i = lo + pl.place(k);
+            P.row = goff[P.t] + (pass ? total : 0u);
+            P.k = ps.place[in ? in[i] : i];
+        }
+        RaArgs A;
+        if (const int rc = pd_stage(c, who, *s, pl, np, kKerRowassign, A)) return rc;
+        A.mask = s->mask.p;
+        A.cols = pass ? 2 * total : total;
+        A.out = s->out.p;
+        PD_CK(who, s->need.reserve(words));
+        if (pass == 0) PD_CK(who, hipMemsetAsync(s->need.p, 0, words * 4, st));
+        RaDecide D;
+        D.bd = make_bounds(c, kKerRowassignDecide);
+        D.pairs = s->pairs.p, D.dist = s->out.p, D.lens = c->d_lens;
+        D.np = (uint32_t)np, D.pass = (uint32_t)pass;
+        D.cap_hit = s->cap_hit.p, D.cap_half = s->cap_half.p;
+        D.bin_off = s->bin_off.p, D.bins = s->bins.p;
+        D.n_len = (uint32_t)n_len, D.n_sel = (uint32_t)n_sel, D.n_bins = n_bins;
+        D.best = s->best.p, D.need = s->need.p;
+        D.need_words = pass == 0 ? (uint32_t)words : 0u;
+        D.cnt = s->cnt.p;
+        PD_CK(who, hipEventRecord(s->ev[0], st));
+        pd_launch_forward(rowassign_kernel, A, st);
+        hipLaunchKernelGGL(rowassign_decide_kernel,
+                           dim3((uint32_t)((np + kRrRcBlock - 1) / kRrRcBlock)), dim3(kRrRcBlock),
+                           0, st, D);
+        PD_CK(who, hipGetLastError());
+        PD_CK(who, hipEventRecord(s->ev[1], st));
+        if (pass == 0) {
+            need.resize(words);
+            PD_CK(who, hipMemcpyAsync(need.data(), s->need.p, words * 4, hipMemcpyDeviceToHost, st));
+        }
+        PD_CK(who, hipStreamSynchronize(st));   // the plan's pair records are pageable
+        if (const int brc = bounds_check(c, who)) return brc;
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+        total_ms += ms;
+        *end = hi;
+        return DMX_OK;
+    };
+
+    std::vector<uint32_t> fcap(n), retry;
+    for (size_t i = 0; i < n; ++i)
+        fcap[i] = (uint32_t)std::max(std::max(cap_hit[ps.L[i]], cap_half[ps.L[i]]), 0);
+    for (size_t lo = 0, hi = 0; lo < n; lo = hi) {
+        if (const int rc = launch(ps.q.data(), ps.row.data(), fcap.data(), ps.tn.data(), n, lo,
+                                  nullptr, 0, &hi))
+            return rc;
+        for (size_t w = 0; w < need.size(); ++w)
+            for (uint32_t bits = need[w]; bits; bits &= bits - 1u) {
+                const size_t b = 32 * w + (size_t)__builtin_ctz(bits);
+                if (b < hi - lo) retry.push_back((uint32_t)(lo + pl.place(b)));
+            }
+    }
+    const size_t n2 = retry.size();
+    if (n2) {
+        // the reverse complement of every uploaded row, `total` columns behind the row
+        PD_CK(who, s->rows.reserve(used.size()));
+        PD_CK(who, hipMemcpyAsync(s->rows.p, used.data(), used.size() * sizeof(RrRow),
+                                  hipMemcpyHostToDevice, st));
+        PD_CK(who, bounds_reset(c, st));
+        RrRcArgs R;
+        R.bd = make_bounds(c, kKerRowpairRc);
+        R.rows = s->rows.p;
+        R.n_rows = (uint32_t)used.size();
+        R.mask = s->mask.p;
+        R.half = total;
+        R.cols = 2 * total;
+        PD_CK(who, hipEventRecord(s->ev[0], st));
+        hipLaunchKernelGGL(rowpair_rc_kernel, dim3(R.n_rows), dim3(kRrRcBlock), 0, st, R);
+        PD_CK(who, hipGetLastError());
+        PD_CK(who, hipEventRecord(s->ev[1], st));
+        PD_CK(who, hipStreamSynchronize(st));   // `used` is pageable
+        if (const int brc = bounds_check(c, who)) return brc;
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+        total_ms += ms;
+        std::sort(retry.begin(), retry.end());
+        std::vector<uint32_t> q2(n2), r2(n2), cap2(n2), tn2(n2);
+        for (size_t k = 0; k < n2; ++k) {
+            const uint32_t i = retry[k];
+            q2[k] = ps.q[i];
+            r2[k] = ps.row[i];
+            tn2[k] = ps.tn[i];
+            cap2[k] = (uint32_t)cap_hit[ps.L[i]];   // >= 0 where a retry is asked for
+        }
+        for (size_t lo = 0, hi = 0; lo < n2; lo = hi)
+            if (const int rc = launch(q2.data(), r2.data(), cap2.data(), tn2.data(), n2, lo,
+                                      retry.data(), 1, &hi))
+                return rc;
+    }
+    RaFinish F;
+    F.bd = make_bounds(c, kKerRowassignFinish);
+    F.best = s->best.p;
+    F.n_sel = (uint32_t)n_sel;
+    F.row = s->o_row.p, F.d = s->o_d.p, F.cls = s->o_class.p;
+    PD_CK(who, bounds_reset(c, st));
+    PD_CK(who, hipEventRecord(s->ev[0], st));
+    hipLaunchKernelGGL(rowassign_finish_kernel,
+                       dim3((uint32_t)((n_sel + kRrRcBlock - 1) / kRrRcBlock)), dim3(kRrRcBlock), 0,
+                       st, F);
+    PD_CK(who, hipGetLastError());
+    PD_CK(who, hipEventRecord(s->ev[1], st));
+    unsigned long long lines = 0;
+    PD_CK(who, hipMemcpyAsync(best_row, s->o_row.p, n_sel * 4, hipMemcpyDeviceToHost, st));
+    PD_CK(who, hipMemcpyAsync(best_d, s->o_d.p, n_sel * 4, hipMemcpyDeviceToHost, st));
+    PD_CK(who, hipMemcpyAsync(best_class, s->o_class.p, n_sel * 2, hipMemcpyDeviceToHost, st));
+    PD_CK(who, hipMemcpyAsync(&lines, s->cnt.p, sizeof lines, hipMemcpyDeviceToHost, st));
+    PD_CK(who, hipStreamSynchronize(st));
+    if (const int brc = bounds_check(c, who)) return brc;
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+    s->ms = total_ms + ms;
+    *n_lines = lines;
+    return DMX_OK;
 }

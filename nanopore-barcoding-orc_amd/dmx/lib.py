@@ -49,7 +49,8 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_hitgroups_host", "dmx_hitgroups_stats", "dmx_rowpairdist", "dmx_rowpairdist_host",
            "dmx_rowhits", "dmx_rowhits_host", "dmx_panel_piece_pairs", "dmx_hithist",
            "dmx_pairhits_cross", "dmx_hitgroups_within", "dmx_hithist_host",
-           "dmx_pairhits_cross_host", "dmx_hitgroups_within_host", "dmx_panel_near_shared"]
+           "dmx_pairhits_cross_host", "dmx_hitgroups_within_host", "dmx_panel_near_shared",
+           "dmx_rowassign", "dmx_rowassign_host"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -190,6 +191,14 @@ def load() -> ctypes.CDLL:
                                        P, c_int]
         L.dmx_rowdist_ms.argtypes = [P]
         L.dmx_rowdist_ms.restype = ctypes.c_float
+    if hasattr(L, "dmx_rowassign"):
+        u64 = ctypes.c_uint64
+        ra = [c_size, P, c_u64p, P, c_size, P, P, P, c_size, P, c_size, u64, u64, P, P, P,
+              ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.dmx_rowassign.argtypes = [P] + ra
+        L.dmx_rowassign_host.argtypes = [P, P, c_u64p, P, c_size] + ra + [c_int]
+        L.dmx_rowassign_ms.argtypes = [P]
+        L.dmx_rowassign_ms.restype = ctypes.c_float
     if hasattr(L, "dmx_edgegroups"):
         L.dmx_edgegroups.argtypes = [P, P, P, c_size, ctypes.c_uint32, P]
         L.dmx_edgegroups_host.argtypes = [P, P, c_size, ctypes.c_uint32, P]
@@ -542,6 +551,28 @@ class Context:
     def rowdist_ms(self) -> float:
         """Device time (ms) of the last rowdist call."""
         return float(self._L.dmx_rowdist_ms(self._h))
+
+    # ---- reads assigned to rows of masks (include/dmx.h dmx_rowassign; DESIGN.md §8l) -----------
+    def rowassign(self, rows, reads, cap_hit, cap_half, bin_off, bins, chunk: int = 2_000_000,
+                  max_chunks: int = 100):
+        """The best row per read, decided on the device: reads[k] (resident read indices; every
+        place k is an entry of its own) against every row (as rowdist's) within 5 % of its
+        length; cap_hit / cap_half (int32, -1 = none) and bin_off (uint32) are indexed by the
+        pair's longer length, bins (uint16) maps bin_off[L] + d to the identity class; the
+        generation stops after the place at whose end max_chunks chunks of `chunk` pairs are
+        full.  Returns (best_row uint32, LG_NONE = no line; best_d uint32, d or d | LG_REV;
+        best_class uint16; n_pairs; n_lines)."""
+        a = _rowassign_args(rows, reads, cap_hit, cap_half, bin_off, bins, chunk, max_chunks)
+        try:
+            self._check(self._L.dmx_rowassign(self._h, *a.call()), "dmx_rowassign")
+        except DmxError as e:
+            e.outputs = (a.best_row, a.best_d, a.best_class)   # a refusal leaves them untouched
+            raise
+        return a.result()
+
+    def rowassign_ms(self) -> float:
+        """Device time (ms) of the last rowassign call."""
+        return float(self._L.dmx_rowassign_ms(self._h))
 
     # ---- rows of masks against rows of masks (include/dmx.h dmx_rowpairdist; DESIGN.md §8j) -----
     def rowpairdist(self, rows, q, t, mode: int, flags=None, caps=None) -> np.ndarray:
@@ -962,6 +993,71 @@ def rowdist_host(p: "Packed", rows, q, r, caps=None, n_threads: int = 1) -> np.n
         msg = L.dmx_last_error(None)
         raise DmxError(f"dmx_rowdist_host failed ({rc}): {msg.decode() if msg else ''}")
     return out
+
+
+class _rowassign_args:
+    """The arrays of dmx_rowassign(_host), checked, and the outputs.  The outputs start as the
+    value a refused call must leave in them, so that the tests can see them untouched."""
+
+    def __init__(self, rows, reads, cap_hit, cap_half, bin_off, bins, chunk, max_chunks):
+        self.masks, self.off, self.reads, _, _ = _rowdist_args(rows, reads, reads, None)
+        self.cap_hit = np.ascontiguousarray(cap_hit, dtype=np.int32)
+        self.cap_half = np.ascontiguousarray(cap_half, dtype=np.int32)
+        self.bin_off = np.ascontiguousarray(bin_off, dtype=np.uint32)
+        self.bins = np.ascontiguousarray(bins, dtype=np.uint16)
+        if (self.cap_hit.ndim != 1 or self.cap_half.shape != self.cap_hit.shape
+                or self.bin_off.shape != self.cap_hit.shape or self.bins.ndim != 1):
+            raise DmxError("rowassign: cap_hit, cap_half and bin_off must be one-dimensional and "
+                           "of equal length, bins one-dimensional")
+        if int(chunk) < 0 or int(max_chunks) < 0:
+            raise DmxError("rowassign: chunk and max_chunks must not be negative")
+        self.chunk, self.max_chunks = int(chunk), int(max_chunks)
+        n = len(self.reads)
+        self.best_row = np.full(n, 0xDEADBEEF, dtype=np.uint32)
+        self.best_d = np.full(n, 0xDEADBEEF, dtype=np.uint32)
+        self.best_class = np.full(n, 0xBEEF, dtype=np.uint16)
+        self.n_pairs, self.n_lines = ctypes.c_uint64(0), ctypes.c_uint64(0)
+
+    def call(self):
+        self._keep = []   # a valid pointer even for an empty array: only the lengths decide
+        return [len(self.off) - 1, self.masks.ctypes.data, self.off.ctypes.data,
+                _keep_ptr(self, self.reads),
+                len(self.reads), _keep_ptr(self, self.cap_hit), _keep_ptr(self, self.cap_half),
+                _keep_ptr(self, self.bin_off), len(self.cap_hit), _keep_ptr(self, self.bins),
+                len(self.bins), self.chunk, self.max_chunks,
+                _keep_ptr(self, self.best_row), _keep_ptr(self, self.best_d),
+                _keep_ptr(self, self.best_class), ctypes.byref(self.n_pairs),
+                ctypes.byref(self.n_lines)]
+
+    def result(self):
+        return (self.best_row, self.best_d, self.best_class, int(self.n_pairs.value),
+                int(self.n_lines.value))
+
+
+def _keep_ptr(owner, a):
+    """a's address, or that of a one-element stand-in kept alive by owner when a is empty."""
+    if len(a):
+        return a.ctypes.data
+    owner._keep.append(np.zeros(1, dtype=a.dtype))
+    return owner._keep[-1].ctypes.data
+
+
+def rowassign_host(p: "Packed", rows, reads, cap_hit, cap_half, bin_off, bins,
+                   chunk: int = 2_000_000, max_chunks: int = 100, n_threads: int = 1):
+    """dmx_rowassign's contract on the host (no GPU), on dmx_rowdist_host's DP with the decision
+    and the reduction in sequential C++: the checker of the kernels and ctx=None of
+    sorter.assign_best.  Returns what Context.rowassign returns."""
+    L = load()
+    a = _rowassign_args(rows, reads, cap_hit, cap_half, bin_off, bins, chunk, max_chunks)
+    try:
+        _host_check(L, L.dmx_rowassign_host(p.seq2b.ctypes.data, p.nmask.ctypes.data,
+                                            p.offsets.ctypes.data, p.lengths.ctypes.data,
+                                            p.n_reads, *a.call(), int(n_threads)),
+                    "dmx_rowassign_host")
+    except DmxError as e:
+        e.outputs = (a.best_row, a.best_d, a.best_class)
+        raise
+    return a.result()
 
 
 def _rowpair_args(rows, q, t, flags, caps):

@@ -10,8 +10,13 @@ comp_consensus_groups() and compare_consensus() restate the two merge loops (:12
 :1857-1958) on dmx_rowhits (consensus against consensus, HW, both strands), with
 the first reads of a group in index order where the reference samples at random.
 estimate_ssg() and species_groups() restate SSG (:810-836) and the first half of read_indexes
-(:1363-1411) on dmx_hithist / dmx_pairhits_cross / dmx_hitgroups_within.  NOT
-replaced: that random sampling, finetune and the .group / results files.  The
+(:1363-1411) on dmx_hithist / dmx_pairhits_cross / dmx_hitgroups_within.
+assign_best() is one pass of process_consensuslist / similarity_species / update_groups
+(:1628-1755) as one dmx_rowassign call (pairs, decision and best line per read
+inside the call), rest_reads() the loop around it (:1962-2014), species_consensuses() the second
+half of read_indexes (:1431-1456), and sort_species() runs them per gene group.  NOT replaced:
+that random sampling, finetune (rest_reads has a hook where it runs) and the .group / results
+files.  The
 random selection modes (-ra, -a) are out of scope.  Alphabet: A, C, G, T, N (a read with any other byte is refused;
 the reference would compare such bytes literally).
 
@@ -489,6 +494,208 @@ def assign(ctx, reads, unassigned, consensuses, similar: float, n_threads: int =
     return lines, best, [b for b in best if b[2] >= similar]
 
 
+def _assign_tables(lengths, similar):
+    """dmx_rowassign's three tables, indexed by the longer length of a pair: for every distinct
+    length L among `lengths`, cap_hit[L] = identity_cap(L, similar - 0.01), cap_half[L] =
+    identity_cap(L, 0.5) and a row of cap_hit[L] + 1 identity classes (thousandths, by
+    identity() itself, as _identity_table makes them).  Returns (cap_hit, cap_half, bin_off,
+    bins)."""
+    thr = similar - 0.01
+    top = (int(max(lengths)) + 1) if len(lengths) else 0
+    cap_hit = np.full(top, -1, dtype=np.int32)
+    cap_half = np.full(top, -1, dtype=np.int32)
+    bin_off = np.zeros(top, dtype=np.uint32)
+    rows, at = [], 0
+    for L in sorted({int(x) for x in lengths}):
+        if L < 1:
+            continue
+        cap_half[L] = identity_cap(L, 0.5)
+        cap_hit[L] = cap = identity_cap(L, thr)
+        bin_off[L] = at
+        n = max(cap, 0) + 1
+        rows.append(np.array([int(round(identity(d, L) * 1000)) for d in range(n)],
+                             dtype=np.uint16))
+        at += n
+    return cap_hit, cap_half, bin_off, np.concatenate(rows + [np.zeros(1, dtype=np.uint16)])
+
+
+def assign_best(ctx, reads, unassigned, consensuses, similar: float, n_threads: int = 16,
+                chunk: int = 2_000_000, max_chunks: int = 100):
+    """assign() without the lines: the same pass (process_consensuslist :1628-1691,
+    similarity_species :1693-1716, the best-hit filter of update_groups :1730-1755) as one
+    dmx_rowassign call: the pairs are generated, decided and reduced inside the
+    call, and one record per read comes back.  Arguments as assign()'s; ctx: a Context, or None
+    for the host twin (lib.rowassign_host, n_threads).  The tables are built once per distinct
+    length among the reads and the consensuses (_assign_tables).
+    Returns (best, added): exactly assign()'s second and third return values for the same
+    arguments, the same tuples (read, group, iden) with iden = class / 1000, in the same order.
+    The batch of an unchanged `reads` list stays resident (ctx._resident), as in assign()."""
+    seqs = _clean(reads)
+    cons = _clean(consensuses, "consensus")
+    for g, s in enumerate(cons):
+        if not s:
+            raise DmxError(f"assign_best: consensus {g} is empty")
+    un = np.asarray(unassigned, dtype=np.int64).reshape(-1)
+    if len(un) and (int(un.min()) < 0 or int(un.max()) >= len(seqs)):
+        raise DmxError("assign_best: an unassigned index is outside the reads")
+    ln = np.array([len(s) for s in seqs], dtype=np.int64)
+    lc = np.array([len(s) for s in cons], dtype=np.int64)
+    if (len(ln) and int(ln.max()) > lib.PD_MAX_LEN) or (len(lc) and int(lc.max()) > lib.PD_MAX_LEN):
+        raise DmxError(f"a read or a consensus is longer than {lib.PD_MAX_LEN} nt")
+    if not len(un) or not len(cons):
+        return [], []
+    tables = _assign_tables(np.concatenate([ln[un], lc]), similar)
+    rows = [lib.mask_row(s) for s in cons]
+    p = None
+    if ctx is None or getattr(ctx, "_resident", None) is not reads:
+        blob = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+        offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
+        p = lib.pack(blob, offs, ln.astype(np.uint32))
+        if ctx is not None:
+            ctx.load(p)
+            ctx._resident = reads
+    if ctx is not None:
+        row, _, cls, _, _ = ctx.rowassign(rows, un, *tables, chunk=chunk, max_chunks=max_chunks)
+    else:
+        row, _, cls, _, _ = lib.rowassign_host(p, rows, un, *tables, chunk=chunk,
+                                               max_chunks=max_chunks, n_threads=n_threads)
+    # one entry per read in first-appearance order; a read named twice keeps its later place's
+    # line iff that identity is >= the kept one's, as a later line of the same read would
+    best = {}
+    for k in np.flatnonzero(row != lib.LG_NONE):
+        rd, iden = int(un[k]), int(cls[k]) / 1000
+        if rd not in best or iden >= best[rd][2]:
+            best[rd] = (rd, int(row[k]), iden)
+    best = list(best.values())
+    return best, [b for b in best if b[2] >= similar]
+
+
+def species_consensuses(ctx, reads, species, sample: int = 100, n_threads: int = 16) -> list:
+    """The second half of read_indexes (:1431-1456): a consensus per species group
+    (make_consensus) of its first `sample` reads in index order; the reference takes 100 at
+    random from a larger group (:1434-1435).  species: index arrays into reads.  Returns the
+    consensus strings, one per group."""
+    if not len(species):
+        return []
+    return _group_consensuses(ctx, reads, species, sample, n_threads)
+
+
+def rest_reads(ctx, reads, indexes, groups, consensuses, similar_species: float = 85.0,
+               similar_consensus: float = 96.0, length_diff: float = 8.0, start: float = 0.95,
+               finetune=None, n_threads: int = 16):
+    """rest_reads (:1962-2014), restated literally: the reads of a gene group that are in no
+    species group yet are compared with the groups' consensuses at `similar` = start, lowered in
+    steps of 0.01 down to similar_species / 100, up to three passes per step.
+    reads: the reads the indices name; indexes: the gene group's reads; groups: its species
+    groups (index arrays) with their `consensuses`.  State: the groups and their consensuses,
+    the kept best list of the last pass (the reference's temp file, read back as `templist`) and
+    `templist2`, its entries with iden >= similar.
+      process + update   one assign_best at the current similar over the reads of `indexes` in
+                         no group, ascending (:1648-1657), then update.
+      update alone       (:2008-2011) thresholds the kept best list at the lowered similar
+                         without comparing again, as the reference reads its temp file again.
+      update             every entry of templist2 appends its read to its group; every group
+                         that received a read gets a fresh consensus (make_consensus) of its
+                         first 200 reads in index order.  The reference samples 200 at random
+                         (:1791-1792); index order is this project's standing stand-in for the
+                         reference's random samples.
+    compare_consensus is sorter.compare_consensus with length_diff = 8.0 inside the loop (:1980,
+    :1991: the literal 1.08) and the caller's length_diff at the end (:2014).  The k / similar
+    state machine is the reference's, similar = round(similar - 0.01, 2) included; an update
+    alone after a pass that added reads appends them a second time, as the reference does (a
+    merge or a consensus does not count a read twice).
+    finetune: at similar in [0.94, 0.88] the reference runs finetune (:1997-2000), which draws
+    random samples at every step and has no value to pin.  Here it is a callable
+    (groups, consensuses) -> (groups, consensuses) run at that point, empty groups dropped
+    afterwards; None skips the call.  Either way the process step of :2000 runs (its kept list
+    replaces the previous one), which is the difference from the reference with finetune=None.
+    ctx: a Context, or None for the host twins.  Returns (groups, consensuses)."""
+    groups = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+    cons = [c.decode("ascii") if isinstance(c, (bytes, bytearray)) else str(c)
+            for c in consensuses]
+    if len(groups) != len(cons):
+        raise ValueError("rest_reads: one consensus per group")
+    indexes = np.unique(np.asarray(indexes, dtype=np.int64).reshape(-1))
+    similar = start
+    min_similar = similar_species / 100
+    state = {"kept": [], "groups": groups, "cons": cons}
+
+    def tag():   # make_consensus loaded this very list, packed as assign_best packs it
+        if ctx is not None:
+            ctx._resident = reads
+
+    def process():
+        inside = (np.concatenate(state["groups"]) if state["groups"]
+                  else np.zeros(0, dtype=np.int64))
+        un = indexes[~np.isin(indexes, inside)]
+        state["kept"] = assign_best(ctx, reads, un, state["cons"], similar,
+                                    n_threads=n_threads)[0]
+
+    def update():
+        templist = state["kept"]
+        templist2 = [b for b in templist if b[2] >= similar]
+        if templist2:
+            grown = {}
+            for rd, g, _ in templist2:
+                grown.setdefault(g, []).append(rd)
+            for g, more in grown.items():
+                state["groups"][g] = np.concatenate([state["groups"][g],
+                                                     np.array(more, dtype=np.int64)])
+            order = sorted(grown)
+            fresh = _group_consensuses(ctx, reads, [state["groups"][g] for g in order], 200,
+                                       n_threads)
+            tag()
+            for g, c in zip(order, fresh):
+                state["cons"][g] = c
+        return templist, templist2
+
+    def compare(ld):
+        made = len(state["groups"]) > 1   # compare_consensus then makes consensuses of `reads`
+        state["groups"], state["cons"] = compare_consensus(
+            ctx, reads, state["groups"], state["cons"], similar_consensus, ld, 200, n_threads)
+        if made:
+            tag()
+
+    k = 0
+    process()
+    templist, templist2 = update()
+    if len(templist2) > 200:
+        compare(8.0)
+    k += 1
+    while similar > min_similar:
+        while k <= 2:
+            if len(templist2) > 0:
+                process()
+                templist, templist2 = update()
+                if len(templist2) > 0 and k < 2:
+                    if len(state["groups"]) > 1:
+                        compare(8.0)
+                k += 1
+            else:
+                k = 3
+        else:
+            k = 0
+            if similar in [0.94, 0.88]:
+                if finetune is not None:
+                    g2, c2 = finetune(state["groups"], state["cons"])
+                    keep = [i for i, g in enumerate(g2) if len(g) > 0]
+                    state["groups"] = [np.asarray(g2[i], dtype=np.int64).reshape(-1)
+                                       for i in keep]
+                    state["cons"] = [str(c2[i]) for i in keep]
+                process()
+            similar = round(similar - 0.01, 2)
+            if len(templist) == 0:
+                process()
+                templist, templist2 = update()
+                k += 1
+            else:
+                templist, templist2 = update()
+                k += 1
+    if len(state["groups"]) > 1:
+        compare(length_diff)
+    return state["groups"], state["cons"]
+
+
 def compare_consensuses(ctx, consensuses, length_diff: float = 8.0, threshold: float = 0.60,
                         n_threads: int = 16) -> list:
     """The pair loop of comp_consensus_groups / compare_consensus (:1276-1296, :1869-1889) with
@@ -931,6 +1138,44 @@ def species_groups(ctx, reads, groups, ssg, similar_genes: float = 80.0, minleng
     return out
 
 
+def sort_species(ctx, reads, gene_groups, species, similar_species: float = 85.0,
+                 similar_consensus: float = 96.0, length_diff: float = 8.0, finetune=None,
+                 n_threads: int = 16, log=None) -> list:
+    """What the stage is run for: per gene group with at least one species group (the others
+    are the reference's 'Nothing to do', :2124-2127, reported through `log`),
+    species_consensuses() and then rest_reads() over the gene group's reads.  gene_groups and
+    species as gene_groups() / comp_consensus_groups() and species_groups() return them (index
+    arrays into `reads`, the length-filtered list).  Returns a list of (gene group index, final
+    species groups, their consensuses)."""
+    out = []
+    for k, (g, sp) in enumerate(zip(gene_groups, species)):
+        if not len(sp):
+            if log is not None:
+                log(f"gene group {k}: no species group, nothing to do")
+            continue
+        cons = species_consensuses(ctx, reads, sp, n_threads=n_threads)
+        groups, cons = rest_reads(ctx, reads, g, sp, cons, similar_species, similar_consensus,
+                                  length_diff, finetune=finetune, n_threads=n_threads)
+        out.append((k, groups, cons))
+    return out
+
+
+def write_assigned(path: str, sorted_species, similar_species: float, similar_consensus: float,
+                   length_diff: float):
+    """sort_species()'s result as two files: `path`, a first line '# ss N sc N ldc N' and per
+    final species group a line '<gene group>.<k>: ' and its read indices; `path`.fasta, a record
+    '>consensus_<gene group>_<k>(<n reads>)' per group, the reference's header shape (:1568)."""
+    with open(path, "w") as f:
+        f.write(f"# ss {similar_species:g} sc {similar_consensus:g} ldc {length_diff:g}\n")
+        for k, groups, _ in sorted_species:
+            for j, g in enumerate(groups):
+                f.write(f"{k}.{j}: " + " ".join(str(int(x)) for x in g) + "\n")
+    with open(path + ".fasta", "w") as f:
+        for k, groups, cons in sorted_species:
+            for j, (g, c) in enumerate(zip(groups, cons)):
+                f.write(f">consensus_{k}_{j}({len(g)})\n{c}\n")
+
+
 def read_sequences(path: str) -> list:
     """Every record's sequence of a FASTQ/FASTA(.gz) file, through the native reader."""
     from . import nio
@@ -951,8 +1196,10 @@ def main(argv=None) -> int:
                     "--merged-groups the groups after comp_consensus_groups' merge loop "
                     "(consensuses compared on the GPU, dmx_rowhits), and with "
                     "--species-groups the species groups of every group at the estimated or "
-                    "given ssg; the random sampling, finetune and the .group / results files "
-                    "stay with the reference.")
+                    "given ssg, and with --assigned the species group every read ends up in "
+                    "(the rest_reads loop, reads assigned on the GPU, dmx_rowassign); the "
+                    "random sampling, finetune and the .group / results files stay with the "
+                    "reference.")
     ap.add_argument("-i", "--input", required=True, help="bin in FASTQ/FASTA, optionally .gz")
     ap.add_argument("-o", "--output", default=None,
                     help="similarity lines (i:j:iden[:reverse]); optional with --groups")
@@ -982,6 +1229,22 @@ def main(argv=None) -> int:
                     help="species threshold in percent for --species-groups (default: "
                          "estimated from the identities of all similarity lines, as the "
                          "reference's 'Estimate')")
+    ap.add_argument("--assigned", default=None, metavar="FILE",
+                    help="with --species-groups: the species group every read ends up in.  Per "
+                         "gene group with a species group: a consensus per species group, then "
+                         "the rest_reads loop (the other reads against the consensuses at a "
+                         "similarity lowered from 0.95 to -ss, reads assigned on the GPU, "
+                         "dmx_rowassign; consensuses compared and groups merged at -sc); first "
+                         "line '# ss N sc N ldc N', then '<gene group>.<k>: ' and the read "
+                         "indices per final group; FILE.fasta gets a "
+                         "'>consensus_<gene group>_<k>(<n reads>)' record per group.  finetune "
+                         "is not run")
+    ap.add_argument("-ss", "--similar_species", type=float, default=85.0, metavar="N",
+                    help="lowest similarity (%%) at which a read joins a species group "
+                         "(default 85.0)")
+    ap.add_argument("-sc", "--similar_consensus", type=float, default=96.0, metavar="N",
+                    help="similarity (%%) at which two species groups' consensuses merge them "
+                         "(default 96.0)")
     ap.add_argument("-ldc", "--length_diff_consensus", type=float, default=8.0,
                     help="length difference (%%) allowed between two compared consensuses "
                          "(default 8.0)")
@@ -1000,6 +1263,8 @@ def main(argv=None) -> int:
         ap.error("--merged-groups needs --groups")
     if a.species_groups is not None and a.groups is None:
         ap.error("--species-groups needs --groups")
+    if a.assigned is not None and a.species_groups is None:
+        ap.error("--assigned needs --species-groups")
     if a.consensus_reads < 2:
         ap.error("--consensus-reads must be at least 2")
     try:
@@ -1050,6 +1315,17 @@ def main(argv=None) -> int:
                                         for k, sp in enumerate(species) for m in sp))
                     print(f"dmx-similarity: {sum(len(sp) for sp in species)} species groups -> "
                           f"{a.species_groups}", file=sys.stderr)
+                    if a.assigned is not None:
+                        kept = [reads[i] for i in usable([len(s) for s in reads], a.minlength,
+                                                         a.maxlength)]
+                        done = sort_species(
+                            ctx, kept, of, species, a.similar_species, a.similar_consensus,
+                            a.length_diff_consensus,
+                            log=lambda m: print(f"dmx-similarity: {m}", file=sys.stderr))
+                        write_assigned(a.assigned, done, a.similar_species, a.similar_consensus,
+                                       a.length_diff_consensus)
+                        print(f"dmx-similarity: {sum(len(g) for _, g, _ in done)} final species "
+                              f"groups -> {a.assigned}, {a.assigned}.fasta", file=sys.stderr)
     except (DmxError, OSError, ValueError) as e:
         print(f"dmx-similarity: {e}", file=sys.stderr)
         return 1
