@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Replay a tools/parity_sweep.py run's random draws on the CPU (no GPU, no oracle) up to the
-case whose parameters match a recorded mismatch, and write that case (parameters + every read)
-as JSON, so it can be run alone against the oracle with any libdmx build (--run, on the GPU box).
+"""Rebuild a recorded mismatch of a tools/parity_sweep.py run on the CPU (no GPU, no oracle) from
+its seed and k, and write that case (parameters + every read) as JSON, so it can be run alone
+against the oracle with any libdmx build (--run, on the GPU box).  With the library of the tree,
+`python tools/parity_sweep.py --case SEED:K` does both steps at once.
 
 usage: python tools/replay_sweep.py SWEEP_JSON [--which 0] --out CASE_JSON
        python tools/replay_sweep.py --run CASE_JSON        (GPU: per-read diff vs the oracle)
@@ -21,42 +22,25 @@ for p in (ROOT, os.path.join(ROOT, "nanopore-barcoding-orc_amd"), os.path.join(R
 import oracle  # noqa: E402  (checker only)
 
 
-class _NoCtx:
-    """Stands in for lib.Context while replaying the draws: records nothing, runs nothing."""
-
-    def set_panel(self, *a, **k):
-        pass
-
-    set_panel_mixed = set_mode = set_panel
-
-    def run(self, p):
-        from dmx import lib
-        return np.zeros(p.n_reads, dtype=lib.RESULT_DTYPE)
-
-
 def find(sweep_json, which, out):
-    import parity_sweep as ps
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sweep_cases as sw
     rec = json.load(open(sweep_json))
     target = rec["mismatches"][which]
-    rng = np.random.default_rng(rec["seed"])
-    real = oracle.run_batch
-    oracle.run_batch = lambda p1, p2, blob, offs, lens, **k: np.zeros(
-        len(lens), dtype=oracle.RESULT_DTYPE)
-    try:
-        for case in range(rec["cases"]):
-            u = rng.random()
-            fn = ps.case_random if u < 0.5 else (ps.case_random_pair if u < 0.8
-                                                 else ps.case_synth)
-            _, _, params, seqs = fn(rng, _NoCtx())
-            if all(params.get(k) == v for k, v in params.items() if k in target) and \
-                    all(target.get(k) == params.get(k) for k in params):
-                json.dump(dict(case=case, params=params, reads=seqs), open(out, "w"))
-                print(f"case {case}: {params['kind']}, {len(seqs or [])} reads -> {out}")
-                return 0
-    finally:
-        oracle.run_batch = real
-    print("not found")
-    return 1
+    if "k" not in target:
+        print("this sweep was recorded before every case had a stream of its own "
+              "(tools/parity_sweep.py): its draws cannot be replayed")
+        return 1
+    case = sw.sweep_case(rec["seed"], target["k"])
+    if case["kind"] != "single":
+        print(f"case {case['id']} is no single-round case: python tools/parity_sweep.py "
+              f"--case {case['id']}")
+        return 1
+    params = dict(kind="random", panel=case["panels"][0], wheres=case["wheres"][0], e=case["e"],
+                  min_overlap=case["min_overlap"], rc=case["rc"])
+    json.dump(dict(case=target["k"], params=params, reads=case["reads"]), open(out, "w"))
+    print(f"case {case['id']}: {len(case['reads'])} reads -> {out}")
+    return 0
 
 
 def run(case_json):
