@@ -21,11 +21,19 @@
 extern "C" {
 #endif
 
+/* 4 also covers the calls added since without a bump, all additive (no existing signature or
+ * behaviour changed): the amplicon-sorting entry points below, and dmx_set_panel_ex,
+ * dmx_ends_host, DMX_ANCHORED and DMX_NONINTERNAL.  A caller that needs one of them checks for
+ * the symbol. */
 #define DMX_ABI_VERSION 4
 
 /* Panel flags (dmx_set_panel.flags). */
 #define DMX_FRONT 0x01  /* -g ADAPTER: 5' adapter, Where.FRONT (prefix of adapter may be skipped at read start) */
 #define DMX_BACK 0x02   /* -a ADAPTER: 3' adapter, Where.BACK  (suffix may be skipped at read end)          */
+/* Restricted adapter types, each combined with DMX_FRONT or DMX_BACK; both
+ * together is DMX_E_INVALID.  Their matches touch the start (FRONT) or the end (BACK) of the view. */
+#define DMX_ANCHORED 0x04    /* -g ^ADAPTER / -a ADAPTER$: the whole adapter (min_overlap = its length)      */
+#define DMX_NONINTERNAL 0x08 /* -g XADAPTER / -a ADAPTERX: may be cut off at the read end it touches only     */
 #define DMX_RC 0x10     /* --rc: also try the reverse complement; use it iff its score is strictly greater  */
 
 /* Run modes (dmx_set_mode). */
@@ -83,7 +91,28 @@ int dmx_set_panel(dmx_ctx* ctx, int round, const char* const* seqs, const int* l
 int dmx_set_panel_mixed(dmx_ctx* ctx, int round, const char* const* seqs, const int* lens,
                         const int* wheres, int n_adapters, double max_errors, int min_overlap,
                         int rc);
+/* As dmx_set_panel_mixed, with a minimum overlap per adapter: min_overlaps[a] replaces
+ * min_overlap for adapter a (NULL: min_overlap for all).  wheres[a] is DMX_FRONT or DMX_BACK,
+ * alone or with DMX_ANCHORED or DMX_NONINTERNAL (dmx_set_panel's flags and dmx_set_panel_mixed's
+ * wheres take the two bits too).  An anchored adapter's minimum overlap is its length, whatever
+ * is passed.  The unrestricted adapters of a panel share one minimum overlap (DMX_E_UNSUPPORTED
+ * otherwise) and run through the internal-adapter pipeline; the restricted ones run through the
+ * end-window stage, and both meet in the read's winner slot with their panel indices.
+ * DMX_MODE_LINKED refuses a panel with restricted adapters at dmx_exec (DMX_E_UNSUPPORTED). */
+int dmx_set_panel_ex(dmx_ctx* ctx, int round, const char* const* seqs, const int* lens,
+                     const int* wheres, const int* min_overlaps, int n_adapters,
+                     double max_errors, int min_overlap, int rc);
 int dmx_set_mode(dmx_ctx* ctx, int mode);
+/* Host only (no GPU; tests, the sanitizer program): one DMX_MODE_SINGLE round of the panel
+ * dmx_set_panel_ex would build, on a dmx_pack layout, by a plain full-matrix DP per (read,
+ * orientation, adapter) over cutadapt's column range with its boundary conditions (a different
+ * algorithm from the kernels' on purpose: no bit-vectors, no windows lists, no keys).  Every
+ * adapter type, restricted or not.  out[i] is what dmx_run writes for read i.  Errors:
+ * dmx_last_error(NULL). */
+int dmx_ends_host(const char* const* seqs, const int* lens, const int* wheres,
+                  const int* min_overlaps, int n_adapters, double max_errors, int min_overlap,
+                  int rc, const uint32_t* seq2b, const uint32_t* nmask, const uint64_t* offsets,
+                  const uint32_t* read_lens, size_t n_reads, dmx_result* out);
 /* Host only (no GPU; tests): the piece screen dmx_set_panel would build for
  * these arguments: out[0..7] = {sampling stride (0 = off: the full filter pass), pieces, sampled
  * 8-mer keys, entries, FRONT partial-alignment reach, positions per screen lane, min len + dlo - 1
@@ -218,12 +247,14 @@ int dmx_counts(dmx_ctx* ctx, uint64_t* out_counts, size_t n_out);
  * the parts of scan0/scan1 spent in the shared-suffix filter and the prefix verification:
  * filter0, verify0, filter1, verify1, then the index screen and the window scan:
  * screen0, wscan0, screen1, wscan1, then the piece screen's part of filter0 / filter1:
- * pieces0, pieces1 — pass n_stage = 17 to receive them all), and
- * counts[n_counts <= 14] = {candidate clusters r0, r1, filter windows kept for the window scan
+ * pieces0, pieces1, then the end-window stage: ends0, ends1 — pass n_stage = 19 to receive them
+ * all), and
+ * counts[n_counts <= 18] = {candidate clusters r0, r1, filter windows kept for the window scan
  * r0, r1, candidate cells (band mode) or clusters resolved after pruning (ring mode) r0, r1,
  * band DPs / tracebacks r0, r1, filter windows before prefix verification r0, r1, (window
  * piece, adapter) tasks passed by the index screen r0, r1, filter tasks of the piece screen
- * r0, r1}, and flags
+ * r0, r1, (view, orientation, restricted adapter) triples the end-window stage ran its exact DP
+ * for r0, r1, triples it looked at (views of at least min_overlap columns) r0, r1}, and flags
  * (bit0 cluster overflow, bit1 exactness-check violation, bit2 filter-window / task overflow,
  * bit3 candidate-cell overflow, bit4 a filter invariant (step bucket or piece-screen cell range)
  * violated, bit5 a bounds violation (DMX_DEBUG_BOUNDS builds); must be 0). */

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <tuple>
@@ -73,8 +74,8 @@ int dev_alloc(Ctx* c, T** p, size_t count) {
 
 // (A0+1)(A1+1) per-bin counts + 2 RC counts (include/dmx.h dmx_counts)
 size_t counts_size(const Ctx* c) {
-    const size_t a1 = c->mode == DMX_MODE_SINGLE ? 0 : (size_t)c->panel[1].n;
-    return ((size_t)c->panel[0].n + 1) * (a1 + 1) + 2;
+    const size_t a1 = c->mode == DMX_MODE_SINGLE ? 0 : (size_t)c->panel[1].n_all;
+    return ((size_t)c->panel[0].n_all + 1) * (a1 + 1) + 2;
 }
 
 int ensure_pipeline(Ctx* c) {
@@ -358,7 +359,8 @@ void dmx_close(dmx_ctx* c) {
                     c->d_cl[1],     c->d_outc[0],   c->d_outc[1],  c->d_items, c->d_win, c->d_win2, c->d_linked, c->d_tasks, c->d_counters, c->d_shard,
                     c->d_counts,    c->d_panel[0],  c->d_panel[1], c->d_pieces[0], c->d_pieces[1],
                     c->d_ftask, c->d_stage, c->d_pieces_flat, c->d_cells[0], c->d_cells[1], c->d_cells[2],
-                    c->d_cells[3]};
+                    c->d_cells[3], c->d_ends[0], c->d_ends[1], c->d_panel_all[0],
+                    c->d_panel_all[1]};
     for (void* b : bufs)
         if (b) hipFree(b);
     for (int r = 0; r < 2; ++r)
@@ -402,16 +404,70 @@ static int set_panel_impl(dmx_ctx* c, int round, const char* const* seqs, const 
                           const int* wheres, int n, double max_errors, int min_overlap,
                           int flags);
 
+static int set_panel_ends(dmx_ctx* c, int round, const char* const* seqs, const int* lens,
+                          const int* wheres, const int* min_overlaps, int n, double max_errors,
+                          int min_overlap, int rc);
+
+constexpr int kRestrictBits = DMX_ANCHORED | DMX_NONINTERNAL;
+
+// A per-adapter `where`: one of DMX_FRONT / DMX_BACK, at most one of the restricted bits.
+static bool where_valid(int w) {
+    const int side = w & (DMX_FRONT | DMX_BACK);
+    return (w & ~(DMX_FRONT | DMX_BACK | kRestrictBits)) == 0 &&
+           (side == DMX_FRONT || side == DMX_BACK) && (w & kRestrictBits) != kRestrictBits;
+}
+
 int dmx_set_panel(dmx_ctx* c, int round, const char* const* seqs, const int* lens, int n,
                   double max_errors, int min_overlap, int flags) {
-    return set_panel_impl(c, round, seqs, lens, nullptr, n, max_errors, min_overlap, flags);
+    if (!(flags & kRestrictBits))
+        return set_panel_impl(c, round, seqs, lens, nullptr, n, max_errors, min_overlap, flags);
+    if (!c || n <= 0 || n > kMaxAdapters) return DMX_E_INVALID;
+    if (!where_valid(flags & ~DMX_RC)) {
+        c->err = "panel flags: one of DMX_FRONT / DMX_BACK, at most one of DMX_ANCHORED / "
+                 "DMX_NONINTERNAL";
+        return DMX_E_INVALID;
+    }
+    int wheres[kMaxAdapters];
+    for (int a = 0; a < n; ++a) wheres[a] = flags & ~DMX_RC;
+    return set_panel_ends(c, round, seqs, lens, wheres, nullptr, n, max_errors, min_overlap,
+                          (flags & DMX_RC) ? 1 : 0);
+}
+
+int dmx_set_panel_ex(dmx_ctx* c, int round, const char* const* seqs, const int* lens,
+                     const int* wheres, const int* min_overlaps, int n, double max_errors,
+                     int min_overlap, int rc) {
+    if (!c || !wheres || !seqs || !lens) return DMX_E_INVALID;
+    if (n <= 0 || n > kMaxAdapters) {
+        c->err = "panel must hold 1..64 adapters";
+        return DMX_E_INVALID;
+    }
+    bool plain = true;
+    for (int a = 0; a < n; ++a) {
+        if (!where_valid(wheres[a])) {
+            c->err = "adapter " + std::to_string(a) + ": where must be DMX_FRONT or DMX_BACK, "
+                     "alone or with one of DMX_ANCHORED / DMX_NONINTERNAL";
+            return DMX_E_INVALID;
+        }
+        plain &= !(wheres[a] & kRestrictBits) && (!min_overlaps || min_overlaps[a] == min_overlap);
+    }
+    if (plain)   // nothing new asked for: dmx_set_panel_mixed itself
+        return set_panel_impl(c, round, seqs, lens, wheres, n, max_errors, min_overlap,
+                              DMX_FRONT | (rc ? DMX_RC : 0));
+    return set_panel_ends(c, round, seqs, lens, wheres, min_overlaps, n, max_errors, min_overlap,
+                          rc);
 }
 
 int dmx_set_panel_mixed(dmx_ctx* c, int round, const char* const* seqs, const int* lens,
                         const int* wheres, int n, double max_errors, int min_overlap, int rc) {
     if (!wheres) return DMX_E_INVALID;
-    for (int a = 0; a < n; ++a)
-        if (wheres[a] != DMX_FRONT && wheres[a] != DMX_BACK) return DMX_E_INVALID;
+    bool plain = true;
+    for (int a = 0; a < n; ++a) plain &= wheres[a] == DMX_FRONT || wheres[a] == DMX_BACK;
+    if (!plain) {
+        for (int a = 0; a < n; ++a)
+            if (!where_valid(wheres[a])) return DMX_E_INVALID;
+        return dmx_set_panel_ex(c, round, seqs, lens, wheres, nullptr, n, max_errors, min_overlap,
+                                rc);
+    }
     return set_panel_impl(c, round, seqs, lens, wheres, n, max_errors, min_overlap,
                           DMX_FRONT | (rc ? DMX_RC : 0));
 }
@@ -802,6 +858,9 @@ static int set_panel_impl(dmx_ctx* c, int round, const char* const* seqs, const 
     const int brc = build_panel(c, seqs, lens, wheres, n, max_errors, min_overlap, flags, hp, dp);
     if (brc) return brc;
     c->panel[round] = hp;
+    c->panel[round].n_all = n;
+    c->ends_n[round] = 0;
+    c->ends_remap[round] = false;
     ++c->panel_gen;
     c->ring_small[round] = hp.ring_small;
     c->band_ok[round] = true;
@@ -815,6 +874,126 @@ static int set_panel_impl(dmx_ctx* c, int round, const char* const* seqs, const 
     CK(hipMemcpy(c->d_panel[round], &dp, sizeof(dp), hipMemcpyHostToDevice));
     if (hp.piece_step)
         CK(hipMemcpy(c->d_pieces[round], &hp.pieces, sizeof(DevPieces), hipMemcpyHostToDevice));
+    return DMX_OK;
+}
+
+// A panel with restricted adapters or per-adapter minimum overlaps.  The
+// unrestricted adapters form the sub-panel the internal pipeline runs (build_panel, as for any
+// panel); every restricted adapter gets its tables from build_panel on itself alone, with its own
+// minimum overlap; finalize decodes against the whole panel.
+static int set_panel_ends(dmx_ctx* c, int round, const char* const* seqs, const int* lens,
+                          const int* wheres, const int* min_overlaps, int n, double max_errors,
+                          int min_overlap, int rc) {
+    if (!c || round < 0 || round > 1 || !seqs || !lens || !wheres) return DMX_E_INVALID;
+    if (n <= 0 || n > kMaxAdapters) {
+        c->err = "panel must hold 1..64 adapters";
+        return DMX_E_INVALID;
+    }
+    const int rcflag = rc ? DMX_RC : 0;
+    std::vector<const char*> sseq;
+    std::vector<int> slen, swhere, sidx;
+    int sub_mo = -1;
+    for (int a = 0; a < n; ++a) {
+        if (!where_valid(wheres[a])) return DMX_E_INVALID;
+        if (wheres[a] & kRestrictBits) continue;
+        const int mo = min_overlaps ? min_overlaps[a] : min_overlap;
+        if (sub_mo >= 0 && mo != sub_mo) {
+            c->err = "the unrestricted adapters of a panel must share one minimum overlap";
+            return DMX_E_UNSUPPORTED;
+        }
+        sub_mo = mo;
+        sseq.push_back(seqs[a]);
+        slen.push_back(lens[a]);
+        swhere.push_back(wheres[a]);
+        sidx.push_back(a);
+    }
+    HostPanel hp;
+    std::unique_ptr<DevPanel> dp(new DevPanel()), all(new DevPanel());
+    std::unique_ptr<DevEnds> de(new DevEnds());
+    memset(dp.get(), 0, sizeof(DevPanel));
+    memset(all.get(), 0, sizeof(DevPanel));
+    memset(de.get(), 0, sizeof(DevEnds));
+    if (!sseq.empty()) {
+        const int brc = build_panel(c, sseq.data(), slen.data(), swhere.data(), (int)sseq.size(),
+                                    max_errors, sub_mo, DMX_FRONT | rcflag, hp, *dp);
+        if (brc) return brc;
+    } else {   // restricted adapters only: no screen, no scan
+        hp = HostPanel();
+        hp.set = true;
+        hp.n_orient = rc ? 2 : 1;
+        hp.reach = panel_reach(hp, *dp);
+        dp->n_orient = hp.n_orient;
+        dp->near_shared = -1;
+    }
+    bool band_ok = true;
+    int kkmax = 0;
+    for (int s = 0; s < hp.n; ++s) {
+        band_ok &= hp.ad[s].kk <= 7;
+        kkmax = std::max(kkmax, (int)hp.ad[s].kk);
+        all->ad[sidx[s]] = hp.ad[s];
+        de->remap[s] = (uint8_t)sidx[s];
+        if (sidx[s] != s) de->remap_on = 1;
+    }
+    for (int a = 0; a < n; ++a) {
+        if (!(wheres[a] & kRestrictBits)) continue;
+        const bool front = (wheres[a] & DMX_FRONT) != 0;
+        const bool anchored = (wheres[a] & DMX_ANCHORED) != 0;
+        const int mo = anchored ? lens[a] : (min_overlaps ? min_overlaps[a] : min_overlap);
+        if (mo < 1) {
+            c->err = "adapter " + std::to_string(a) + ": minimum overlap must be >= 1";
+            return DMX_E_INVALID;
+        }
+        Ctx tmp;   // never opened: one adapter's tables, no filter blocks
+        tmp.no_filter = tmp.no_verify = tmp.no_pieces = true;
+        HostPanel h1;
+        std::unique_ptr<DevPanel> d1(new DevPanel());
+        const char* s1[1] = {seqs[a]};
+        const int l1[1] = {lens[a]};
+        const int brc = build_panel(&tmp, s1, l1, nullptr, 1, max_errors, mo,
+                                    front ? DMX_FRONT : DMX_BACK, h1, *d1);
+        if (brc) {
+            c->err = "adapter " + std::to_string(a) + ": " + tmp.err;
+            return brc;
+        }
+        const DevAdapter& src = h1.ad[0];
+        EndAdapter& e = de->ad[de->n++];
+        for (int k = 0; k < 4; ++k) e.peq[k] = src.peq[k];
+        memcpy(e.acc, src.acc, sizeof(e.acc));
+        memcpy(e.pacc, src.pacc, sizeof(e.pacc));
+        e.m = src.m;
+        e.k = src.k;
+        e.kk = src.kk;
+        e.orig = (uint8_t)a;
+        e.type = front ? (anchored ? kEndPrefix : kEndFrontX) : (anchored ? kEndSuffix : kEndBackX);
+        all->ad[a] = src;
+        hp.nonpos |= h1.nonpos;
+        hp.ring_small &= h1.ring_small;
+        band_ok &= src.kk <= 7;
+    }
+    hp.n_all = n;
+    all->n_adapters = n;
+    all->n_orient = hp.n_orient;
+    all->near_shared = -1;
+    de->n_orient = hp.n_orient;
+    de->n_sub = hp.n;
+    c->panel[round] = hp;
+    c->ends_n[round] = de->n;
+    c->ends_remap[round] = de->remap_on != 0;
+    ++c->panel_gen;
+    c->ring_small[round] = hp.ring_small;
+    c->band_ok[round] = band_ok;
+    c->band_wide[round] = kkmax > 5;
+    CK(hipSetDevice(c->device));
+    CK(hipMemcpy(c->d_panel[round], dp.get(), sizeof(DevPanel), hipMemcpyHostToDevice));
+    if (hp.piece_step)
+        CK(hipMemcpy(c->d_pieces[round], &hp.pieces, sizeof(DevPieces), hipMemcpyHostToDevice));
+    if (de->n) {
+        if (!c->d_ends[round]) CK(hipMalloc((void**)&c->d_ends[round], sizeof(DevEnds)));
+        if (!c->d_panel_all[round])
+            CK(hipMalloc((void**)&c->d_panel_all[round], sizeof(DevPanel)));
+        CK(hipMemcpy(c->d_ends[round], de.get(), sizeof(DevEnds), hipMemcpyHostToDevice));
+        CK(hipMemcpy(c->d_panel_all[round], all.get(), sizeof(DevPanel), hipMemcpyHostToDevice));
+    }
     return DMX_OK;
 }
 
@@ -993,9 +1172,28 @@ int dmx_panel_piece_pairs(const char* const* seqs, const int* lens, int n, doubl
 int dmx_panel_reach(const char* const* seqs, const int* lens, const int* wheres, int n,
                     double max_errors, int min_overlap, int flags, int32_t* out, int n_out) {
     if (!out || n_out < 6) return DMX_E_INVALID;
-    if (wheres) {   // dmx_set_panel_mixed's form
-        for (int a = 0; a < n; ++a)
-            if (wheres[a] != DMX_FRONT && wheres[a] != DMX_BACK) return DMX_E_INVALID;
+    // Restricted adapters (DMX_ANCHORED / DMX_NONINTERNAL in wheres or flags) take no part in the
+    // internal pipeline: the reach is that of the sub-panel of the others.  The end-window stage
+    // gathers view positions [0, len + 15] only, whatever the view's length: inside every
+    // panel's reach.
+    std::vector<const char*> sseq;
+    std::vector<int> slen, swhere;
+    if (wheres || (flags & kRestrictBits)) {
+        if (!seqs || !lens || n <= 0 || n > kMaxAdapters) return DMX_E_INVALID;
+        for (int a = 0; a < n; ++a) {
+            const int w = wheres ? wheres[a] : (flags & ~DMX_RC);
+            if (!where_valid(w)) return DMX_E_INVALID;
+            if (w & kRestrictBits) continue;
+            sseq.push_back(seqs[a]);
+            slen.push_back(lens[a]);
+            swhere.push_back(w);
+        }
+        if ((int)sseq.size() != n) {
+            seqs = sseq.data();
+            lens = slen.data();
+            wheres = swhere.data();
+            n = (int)sseq.size();
+        }
         flags = DMX_FRONT | (flags & DMX_RC);
     }
     Ctx tmp;   // never opened: build_panel reads only the A/B switches dmx_open would set
@@ -1006,6 +1204,13 @@ int dmx_panel_reach(const char* const* seqs, const int* lens, const int* wheres,
     HostPanel hp;
     DevPanel dp;
     PanelReach r;
+    if (n == 0) {   // restricted adapters only
+        memset(&dp, 0, sizeof(dp));
+        r = panel_reach(hp, dp);
+        const int32_t v0[6] = {r.pre_raw, r.pre, r.post, r.need_pre, r.need_post, kGuardNt};
+        for (int i = 0; i < 6; ++i) out[i] = v0[i];
+        return DMX_OK;
+    }
     const int rc = build_panel(&tmp, seqs, lens, wheres, n, max_errors, min_overlap, flags, hp, dp);
     if (rc == DMX_OK) r = hp.reach;
     else if (rc == DMX_E_UNSUPPORTED && hp.set) r = hp.reach;   // refused by the reach check
@@ -1047,11 +1252,27 @@ int dmx_debug_bounds_selftest(dmx_ctx* c, uint32_t* out3) {
     return bounds_selftest(c, out3);
 }
 
+// One round's matches into its winner slots: the internal pipeline for the unrestricted adapters
+// (all of them, for every panel without restricted ones), then the end-window stage.
+static int run_round(dmx_ctx* c, int round, hipStream_t st) {
+    int rc;
+    if (c->panel[round].n > 0) {
+        if ((rc = launch_round(c, round, st))) return rc;
+    } else {   // restricted adapters only: no screen, no scan; the stage times read as 0
+        for (int e = 0; e < 3; ++e) CK(hipEventRecord(c->ev[3 * round + e], st));
+    }
+    return c->ends_n[round] ? launch_ends(c, round, st) : DMX_OK;
+}
+
 int dmx_exec(dmx_ctx* c) {
     if (!c) return DMX_E_INVALID;
     if (!c->panel[0].set || (c->mode != DMX_MODE_SINGLE && !c->panel[1].set)) {
         c->err = "panels not set for this mode";
         return DMX_E_STATE;
+    }
+    if (c->mode == DMX_MODE_LINKED && (c->ends_n[0] || c->ends_n[1])) {
+        c->err = "linked mode does not take anchored / non-internal adapters";
+        return DMX_E_UNSUPPORTED;
     }
     CK(hipSetDevice(c->device));
     int rc = ensure_pipeline(c);
@@ -1072,12 +1293,12 @@ int dmx_exec(dmx_ctx* c) {
                                                      : c->n_reads * (c->orient_slot[0] ? 2 : 1);
     CK(hipMemsetAsync(c->d_winner[0], 0xFF, slots0 * sizeof(unsigned long long), st));
     if ((rc = prepare_flat(c, st))) return rc;
-    if ((rc = launch_round(c, 0, st))) return rc;
+    if ((rc = run_round(c, 0, st))) return rc;
     if ((rc = launch_finalize(c, 0, st))) return rc;
     if (c->mode != DMX_MODE_SINGLE) {
         CK(hipMemsetAsync(c->d_winner[1], 0xFF, c->item_cap * (c->orient_slot[1] ? 2 : 1) *
                                                      sizeof(unsigned long long), st));
-        if ((rc = launch_round(c, 1, st))) return rc;
+        if ((rc = run_round(c, 1, st))) return rc;
         if ((rc = launch_finalize(c, 1, st))) return rc;
     }
     c->executed = true;
@@ -1134,7 +1355,7 @@ int dmx_stats(dmx_ctx* c, float* stage_ms, int n_stage, uint64_t* counts, int n_
     CK(hipSetDevice(c->device));
     CK(hipStreamSynchronize(c->stream));
     const int rounds = c->mode == DMX_MODE_SINGLE ? 1 : 2;
-    float t[17] = {};
+    float t[19] = {};
     for (int r = 0; r < rounds; ++r) {
         hipEventElapsedTime(&t[3 * r + 0], c->ev[3 * r + 0], c->ev[3 * r + 1]);
         hipEventElapsedTime(&t[3 * r + 1], c->ev[3 * r + 1], c->ev[3 * r + 2]);
@@ -1150,7 +1371,9 @@ int dmx_stats(dmx_ctx* c, float* stage_ms, int n_stage, uint64_t* counts, int n_
         }
     }
     hipEventElapsedTime(&t[6], c->ev[8], c->ev[6 + rounds - 1]);
-    for (int i = 0; i < n_stage && i < 17; ++i) stage_ms[i] = t[i];
+    for (int r = 0; r < rounds; ++r)
+        if (c->ends_n[r]) hipEventElapsedTime(&t[17 + r], c->ev[17 + 2 * r], c->ev[18 + 2 * r]);
+    for (int i = 0; i < n_stage && i < 19; ++i) stage_ms[i] = t[i];
     uint32_t cnt[32];
     int list_ovf = 0;
     CK(read_counters(c, cnt, &list_ovf));
@@ -1162,7 +1385,7 @@ int dmx_stats(dmx_ctx* c, float* stage_ms, int n_stage, uint64_t* counts, int n_
                 cnt[23], cnt[6], cnt[7], cnt[8], cnt[9]);
     if (counts) {
         const bool b0 = c->band_ok[0] && !c->force_ring, b1 = c->band_ok[1] && !c->force_ring;
-        const uint64_t v[14] = {cnt[0],
+        const uint64_t v[18] = {cnt[0],
                                 cnt[1],
                                 c->panel[0].verify ? cnt[10] : cnt[4],
                                 c->panel[1].verify ? cnt[11] : cnt[5],
@@ -1175,8 +1398,12 @@ int dmx_stats(dmx_ctx* c, float* stage_ms, int n_stage, uint64_t* counts, int n_
                                 cnt[12],
                                 cnt[13],
                                 cnt[14],
-                                cnt[15]};
-        for (int i = 0; i < n_counts && i < 14; ++i) counts[i] = v[i];
+                                cnt[15],
+                                cnt[28],
+                                cnt[29],
+                                cnt[30],
+                                cnt[31]};
+        for (int i = 0; i < n_counts && i < 18; ++i) counts[i] = v[i];
     }
     if (flags) {
         int f = (int)cnt[3];
@@ -1631,8 +1858,8 @@ int dmx_run_multi(dmx_ctx* const* ctxs, int n_ctx, const uint32_t* seq2b, const 
     dmx_ctx* c0 = ctxs[0];
     if (n_reads && (!seq2b || !nmask || !offsets || !lens || !out)) return DMX_E_INVALID;
     for (int k = 1; k < n_ctx; ++k) {
-        if (!ctxs[k] || ctxs[k]->mode != c0->mode || ctxs[k]->panel[0].n != c0->panel[0].n ||
-            ctxs[k]->panel[1].n != c0->panel[1].n) {
+        if (!ctxs[k] || ctxs[k]->mode != c0->mode || ctxs[k]->panel[0].n_all != c0->panel[0].n_all ||
+            ctxs[k]->panel[1].n_all != c0->panel[1].n_all) {
             c0->err = "dmx_run_multi: contexts must share mode and panels";
             return DMX_E_INVALID;
         }

@@ -359,6 +359,29 @@ __host__ __device__ inline int key_delta(uint64_t k) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// End-window stage (dmx_ends.hip): the restricted adapters of a panel (cutadapt's
+// PrefixAdapter ^A, NonInternalFrontAdapter XA, SuffixAdapter A$, NonInternalBackAdapter AX).
+// ---------------------------------------------------------------------------------------------
+enum EndType : uint8_t { kEndPrefix = 0, kEndFrontX = 1, kEndSuffix = 2, kEndBackX = 3 };
+struct EndAdapter {
+    uint64_t peq[4];    // DevAdapter's, codes A, C, G, T (a masked read position matches nothing)
+    int8_t acc[72];     // DevAdapter's, built with this adapter's own min_overlap
+    int8_t pacc[72];
+    uint8_t m, k, type, orig;   // length, int(rate * m), EndType, index in the whole panel
+    int8_t kk;
+    uint8_t pad[3];
+};
+static_assert(sizeof(EndAdapter) == 184, "EndAdapter layout");
+struct DevEnds {
+    int32_t n;          // restricted adapters
+    int32_t n_orient;   // 2 with --rc
+    int32_t n_sub;      // unrestricted adapters (the sub-panel the internal pipeline runs)
+    int32_t remap_on;   // some sub-panel index differs from its index in the whole panel
+    uint8_t remap[kMaxAdapters];   // sub-panel index -> index in the whole panel (increasing)
+    EndAdapter ad[kMaxAdapters];
+};
+
+// ---------------------------------------------------------------------------------------------
 // Bounds of the device buffers.  Release builds: empty, every check is `true`.
 // DMX_DEBUG_BOUNDS builds (dmx/libdmx_bounds.so): every gather of the packed batch and every
 // slot / item / result / count access is checked against its buffer's extent, which the host
@@ -370,7 +393,8 @@ enum BoundsBuf : uint32_t {
     kBufSeq = 1, kBufMask = 2, kBufSlot = 3, kBufItem = 4, kBufRes = 5, kBufCount = 6,
     kBufRead = 7, kBufLinked = 8, kBufCand = 9, kBufChop = 10, kBufPd = 11,
     kBufPaTrace = 12, kBufPaOps = 13, kBufGaCols = 14, kBufRdCols = 15, kBufRrCols = 16,
-    kBufHistBins = 17, kBufRaCols = 18, kBufRaTable = 19, kBufRaBest = 20
+    kBufHistBins = 17, kBufRaCols = 18, kBufRaTable = 19, kBufRaBest = 20,
+    kBufEndsSeq = 21, kBufEndsMask = 22, kBufEndsSlot = 23, kBufEndsItem = 24, kBufEndsRead = 25
 };
 enum BoundsKernel : int32_t {
     kKerFilter = 1, kKerVerify, kKerScreen, kKerScreen4, kKerWscan, kKerScan, kKerBand0,
@@ -378,7 +402,7 @@ enum BoundsKernel : int32_t {
     kKerFin2L, kKerChop, kKerChopBig, kKerChopStart, kKerSelfTest, kKerPieces, kKerPairdist,
     kKerPairalign, kKerPairalignTb, kKerGroupalign, kKerGroupalignTb, kKerGroupalignMerge,
     kKerRowdist, kKerRowpair, kKerRowpairRc, kKerHithist, kKerRowassign,
-    kKerRowassignDecide, kKerRowassignFinish
+    kKerRowassignDecide, kKerRowassignFinish, kKerEnds, kKerEndsOrigin, kKerEndsRemap
 };
 constexpr int kBoundsRec = 24;     // d_counters[24..27]: kernel id + 1, buffer, index lo / hi
 

@@ -56,7 +56,8 @@ struct PanelReach {
 
 struct HostPanel {
     bool screen = false;      // index screen usable (filter + verify, index blocks 1..32)
-    int n = 0;
+    int n = 0;                // adapters of the internal pipeline (the unrestricted ones)
+    int n_all = 0;            // adapters of the whole panel: bins, counts, finalize
     int n_orient = 1;
     bool set = false;
     bool ring_small = true;
@@ -84,6 +85,13 @@ struct Ctx {
     HostPanel panel[2];
     DevPanel* d_panel[2] = {nullptr, nullptr};
     DevPieces* d_pieces[2] = {nullptr, nullptr};
+    // end-window stage: per round the number of restricted adapters (0: the
+    // stage does not run and nothing below is read), whether the internal pipeline's keys need
+    // their adapter index mapped back, the stage's tables and the whole panel for finalize
+    int ends_n[2] = {0, 0};
+    bool ends_remap[2] = {false, false};
+    DevEnds* d_ends[2] = {nullptr, nullptr};
+    DevPanel* d_panel_all[2] = {nullptr, nullptr};
 
     // resident batch
     size_t n_reads = 0, n_words = 0;
@@ -167,9 +175,10 @@ struct Ctx {
     bool screen_v1 = false;              // DMX_SCREEN_V1=1: one lane per (window, adapter) screen
     bool near_all = false;               // DMX_NEAR_ALL=1: near pieces keep every adapter's columns
     size_t n_counts = 0;
-    hipEvent_t ev[17] = {};   // [3r..3r+2] round r stages, [6+r] finalize, [8] start,
+    hipEvent_t ev[21] = {};   // [3r..3r+2] round r stages, [6+r] finalize, [8] start,
                               // [9+2r] after filter, [10+2r] after verify, [13+r] after screen,
-                              // [15+r] after the piece screen (its filter tasks follow)
+                              // [15+r] after the piece screen (its filter tasks follow),
+                              // [17+2r] / [18+2r] before / after the end-window stage
     bool executed = false;
     ChopState* chop = nullptr;   // dmx_chop_* state, created by dmx_chop_set
     PdState* pd = nullptr;       // dmx_pairdist buffers, created by its first call
@@ -225,6 +234,15 @@ inline bool band_round(const Ctx* c, int round) { return c->band_ok[round] && !c
 int launch_round(Ctx* c, int round, hipStream_t st);
 int prepare_flat(Ctx* c, hipStream_t st);   // the flat piece scan's index (dmx_kernels.hip)
 int launch_finalize(Ctx* c, int round, hipStream_t st);
+// The end-window stage of round `round` (dmx_ends.hip): maps the internal pipeline's adapter
+// indices back to the whole panel's where they differ, then one atomicMin per accepted
+// restricted-adapter match into the same winner slots (ring rounds: a second pass writes the
+// winner's origin).  Called between launch_round and launch_finalize when ends_n[round] > 0.
+int launch_ends(Ctx* c, int round, hipStream_t st);
+// The panel finalize decodes with: the whole panel where the round has restricted adapters.
+inline const DevPanel* final_panel(const Ctx* c, int round) {
+    return c->ends_n[round] ? c->d_panel_all[round] : c->d_panel[round];
+}
 // offs[i] -= g0 for a chunk's offsets uploaded as the caller gave them (stream st)
 int launch_rebase_offsets(uint64_t* offs, uint32_t n, uint64_t g0, hipStream_t st);
 // mask[idx[i] - base] = val[i] for the n staged exceptions at d_exc ([idx][val]); stream st

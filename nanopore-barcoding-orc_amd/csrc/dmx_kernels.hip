@@ -4627,14 +4627,16 @@ int bounds_check(Ctx* c, const char* where) {
         "pairalign_traceback_kernel", "groupalign_kernel", "groupalign_traceback_kernel",
         "groupalign_merge_kernel", "rowdist_kernel", "rowpair_kernel", "rowpair_rc_kernel",
         "lg_hist_kernel", "rowassign_kernel", "rowassign_decide_kernel",
-        "rowassign_finish_kernel"};
+        "rowassign_finish_kernel", "ends_kernel", "ends_origin_kernel", "ends_remap_kernel"};
     static const char* const kBuf[] = {"?", "seq", "nmask", "winner slots", "items", "results",
                                        "counts", "reads", "linked keys", "candidates", "chop",
                                        "pairdist scratch", "pairalign trace", "pairalign ops",
                                        "groupalign columns", "rowdist columns",
                                        "rowpair columns", "identity table",
                                        "rowassign columns", "rowassign tables",
-                                       "rowassign places"};
+                                       "rowassign places", "end-window seq",
+                                       "end-window nmask", "end-window winner slots",
+                                       "end-window items", "end-window reads"};
     uint32_t rec[4];
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess)
@@ -5034,8 +5036,8 @@ int launch_mask_scatter(uint32_t* mask, const uint32_t* d_exc, uint32_t n, uint3
 int launch_finalize(Ctx* c, int round, hipStream_t st) {
     FinalArgs F;
     F.lens = c->d_lens;
-    F.p0 = c->d_panel[0];
-    F.p1 = c->d_panel[1];
+    F.p0 = final_panel(c, 0);
+    F.p1 = final_panel(c, 1);
     F.winner = c->d_winner[round];
     F.origin = c->d_origin[round];
     F.okey = band_round(c, round) ? 1 : 0;
@@ -5044,8 +5046,8 @@ int launch_finalize(Ctx* c, int round, hipStream_t st) {
     F.n_items = c->d_counters + 2;
     F.n_reads = (uint32_t)c->n_reads;
     F.mode = c->mode;
-    F.A0 = c->panel[0].n;
-    F.A1 = c->mode == DMX_MODE_SINGLE ? 0 : c->panel[1].n;
+    F.A0 = c->panel[0].n_all;
+    F.A1 = c->mode == DMX_MODE_SINGLE ? 0 : c->panel[1].n_all;
     F.oslot = c->orient_slot[round] ? 1 : 0;
     F.counts = c->d_counts;
     F.winner0 = c->d_winner[0];

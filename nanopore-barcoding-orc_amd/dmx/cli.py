@@ -7,7 +7,8 @@ Drop-in for the executable the reference's scripts call (boundary = the cutadapt
   scripts/04_cleaning_primers.sh:377  cutadapt -j N -g F...R [-g F...R] --untrimmed-output=U -o O IN
   scripts/04_cleaning_primers.sh:507  cutadapt -j N -g F -a R ... -o O IN
 Supported subset: --action=trim, -e, -O, -j, --rc, -g/-a (file:, NAME=SEQ,
-SEQ, linked A...B with -g), -o (with {name} demultiplexing), --untrimmed-output,
+SEQ, anchored ^SEQ / SEQ$, non-internal XSEQ / SEQX, linked A...B with -g), -o (with {name}
+demultiplexing), --untrimmed-output,
 --discard-untrimmed, --json, -Z/--compression-level, FASTQ/FASTA(.gz) in and out.
 All matching runs on the GPU through libdmx (no CPU fallback): a missing extension or GPU is
 an error exit, so `set -euo pipefail` in the calling script aborts.
@@ -148,7 +149,10 @@ def run(argv=None, keep_contexts: bool = False) -> int:
                      "'{name2}_{name1}_{ds}.fastq.gz')")
     aset = panel.AdapterSet()
     for where, spec in args.adapters:
-        aset.add_spec(spec, where)
+        try:
+            aset.add_spec(spec, where)
+        except panel.SpecError as e:
+            _unsupported(str(e))
     ads = aset.adapters
     linked = aset.linked
     if linked and not all(isinstance(a, panel.LinkedAdapter) for a in ads):
@@ -324,7 +328,9 @@ def _configure(ctx, ads, linked, args):
         ctx.set_mode(lib.MODE_LINKED)
         return
     wheres = [lib.DMX_FRONT if a.where == "front" else lib.DMX_BACK for a in ads]
-    if len(set(wheres)) == 1:
+    if any(a.restrict for a in ads):   # anchored / non-internal: dmx_set_panel_ex
+        ctx.set_adapters(0, ads, args.rc, args.error_rate, args.overlap)
+    elif len(set(wheres)) == 1:
         ctx.set_panel(0, [a.seq for a in ads], wheres[0] | (lib.DMX_RC if args.rc else 0),
                       args.error_rate, args.overlap)
     else:

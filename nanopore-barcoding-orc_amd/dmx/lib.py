@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("DMX_LIBDMX") or os.path.join(
     os.environ.get("DMX_LIBDIR") or HERE, "libdmx_bounds.so" if BOUNDS else "libdmx.so")
 
 DMX_FRONT, DMX_BACK, DMX_RC = 0x01, 0x02, 0x10
+DMX_ANCHORED, DMX_NONINTERNAL = 0x04, 0x08   # with DMX_FRONT / DMX_BACK: ^A, A$ / XA, AX
 MODE_SINGLE, MODE_TWO_ROUND, MODE_LINKED = 0, 1, 2
 PACK_PAD = 64
 
@@ -50,7 +51,7 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_rowhits", "dmx_rowhits_host", "dmx_panel_piece_pairs", "dmx_hithist",
            "dmx_pairhits_cross", "dmx_hitgroups_within", "dmx_hithist_host",
            "dmx_pairhits_cross_host", "dmx_hitgroups_within_host", "dmx_panel_near_shared",
-           "dmx_rowassign", "dmx_rowassign_host"]
+           "dmx_rowassign", "dmx_rowassign_host", "dmx_set_panel_ex", "dmx_ends_host"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -114,6 +115,15 @@ def load() -> ctypes.CDLL:
                                       ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
                                       ctypes.c_double, c_int, c_int]
     L.dmx_set_mode.argtypes = [P, c_int]
+    # (guarded only so that DMX_LIBDMX / DMX_ALLOW_ABI can load an older in-tree build for an
+    # A/B run of panels that need neither call; EXPORTS and tests/test_host.py require both)
+    if hasattr(L, "dmx_set_panel_ex"):
+        L.dmx_set_panel_ex.argtypes = [P, c_int, ctypes.POINTER(ctypes.c_char_p),
+                                       ctypes.POINTER(c_int), ctypes.POINTER(c_int), P, c_int,
+                                       ctypes.c_double, c_int, c_int]
+        L.dmx_ends_host.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_int),
+                                    ctypes.POINTER(c_int), P, c_int, ctypes.c_double, c_int,
+                                    c_int, P, P, c_u64p, P, c_size, P]
     L.dmx_pack_words.argtypes = [ctypes.c_uint64, c_size]
     L.dmx_pack_words.restype = c_size
     L.dmx_pack.argtypes = [P, c_u64p, P, c_size, P, P, c_u64p]
@@ -280,6 +290,36 @@ def pack(ascii_blob: np.ndarray, offsets: np.ndarray, lengths: np.ndarray) -> Pa
     return Packed(seq, nm, out_offs, lens)
 
 
+def adapter_wheres(ads) -> list:
+    """The dmx_set_panel_ex `wheres` of parsed single adapters (dmx.panel.Adapter)."""
+    bits = {"": 0, "anchored": DMX_ANCHORED, "noninternal": DMX_NONINTERNAL}
+    return [(DMX_FRONT if a.where == "front" else DMX_BACK) | bits[getattr(a, "restrict", "")]
+            for a in ads]
+
+
+def ends_host(seqs, wheres, p: "Packed", rc: bool, max_errors: float = 0.1, min_overlap: int = 3,
+              min_overlaps=None) -> np.ndarray:
+    """Host only (no GPU): one single round of the panel dmx_set_panel_ex would build, by the
+    full-matrix DP of dmx_ends_host; RESULT_DTYPE records as Context.run writes them."""
+    L = load()
+    arr = (ctypes.c_char_p * len(seqs))(*[s.encode("ascii") for s in seqs])
+    lens = (ctypes.c_int * len(seqs))(*[len(s) for s in seqs])
+    wh = (ctypes.c_int * len(seqs))(*wheres)
+    mo = None
+    if min_overlaps is not None:
+        mo = (ctypes.c_int * len(seqs))(*[int(min_overlap if x is None else x)
+                                          for x in min_overlaps])
+    out = np.zeros(p.n_reads, dtype=RESULT_DTYPE)
+    rc_ = L.dmx_ends_host(arr, lens, wh, mo, len(seqs), float(max_errors), int(min_overlap),
+                          int(bool(rc)), p.seq2b.ctypes.data, p.nmask.ctypes.data,
+                          p.offsets.ctypes.data, p.lengths.ctypes.data, p.n_reads,
+                          out.ctypes.data)
+    if rc_ != 0:
+        msg = L.dmx_last_error(None)
+        raise DmxError(f"dmx_ends_host failed ({rc_}): {msg.decode() if msg else ''}")
+    return out
+
+
 class Context:
     """One device context (include/dmx.h: one per GPU, one host thread per context)."""
 
@@ -332,6 +372,37 @@ class Context:
                                                 float(max_errors), int(min_overlap), int(rc)),
                     "dmx_set_panel_mixed")
         self.panel_sizes[rnd] = len(seqs)
+
+    def set_panel_ex(self, rnd: int, seqs, wheres, rc: bool, max_errors: float = 0.1,
+                     min_overlap: int = 3, min_overlaps=None):
+        """dmx_set_panel_ex: wheres[a] = DMX_FRONT / DMX_BACK, alone or with DMX_ANCHORED /
+        DMX_NONINTERNAL; min_overlaps[a] (None entries and None: min_overlap)."""
+        arr = (ctypes.c_char_p * len(seqs))(*[s.encode("ascii") for s in seqs])
+        lens = (ctypes.c_int * len(seqs))(*[len(s) for s in seqs])
+        wh = (ctypes.c_int * len(seqs))(*wheres)
+        mo = None
+        if min_overlaps is not None:
+            mo = (ctypes.c_int * len(seqs))(*[int(min_overlap if x is None else x)
+                                              for x in min_overlaps])
+        self._check(self._L.dmx_set_panel_ex(self._h, rnd, arr, lens, wh, mo, len(seqs),
+                                             float(max_errors), int(min_overlap), int(rc)),
+                    "dmx_set_panel_ex")
+        self.panel_sizes[rnd] = len(seqs)
+
+    def set_adapters(self, rnd: int, ads, rc: bool, max_errors: float = 0.1,
+                     min_overlap: int = 3):
+        """Round rnd's panel from parsed single adapters (dmx.panel.Adapter): one uniform
+        unrestricted panel is dmx_set_panel, a mix of -g and -a dmx_set_panel_mixed, and a panel
+        with anchored / non-internal adapters dmx_set_panel_ex."""
+        seqs = [a.seq for a in ads]
+        wheres = adapter_wheres(ads)
+        if any(w & (DMX_ANCHORED | DMX_NONINTERNAL) for w in wheres):
+            self.set_panel_ex(rnd, seqs, wheres, rc, max_errors, min_overlap,
+                              [getattr(a, "min_overlap", None) for a in ads])
+        elif len(set(wheres)) == 1:
+            self.set_panel(rnd, seqs, wheres[0] | (DMX_RC if rc else 0), max_errors, min_overlap)
+        else:
+            self.set_panel_mixed(rnd, seqs, wheres, rc, max_errors, min_overlap)
 
     def bounds_selftest(self):
         """DMX_DEBUG_BOUNDS builds: (return code, message, the kernel's 3 outputs)."""
@@ -747,19 +818,21 @@ class Context:
         return buf.view(CAND_DTYPE if what in (DBG_CANDS0, DBG_CANDS1) else WINDOW_DTYPE)
 
     def stats(self):
-        ms = (ctypes.c_float * 17)()
-        cl = np.zeros(14, dtype=np.uint64)
+        ms = (ctypes.c_float * 19)()
+        cl = np.zeros(18, dtype=np.uint64)
         fl = ctypes.c_int()
-        self._check(self._L.dmx_stats(self._h, ms, 17, cl.ctypes.data, 14, ctypes.byref(fl)),
+        self._check(self._L.dmx_stats(self._h, ms, 19, cl.ctypes.data, 18, ctypes.byref(fl)),
                     "dmx_stats")
         # filterN: the whole filter stage (with the piece screen, when on: piecesN is its part)
         names = ["scan0", "resolve0", "finalize0", "scan1", "resolve1", "finalize1", "total",
                  "filter0", "verify0", "filter1", "verify1", "screen0", "wscan0", "screen1",
-                 "wscan1", "pieces0", "pieces1"]
+                 "wscan1", "pieces0", "pieces1", "ends0", "ends1"]
         return {"ms": dict(zip(names, list(ms))), "clusters": cl[:2].tolist(),
                 "windows": cl[2:4].tolist(), "resolved": cl[4:6].tolist(),
                 "traces": cl[6:8].tolist(), "windows_raw": cl[8:10].tolist(),
                 "tasks": cl[10:12].tolist(), "filter_tasks": cl[12:14].tolist(),
+                # end-window stage: triples that ran the exact DP / that it looked at
+                "ends_dp": cl[14:16].tolist(), "ends_seen": cl[16:18].tolist(),
                 "flags": fl.value}
 
 

@@ -195,8 +195,12 @@ def run(argv=None) -> int:
     os.makedirs(os.path.join(outdir, "SP5"), exist_ok=True)
     os.makedirs(os.path.join(outdir, "SP27"), exist_ok=True)
     aset1, aset2 = panel.AdapterSet(), panel.AdapterSet()
-    aset1.add_spec(f"file:{args.sp5}", "front")
-    aset2.add_spec(f"file:{args.sp27}", "back")
+    try:   # records may carry ^ / X (--sp5) and $ / X (--sp27) markers
+        aset1.add_spec(f"file:{args.sp5}", "front")
+        aset2.add_spec(f"file:{args.sp27}", "back")
+    except panel.SpecError as e:
+        print(f"dmx-demux-loop: error: {e}", file=sys.stderr)
+        return 2
     ads1, ads2 = aset1.adapters, aset2.adapters
     n1, n2 = [a.name for a in ads1], [a.name for a in ads2]
 
@@ -244,8 +248,12 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
     reo = sink1 = sink2 = None
     marks.append(("open", time.perf_counter() - _T_IMPORT))
     for ctx in ctxs:
-        ctx.set_panel(0, [a.seq for a in ads1], lib.DMX_FRONT | lib.DMX_RC, args.e_rate, 3)
-        ctx.set_panel(1, [a.seq for a in ads2], lib.DMX_BACK | lib.DMX_RC, args.e_rate, 3)
+        if any(a.restrict for a in ads1 + ads2):   # ^, $ or X markers in the panel files
+            ctx.set_adapters(0, ads1, True, args.e_rate, 3)
+            ctx.set_adapters(1, ads2, True, args.e_rate, 3)
+        else:
+            ctx.set_panel(0, [a.seq for a in ads1], lib.DMX_FRONT | lib.DMX_RC, args.e_rate, 3)
+            ctx.set_panel(1, [a.seq for a in ads2], lib.DMX_BACK | lib.DMX_RC, args.e_rate, 3)
         ctx.set_mode(lib.MODE_TWO_ROUND)
 
     st1 = Stats(ads1)

@@ -6,6 +6,12 @@ scripts/04_cleaning_primers.sh:377 `-g FWD...REV`, :476-498 `-g SEQ` / `-a SEQ`)
   * `file:PATH`: one adapter per FASTA record; name = first word of the header line;
   * `NAME=SEQ` or `SEQ`: a literal adapter, auto-named "1", "2", ... in command-line order;
   * `A...B`: a linked adapter (front A, back B);
+  * `-g ^SEQ` / `-a SEQ$`: anchored (PrefixAdapter / SuffixAdapter: the whole adapter at the read
+    start / end, minimum overlap = its length whatever -O says); `-g XSEQ` / `-a SEQX`:
+    non-internal (NonInternalFrontAdapter / NonInternalBackAdapter; any number of X is stripped).
+    `^` or a leading X with -a, `$` or a trailing X with -g, `^` with a leading X and `$` with a
+    trailing X are refused (SpecError), as parser.py refuses them; the markers are read per
+    record of a `file:` panel;
   * sequences uppercased with U -> T (upstream parser.py; UNVERIFIED).
 The panels in the reference have no trailing newline (M13_amplicon_indices_forward.fa:24) and
 blank lines (RNA_primers.fa:5); both are tolerated.
@@ -57,11 +63,57 @@ def read_fasta(path: str) -> list[tuple[str, str]]:
     return recs
 
 
+class SpecError(ValueError):
+    """An adapter specification cutadapt refuses, or one outside the implemented subset: the
+    command line exits with status 2 and this message."""
+
+
 @dataclass
 class Adapter:
     name: str
     seq: str
     where: str            # "front" (-g) or "back" (-a)
+    restrict: str = ""    # "", "anchored" (^SEQ / SEQ$) or "noninternal" (XSEQ / SEQX)
+    min_overlap: int | None = None   # None: the call's -O; anchored: the adapter's length
+
+    @property
+    def type_name(self) -> str:
+        """The "type" of this adapter's end in the JSON report: cutadapt's anchored_five_prime,
+        noninternal_five_prime, anchored_three_prime, noninternal_three_prime; an unrestricted
+        adapter keeps the "regular" this report has always written."""
+        end = "five_prime" if self.where == "front" else "three_prime"
+        return f"{self.restrict}_{end}" if self.restrict else "regular"
+
+
+def split_markers(spec: str, where: str) -> tuple[str, str]:
+    """(sequence, restriction) of one single-adapter specification (parser.py
+    _parse_not_linked / _restriction_to_class): restriction is "", "anchored" or
+    "noninternal"."""
+    s = spec.strip()
+    front = back = ""
+    if s.startswith("^"):
+        front, s = "anchored", s[1:]
+    if s.upper().startswith("X"):
+        if front:
+            raise SpecError(f"adapter {spec!r}: either '^' (anchored) or a leading 'X' "
+                            "(non-internal), not both")
+        front, s = "noninternal", s.lstrip("xX")
+    if s.endswith("$"):
+        back, s = "anchored", s[:-1]
+    if s.upper().endswith("X"):
+        if back:
+            raise SpecError(f"adapter {spec!r}: either '$' (anchored) or a trailing 'X' "
+                            "(non-internal), not both")
+        back, s = "noninternal", s.rstrip("xX")
+    if front and back:
+        raise SpecError(f"adapter {spec!r}: restricted at both ends; use a linked adapter")
+    if where == "front" and back:
+        raise SpecError(f"adapter {spec!r}: '$' or a trailing 'X' belongs to a 3' adapter "
+                        "(-a), not to -g")
+    if where == "back" and front:
+        raise SpecError(f"adapter {spec!r}: '^' or a leading 'X' belongs to a 5' adapter "
+                        "(-g), not to -a")
+    return s, front or back
 
 
 @dataclass
@@ -82,10 +134,17 @@ class AdapterSet:
 
     def add_spec(self, spec: str, where: str):
         """Add one -g/-a argument."""
-        if spec.startswith("file:"):
-            for header, seq in read_fasta(spec[5:]):
+        # `-g ^file:PATH` / `-a file:PATH$` anchor every record of the file (cutadapt's documented
+        # demultiplexing form); records may also carry their own markers
+        pre = "^" if spec.startswith("^file:") else ""
+        if pre or spec.startswith("file:"):
+            path = spec[len(pre) + 5:]
+            post = ""
+            if path.endswith("$") and not os.path.exists(path):
+                path, post = path[:-1], "$"
+            for header, seq in read_fasta(path):
                 name = header.split()[0] if header.split() else self._auto_name()
-                self._add(name, seq, where)
+                self._add(name, pre + seq.strip() + post, where)
             return
         name = None
         if "=" in spec:
@@ -93,6 +152,9 @@ class AdapterSet:
             name = name.strip()
         if "..." in spec:
             a, b = spec.split("...", 1)
+            if any(ch and ch in "^$xX" for ch in (a[:1], a[-1:], b[:1], b[-1:])):
+                raise SpecError(f"adapter {spec!r}: anchored / non-internal parts of a linked "
+                                "adapter are out of scope (single adapters take ^, $ and X)")
             if where != "front":
                 # -a A...B is also linked in cutadapt (front optional by default); not used by
                 # the reference scripts.
@@ -103,10 +165,10 @@ class AdapterSet:
         self._add(name or self._auto_name(), spec, where)
 
     def _add(self, name: str, seq: str, where: str):
-        s = seq.strip()
-        if s.startswith("^") or s.endswith("$") or s.endswith("X") or s.startswith("X"):
-            raise NotImplementedError("anchored / non-internal adapters are not on the hot path")
-        self.adapters.append(Adapter(name, normalize(s), where))
+        s, restrict = split_markers(seq, where)
+        s = normalize(s)
+        self.adapters.append(Adapter(name, s, where, restrict,
+                                     len(s) if restrict == "anchored" else None))
 
     @property
     def linked(self) -> bool:

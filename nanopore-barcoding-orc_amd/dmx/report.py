@@ -220,7 +220,7 @@ class Stats:
                     v = self.adjacent[a]
                     adj = {k: int(v[i]) for i, k in enumerate(ADJ_KEYS)}
                 ends[part] = {
-                    "type": "regular", "sequence": seq, "error_rate": error_rate, "indels": True,
+                    "type": "regular" if linked else ad.type_name, "sequence": seq, "error_rate": error_rate, "indels": True,
                     "error_lengths": error_lengths(seq, error_rate),
                     "matches": sum(sum(e.values()) for e in h.values()),
                     "adjacent_bases": adj,
@@ -296,12 +296,14 @@ class Stats:
             else:
                 parts = [(ad.where, ad.seq, "5'" if ad.where == "front" else "3'")]
                 rc = (f"; Reverse-complemented: {self.on_rc[a]} times" if self.rc_mode else "")
-                p(f"Sequence: {ad.seq}; Type: regular {parts[0][2]}; Length: {len(ad.seq)}; "
+                kind = {"": "regular", "anchored": "anchored",
+                        "noninternal": "non-internal"}[getattr(ad, "restrict", "")]
+                p(f"Sequence: {ad.seq}; Type: {kind} {parts[0][2]}; Length: {len(ad.seq)}; "
                   f"Trimmed: {self.matches[a]} times{rc}")
             for part, seq, kind in parts:
                 if linked:
                     p(f"\n{'First' if part == 'front' else 'Second'} adapter ({kind}):")
-                p(f"\nMinimum overlap: {self.min_overlap}")
+                p(f"\nMinimum overlap: {getattr(ad, 'min_overlap', None) or self.min_overlap}")
                 p("No. of allowed errors:")
                 p(allowed_errors_text(seq, error_rate))
                 if part == "back" and not linked:

@@ -1,0 +1,357 @@
+"""Case set of the end-window stage (anchored / non-internal adapters), shared by
+test_ends_host.py (CPU: dmx_ends_host against the oracle) and test_ends.py (GPU: the kernels
+against dmx_ends_host).
+
+A group is one panel and a list of reads; the expected records come from `demux`, a demux
+oracle written here from oracle.locate with cutadapt's EndSkip flags, best_match and --rc in
+plain Python.  Every read carries a label naming the stratum it was built for; `coverage`
+derives the strata from the expected records, so a case that stops exercising its stratum
+fails the test that asserts the coverage."""
+from __future__ import annotations
+
+import json
+import os
+import sys
+from dataclasses import dataclass, field
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "nanopore-barcoding-orc_amd"), os.path.join(ROOT, "oracle")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import oracle  # noqa: E402  (checker)
+from dmx import lib  # noqa: E402
+
+F, B = lib.DMX_FRONT, lib.DMX_BACK
+ANCH, NONI = lib.DMX_ANCHORED, lib.DMX_NONINTERNAL
+PREFIX, FRONTX, SUFFIX, BACKX = F | ANCH, F | NONI, B | ANCH, B | NONI
+# oracle flag numbering: REF_START 1, QUERY_START 2, REF_END 4, QUERY_STOP 8
+FLAGS = {F: 11, B: 14, PREFIX: 8, FRONTX: 9, SUFFIX: 2, BACKX: 6}
+RESTRICTED = (PREFIX, FRONTX, SUFFIX, BACKX)
+COMP = str.maketrans("ACGTN", "TGCAN")
+
+
+def revcomp(s: str) -> str:
+    return s.translate(COMP)[::-1]
+
+
+def rate_of(e: float, m: int) -> float:
+    return e / m if e >= 1.0 else e
+
+
+def min_overlap_of(where: int, m: int, overlap: int) -> int:
+    return m if where & ANCH else overlap
+
+
+def best_match(seqs, wheres, view: str, e: float, overlap: int):
+    """AdapterCutter.best_match: (adapter, locate tuple) or None."""
+    best = None
+    for a, (s, w) in enumerate(zip(seqs, wheres)):
+        r = oracle.locate(s, view, rate_of(e, len(s)), FLAGS[w], min_overlap_of(w, len(s), overlap))
+        if r is None:
+            continue
+        if best is None or r[4] > best[1][4] or (r[4] == best[1][4] and r[5] < best[1][5]):
+            best = (a, r)
+    return best
+
+
+def demux(seqs, wheres, reads, rc: bool, e: float, overlap: int) -> np.ndarray:
+    """One cutadapt call (single round) as dmx_result records."""
+    out = np.zeros(len(reads), dtype=lib.RESULT_DTYPE)
+    out["bin1"] = -1
+    out["bin2"] = -1
+    for i, read in enumerate(reads):
+        bf = best_match(seqs, wheres, read, e, overlap)
+        br = best_match(seqs, wheres, revcomp(read), e, overlap) if rc else None
+        fs = bf[1][4] if bf else 0
+        rs = br[1][4] if br else 0
+        use_rc = rc and rs > fs            # ReverseComplementer: strictly greater only
+        b = br if use_rc else bf
+        out["rc1"][i] = 1 if use_rc else 0
+        if b:
+            a, r = b
+            out["bin1"][i] = a
+            for k, v in zip(("astart", "astop", "rstart", "rstop", "score", "errors"), r):
+                out["m1_" + k][i] = v
+    return out
+
+
+def trimmed(read: str, rec, wheres) -> str:
+    """The sequence cutadapt writes for this record (the round-1 view of a two-round run)."""
+    s = revcomp(read) if rec["rc1"] else read
+    if rec["bin1"] < 0:
+        return s
+    return s[rec["m1_rstop"]:] if wheres[rec["bin1"]] & F else s[:rec["m1_rstart"]]
+
+
+@dataclass
+class Group:
+    name: str
+    seqs: list
+    wheres: list
+    e: float
+    overlap: int
+    rc: bool
+    reads: list = field(default_factory=list)
+    labels: list = field(default_factory=list)
+
+    def add(self, label: str, read: str):
+        self.reads.append(read)
+        self.labels.append(label)
+
+    def expected(self) -> np.ndarray:
+        if getattr(self, "_exp", None) is None:
+            self._exp = demux(self.seqs, self.wheres, self.reads, self.rc, self.e, self.overlap)
+        return self._exp
+
+    def packed(self):
+        blob, offs, lens = oracle.pack_ascii(self.reads)
+        return lib.pack(blob, offs, lens)
+
+
+def _rand(rng, n: int, alphabet: str = "ACGT") -> str:
+    return "".join(rng.choice(list(alphabet), n)) if n else ""
+
+
+def _sub(rng, s: str, k: int, lo: int = 0) -> str:
+    """k substitutions at distinct positions >= lo, each to another base."""
+    t = list(s)
+    for i in rng.choice(np.arange(lo, len(s)), k, replace=False):
+        t[i] = "ACGT"[("ACGT".index(t[i]) + 1 + int(rng.integers(3))) % 4]
+    return "".join(t)
+
+
+def _place(where: int, piece: str, body: str) -> str:
+    return piece + body if where & F else body + piece
+
+
+def build_groups(seed: int = 20261020) -> list:
+    rng = np.random.default_rng(seed)
+    groups = []
+    # every type x error setting x adapter length, forward and --rc
+    for e in (0.0, 0.1, 0.25, 2.0):
+        for m in (1, 3, 20, 63, 64):
+            for w in RESTRICTED:
+                ad = _rand(rng, m)
+                k = int(rate_of(e, m) * m)
+                g = Group(f"t{w}_e{e}_m{m}", [ad], [w], e, 3, True)
+                body = _rand(rng, 90)
+                g.add("exact", _place(w, ad, body))
+                g.add("rc", revcomp(_place(w, ad, body)))
+                if k and m > k:
+                    g.add("errors_k", _place(w, _sub(rng, ad, k), body))
+                if m > k + 1:
+                    g.add("errors_k1", _place(w, _sub(rng, ad, k + 1), body))
+                if m >= 20:   # an indel at the end the adapter touches
+                    piece = ad[1:] if w & F else ad[:-1]
+                    g.add("indel_end", _place(w, piece, body))
+                    piece = "G" + ad if w & F else ad + "G"
+                    g.add("indel_end", _place(w, piece, body))
+                    mid = m // 2
+                    g.add("indel_mid", _place(w, ad[:mid] + ad[mid + 1:], body))
+                for n in sorted({0, 1, m - k - 1, m - k, m, m + k, m + k + 1}):
+                    if n < 0:
+                        continue
+                    full = _place(w, ad, body)
+                    g.add(f"len_{n - m}" if n > 1 else f"len{n}",
+                          full[:n] if w & F else full[len(full) - n:])
+                if w & NONI and m >= 20:   # cut to exactly min_overlap and one below
+                    for keep in (3, 2):
+                        piece = ad[m - keep:] if w & F else ad[:keep]
+                        g.add(f"cut_{keep}", _place(w, piece, "") + "")
+                        g.add(f"cutbody_{keep}", _place(w, piece, _rand(rng, 40)))
+                if w & ANCH and m >= 20:   # -O 3 does not shorten an anchored adapter
+                    piece = ad[m - 8:] if w & F else ad[:8]
+                    g.add("anch_partial", _place(w, piece, body))
+                if m >= 20:
+                    i = m // 3
+                    g.add("read_n", _place(w, ad[:i] + "N" + ad[i + 1:], body))
+                    g.add("unrelated", _rand(rng, 70))
+                groups.append(g)
+    # N (and other IUPAC codes) in the adapter
+    for w in RESTRICTED:
+        ad = "ACGTNNACGRYTTGACCA"
+        g = Group(f"iupac_{w}", [ad], [w], 0.12, 3, True)
+        body = _rand(rng, 50)
+        for fill in ("AC", "GT"):
+            real = ad.replace("N", fill[0]).replace("R", "A").replace("Y", fill[1])
+            g.add("adapter_n", _place(w, real, body))
+            g.add("adapter_n", _place(w, _sub(rng, real, 1, 8), body))
+            g.add("adapter_n_rc", revcomp(_place(w, real, body)))
+        groups.append(g)
+    # a reverse-complement tie is kept forward: the read is its own reverse complement
+    for w in RESTRICTED:
+        ad = _rand(rng, 16)
+        g = Group(f"rctie_{w}", [ad], [w], 0.1, 3, True)
+        half = _place(w, ad, "ACGTTGCA") if w & F else "ACGTTGCA" + ad
+        g.add("rc_tie", half + revcomp(half) if w & F else revcomp(half) + half)
+        groups.append(g)
+    # mixed panels: a regular 5' adapter against an anchored one, both ways; all six types
+    ra, aa = _rand(rng, 24), _rand(rng, 24)
+    g = Group("mixed_reg_anch", [aa, ra], [PREFIX, F], 0.1, 3, True)
+    body = _rand(rng, 80)
+    g.add("regular_beats_anchored", _sub(rng, aa, 2) + _rand(rng, 20) + ra + body)
+    g.add("anchored_beats_regular", aa + _rand(rng, 20) + _sub(rng, ra, 2) + body)
+    g.add("regular_only", _rand(rng, 30) + ra + body)
+    groups.append(g)
+    six = [_rand(rng, 22) for _ in range(6)]
+    g = Group("mixed_six", six, [B, PREFIX, F, BACKX, FRONTX, SUFFIX], 0.1, 4, True)
+    for a, w in enumerate(g.wheres):
+        read = _place(w, six[a], _rand(rng, 70)) if w & (ANCH | NONI) else \
+            _rand(rng, 30) + six[a] + _rand(rng, 30)
+        g.add(f"six_{a}", read)
+        g.add(f"six_rc_{a}", revcomp(read))
+    g.add("six_two", six[1] + _rand(rng, 40) + six[5])
+    groups.append(g)
+    # two restricted adapters tie on score and errors: the lower index wins
+    ad = _rand(rng, 18)
+    for ws in ((PREFIX, FRONTX), (FRONTX, PREFIX), (SUFFIX, BACKX), (BACKX, SUFFIX)):
+        g = Group(f"tie_{ws[0]}_{ws[1]}", [ad, ad], list(ws), 0.1, 3, False)
+        g.add("restricted_tie", _place(ws[0], ad, _rand(rng, 40)))
+        groups.append(g)
+    # random panels and reads
+    for it in range(24):
+        n_ad = int(rng.integers(1, 6))
+        e = float(rng.choice([0.0, 0.1, 0.2, 0.25, 1.0, 2.0]))
+        ov = int(rng.integers(1, 7))
+        seqs = [_rand(rng, int(rng.integers(3, 40))) for _ in range(n_ad)]
+        wheres = [int(rng.choice([F, B, PREFIX, FRONTX, SUFFIX, BACKX])) for _ in range(n_ad)]
+        if not any(w in RESTRICTED for w in wheres):
+            wheres[0] = int(rng.choice(RESTRICTED))
+        g = Group(f"rand{it}", seqs, wheres, e, ov, bool(it % 2))
+        for _ in range(24):
+            a = int(rng.integers(n_ad))
+            s, w = seqs[a], wheres[a]
+            piece = s
+            if w & NONI and rng.random() < 0.5:
+                c = int(rng.integers(0, len(s)))
+                piece = s[c:] if w & F else s[:len(s) - c]
+            if len(piece) > 2 and rng.random() < 0.6:
+                piece = _sub(rng, piece, int(rng.integers(0, min(4, len(piece)))))
+            if len(piece) > 2 and rng.random() < 0.3:
+                i = int(rng.integers(len(piece)))
+                piece = piece[:i] + piece[i + 1:] if rng.random() < 0.5 else \
+                    piece[:i] + "T" + piece[i:]
+            body = _rand(rng, int(rng.integers(0, 80)), "ACGT" * 8 + "N")
+            read = _place(w, piece, body) if w in RESTRICTED else \
+                _rand(rng, int(rng.integers(0, 20))) + piece + body
+            g.add("random", revcomp(read) if g.rc and rng.random() < 0.4 else read)
+        groups.append(g)
+    return groups
+
+
+_GROUPS = None
+
+
+def groups() -> list:
+    global _GROUPS
+    if _GROUPS is None:
+        _GROUPS = build_groups()
+        for g in _GROUPS:
+            g.expected()
+    return _GROUPS
+
+
+def coverage(gs) -> set:
+    """The strata the case set exercises, judged from the expected records."""
+    cov = set()
+    for g in gs:
+        exp = g.expected()
+        for i, (lab, read) in enumerate(zip(g.labels, g.reads)):
+            r = exp[i]
+            hit = r["bin1"] >= 0
+            w = g.wheres[r["bin1"]] if hit else g.wheres[0]
+            m = len(g.seqs[r["bin1"]]) if hit else len(g.seqs[0])
+            k = int(rate_of(g.e, m) * m)
+            if hit and w in RESTRICTED:
+                cov.add(("winner", w, "rc" if r["rc1"] else "fwd"))
+                cov.add(("e", g.e))
+                cov.add(("m", m))
+                if k and r["m1_errors"] == k:
+                    cov.add("errors_eq_k")
+                if lab == "indel_end" and r["m1_errors"] >= 1:
+                    cov.add(("indel_end", w))
+                if lab.startswith("cut") and lab.endswith("_3") and \
+                        r["m1_astop"] - r["m1_astart"] == 3:
+                    cov.add(("cut_min_overlap", w))
+                if lab == "read_n" and r["m1_errors"] >= 1:
+                    cov.add("read_n")
+                if lab.startswith("adapter_n"):
+                    cov.add("adapter_n")
+                if lab == "rc_tie" and not r["rc1"]:
+                    cov.add(("rc_tie_forward", w))
+                if lab == "anchored_beats_regular":
+                    cov.add("anchored_beats_regular")
+                if lab == "restricted_tie" and r["bin1"] == 0:
+                    cov.add(("restricted_tie", g.wheres[0]))
+            if hit and lab == "regular_beats_anchored" and w == F:
+                cov.add("regular_beats_anchored")
+            if not hit and lab == "errors_k1":
+                cov.add(("errors_k1_refused", g.wheres[0]))
+            if not hit and lab == "cut_2":
+                cov.add(("cut_below_min_overlap", g.wheres[0]))
+            if not hit and lab == "anch_partial":
+                cov.add(("anchored_needs_full_length", g.wheres[0]))
+            if lab.startswith("len"):
+                cov.add(("len", lab))
+    return cov
+
+
+def required_coverage() -> set:
+    req = {"errors_eq_k", "read_n", "adapter_n", "anchored_beats_regular",
+           "regular_beats_anchored"}
+    for w in RESTRICTED:
+        req |= {("winner", w, "fwd"), ("winner", w, "rc"), ("indel_end", w),
+                ("errors_k1_refused", w), ("rc_tie_forward", w), ("restricted_tie", w)}
+    for w in (FRONTX, BACKX):
+        req |= {("cut_min_overlap", w), ("cut_below_min_overlap", w)}
+    for w in (PREFIX, SUFFIX):
+        req.add(("anchored_needs_full_length", w))
+    req |= {("e", e) for e in (0.0, 0.1, 0.25, 2.0)}
+    req |= {("m", m) for m in (1, 3, 63, 64)}
+    # read lengths 0, 1, m - K - 1, m - K, m, m + K, m + K + 1 (K = 2 at m = 20, -e 0.1)
+    req |= {("len", lab) for lab in ("len0", "len1", "len_-3", "len_-2", "len_0", "len_2", "len_3")}
+    return req
+
+
+def same_records(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Indices of the records that differ in any of their 40 bytes."""
+    return np.nonzero((a.view(np.uint8).reshape(len(a), -1) !=
+                       b.view(np.uint8).reshape(len(b), -1)).any(axis=1))[0]
+
+
+def run_group(ctx, g: Group) -> np.ndarray:
+    ctx.set_panel_ex(0, g.seqs, g.wheres, g.rc, g.e, g.overlap)
+    ctx.set_mode(lib.MODE_SINGLE)
+    return ctx.run(g.packed())
+
+
+def gpu_against_host(ctx, gs) -> tuple:
+    """(records that differ from dmx_ends_host, records, flags of dmx_stats or-ed together)."""
+    bad = n = flags = 0
+    for g in gs:
+        got = run_group(ctx, g)
+        host = lib.ends_host(g.seqs, g.wheres, g.packed(), g.rc, g.e, g.overlap)
+        bad += len(same_records(got, host))
+        n += len(got)
+        flags |= ctx.stats()["flags"]
+    return bad, n, flags
+
+
+def main():
+    """The case set on the library DMX_DEBUG_BOUNDS selects (test_ends.py runs this in a child
+    process with the bounds-checked build): one JSON line."""
+    out = {"lib": os.path.basename(lib.LIB_PATH)}
+    with lib.Context(0) as ctx:
+        try:
+            out["bad"], out["n"], out["flags"] = gpu_against_host(ctx, groups())
+            out["err"] = ""
+        except lib.DmxError as e:
+            out["bad"], out["n"], out["flags"], out["err"] = -1, 0, 0, str(e)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
