@@ -152,13 +152,6 @@ int ensure_pipeline(Ctx* c) {
         c->task_cap = 4 * want_win;
         c->ftask_cap = want_win;
     }
-    // window code slots: verified windows are about one per view and round; later ones gather
-    const size_t want_stage = std::min<size_t>(c->win_cap, 2 * std::max(slots0, n) + 65536);
-    if (c->use_stage && c->stage_cap < want_stage) {
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_stage, want_stage * kStageWords))) return rc;
-        c->stage_cap = want_stage;
-    }
     const size_t nc = counts_size(c);
     if (c->n_counts != nc) {
         int rc;
@@ -299,6 +292,20 @@ int reset_counts(Ctx* c) {
     return DMX_OK;
 }
 
+bool env_on(const char* name) {
+    const char* e = std::getenv(name);
+    return e && e[0] == '1';
+}
+
+PanelSwitches panel_switches_env() {
+    PanelSwitches s;
+    s.no_filter = env_on("DMX_NO_FILTER");
+    s.no_verify = env_on("DMX_NO_VERIFY");
+    s.no_pieces = env_on("DMX_NO_PIECES");
+    s.near_all = env_on("DMX_NEAR_ALL");   // (DevPanel::near_shared = -1)
+    return s;
+}
+
 }  // namespace dmx
 
 
@@ -314,22 +321,11 @@ int dmx_open(int device, dmx_ctx** out) {
         return DMX_E_HIP;
     dmx_ctx* c = new dmx_ctx();
     c->device = device;
-    const char* nf = std::getenv("DMX_NO_FILTER");
-    c->no_filter = nf && nf[0] == '1';
-    const char* nv = std::getenv("DMX_NO_VERIFY");
-    c->no_verify = nv && nv[0] == '1';
-    const char* np = std::getenv("DMX_NO_PIECES");   // A/B: the full filter pass
-    c->no_pieces = np && np[0] == '1';
+    c->sw = panel_switches_env();
     const char* rs = std::getenv("DMX_RESOLVE");
     c->force_ring = rs && std::strcmp(rs, "ring") == 0;
-    const char* stg = std::getenv("DMX_STAGE");   // A/B: window code slots
-    c->use_stage = DMX_STAGE_SLOTS && stg && stg[0] == '1';
-    const char* ns = std::getenv("DMX_NO_SCREEN");   // A/B: no index screen before the
-    c->no_screen = ns && ns[0] == '1';               // window scan
-    const char* s1 = std::getenv("DMX_SCREEN_V1");   // A/B: the unpacked index screen
-    c->screen_v1 = s1 && s1[0] == '1';
-    const char* na = std::getenv("DMX_NEAR_ALL");    // A/B: near pieces scan every column for
-    c->near_all = na && na[0] == '1';                // every adapter (DevPanel::near_shared = -1)
+    c->no_screen = env_on("DMX_NO_SCREEN");   // A/B: no index screen before the window scan
+    c->screen_v1 = env_on("DMX_SCREEN_V1");   // A/B: the unpacked index screen
     if (hipSetDevice(device) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
@@ -358,7 +354,7 @@ void dmx_close(dmx_ctx* c) {
                     c->d_winner[0], c->d_winner[1], c->d_origin[0], c->d_origin[1], c->d_lb[0], c->d_lb[1], c->d_cl[0],
                     c->d_cl[1],     c->d_outc[0],   c->d_outc[1],  c->d_items, c->d_win, c->d_win2, c->d_linked, c->d_tasks, c->d_counters, c->d_shard,
                     c->d_counts,    c->d_panel[0],  c->d_panel[1], c->d_pieces[0], c->d_pieces[1],
-                    c->d_ftask, c->d_stage, c->d_pieces_flat, c->d_cells[0], c->d_cells[1], c->d_cells[2],
+                    c->d_ftask, c->d_pieces_flat, c->d_cells[0], c->d_cells[1], c->d_cells[2],
                     c->d_cells[3], c->d_ends[0], c->d_ends[1], c->d_panel_all[0],
                     c->d_panel_all[1]};
     for (void* b : bufs)
@@ -482,12 +478,12 @@ int dmx_set_panel_mixed(dmx_ctx* c, int round, const char* const* seqs, const in
 // 8-mers at offsets 0 .. s-1 (s = the sampling stride), so a copy starting anywhere has one of
 // them at a sampled position.  Off (piece_step 0) for IUPAC panels, pieces shorter than 8 nt,
 // tables that do not fit, or DMX_NO_PIECES=1.
-static void build_pieces(const Ctx* c, const char* const* seqs, const int* lens, int n,
+static void build_pieces(const PanelSwitches& sw, const char* const* seqs, const int* lens, int n,
                          HostPanel& hp) {
     hp.piece_step = 0;
     DevPieces& Q = hp.pieces;
     memset(&Q, 0, sizeof(Q));
-    if (!hp.filter || c->no_pieces) return;
+    if (!hp.filter || sw.no_pieces) return;
     struct Pc {
         uint32_t val;
         int len, o, dlo, dhi;
@@ -611,22 +607,22 @@ static void build_pieces(const Ctx* c, const char* const* seqs, const int* lens,
 }
 
 // The host and device forms of a panel (parser.py / adapters.py rules above), the filter /
-// verification / screen blocks and the reach check; uses only c->err, c->no_filter, c->no_verify,
-// c->no_pieces, c->near_all (dmx_panel_reach runs it on a context that was never opened).
-static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const int* wheres, int n,
-                       double max_errors, int min_overlap, int flags, HostPanel& hp,
-                       DevPanel& dp) {
+// verification / screen blocks and the reach check.  It needs no context: the switches and where
+// to leave the text of an error are all it takes (the dmx_panel_* information calls run it).
+static int build_panel(const PanelSwitches& sw, std::string& err, const char* const* seqs,
+                       const int* lens, const int* wheres, int n, double max_errors,
+                       int min_overlap, int flags, HostPanel& hp, DevPanel& dp) {
     if (!seqs || !lens) return DMX_E_INVALID;
     if (n <= 0 || n > kMaxAdapters) {
-        c->err = "panel must hold 1..64 adapters";
+        err = "panel must hold 1..64 adapters";
         return DMX_E_INVALID;
     }
     if (!(flags & (DMX_FRONT | DMX_BACK)) || ((flags & DMX_FRONT) && (flags & DMX_BACK))) {
-        c->err = "panel flags need exactly one of DMX_FRONT / DMX_BACK";
+        err = "panel flags need exactly one of DMX_FRONT / DMX_BACK";
         return DMX_E_INVALID;
     }
     if (!(max_errors >= 0.0)) {
-        c->err = "max_errors must be >= 0";
+        err = "max_errors must be >= 0";
         return DMX_E_INVALID;
     }
     hp = HostPanel();
@@ -635,7 +631,7 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
     for (int a = 0; a < n; ++a) {
         const int m = lens[a];
         if (m <= 0 || m > kMaxLen) {
-            c->err = "adapter length must be 1..64 (one 64-bit Myers word)";
+            err = "adapter length must be 1..64 (one 64-bit Myers word)";
             return DMX_E_UNSUPPORTED;
         }
         DevAdapter& ad = hp.ad[a];
@@ -644,7 +640,7 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
         for (int i = 0; i < m; ++i) {
             const char ch = seqs[a][i];
             if (!iupac_mask(ch)) {
-                c->err = std::string("adapter character not IUPAC uppercase: ") + ch;
+                err = std::string("adapter character not IUPAC uppercase: ") + ch;
                 return DMX_E_INVALID;
             }
             if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') wild = true;
@@ -653,7 +649,7 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
         const int k = (int)(rate * m);
         if (m + k + 2 + 4 > kRingSmall) hp.ring_small = false;
         if (m + k + 2 + 4 > kRingLarge) {
-            c->err = "error rate too high for the resolve window (m + k + 6 > 128)";
+            err = "error rate too high for the resolve window (m + k + 6 > 128)";
             return DMX_E_UNSUPPORTED;
         }
         int ncount[kMaxLen + 1];
@@ -665,7 +661,7 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
         ncount[m] = nc;
         const int eff_len = wild ? m - nc : m;
         if (eff_len == 0) {
-            c->err = "adapter consists only of N wildcards";
+            err = "adapter consists only of N wildcards";
             return DMX_E_INVALID;
         }
         for (int i = 0; i < m; ++i) {
@@ -731,7 +727,7 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
     bool near_ok = true;
     for (int j = 65; j + kf_all < 71; ++j) near_ok &= pf_all[j + kf_all] >= kf_far;
     hp.filter = uniform && flen >= kMinFilterLen && flen + kf_all <= 64 && near_ok &&
-                !(c->no_filter);
+                !sw.no_filter;
     if (hp.filter) {
         dp.filter_len = flen;
         int slen = flen;
@@ -775,7 +771,7 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
         // slot (make_key_o): adapters > 0 skip the columns j <= near_shared of a near piece.
         {
             const int js = flen - kf;
-            bool same = dp.where == kFront && js >= 1 && !c->near_all;
+            bool same = dp.where == kFront && js >= 1 && !sw.near_all;
             for (int a = 0; a < n && same; ++a) {
                 same &= lens[a] > flen;
                 for (int L = 0; L <= flen; ++L)
@@ -796,7 +792,7 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
             mmax = std::max(mmax, lens[a]);
         }
         pre = std::min(pre, 32);
-        if (pre >= kMinFilterLen && pre + flen <= mmin && !c->no_verify) {
+        if (pre >= kMinFilterLen && pre + flen <= mmin && !sw.no_verify) {
             hp.verify = true;
             dp.pre_len = pre;
             dp.off_min = mmin - pre;
@@ -827,25 +823,15 @@ static int build_panel(Ctx* c, const char* const* seqs, const int* lens, const i
     // loaders accept (>= kMinOffset nt, >= kMinTail nt before the end): the deepest warm-up
     // before a view (index screen, edge bands), clamped at -kViewReachPre, and the block loads
     // past it.  Adapters of <= 64 nt always fit; the check keeps it explicit.
-    build_pieces(c, seqs, lens, n, hp);
+    build_pieces(sw, seqs, lens, n, hp);
     hp.reach = panel_reach(hp, dp);
     if (hp.reach.need_pre > kGuardNt || hp.reach.need_post > kGuardNt) {
-        c->err = "panel: the kernels' reach around a view (" + std::to_string(hp.reach.pre) +
+        err = "panel: the kernels' reach around a view (" + std::to_string(hp.reach.pre) +
                  " nt before, " + std::to_string(hp.reach.post) +
                  " after) exceeds the device guard";
         return DMX_E_UNSUPPORTED;
     }
     for (int a = 0; a < n; ++a) dp.ad[a] = hp.ad[a];
-    // window code slots: from m + k + 1 columns before a window's first hit
-    // column (the window scan's restricted start), never below the band's own warm-up
-    hp.pre_len = dp.pre_len;
-    int mk = 0, m_max = 0;
-    for (int a = 0; a < n; ++a) {
-        mk = std::max(mk, (int)hp.ad[a].m + (int)hp.ad[a].k + 1);
-        m_max = std::max(m_max, (int)hp.ad[a].m);
-    }
-    hp.stage_back = mk;
-    hp.stage_lo = -std::min(kViewReachPre, m_max + 7);
     return DMX_OK;
 }
 
@@ -855,7 +841,8 @@ static int set_panel_impl(dmx_ctx* c, int round, const char* const* seqs, const 
     if (!c || round < 0 || round > 1 || !seqs || !lens) return DMX_E_INVALID;
     HostPanel hp;
     DevPanel dp;
-    const int brc = build_panel(c, seqs, lens, wheres, n, max_errors, min_overlap, flags, hp, dp);
+    const int brc = build_panel(c->sw, c->err, seqs, lens, wheres, n, max_errors, min_overlap,
+                                flags, hp, dp);
     if (brc) return brc;
     c->panel[round] = hp;
     c->panel[round].n_all = n;
@@ -914,8 +901,9 @@ static int set_panel_ends(dmx_ctx* c, int round, const char* const* seqs, const 
     memset(all.get(), 0, sizeof(DevPanel));
     memset(de.get(), 0, sizeof(DevEnds));
     if (!sseq.empty()) {
-        const int brc = build_panel(c, sseq.data(), slen.data(), swhere.data(), (int)sseq.size(),
-                                    max_errors, sub_mo, DMX_FRONT | rcflag, hp, *dp);
+        const int brc = build_panel(c->sw, c->err, sseq.data(), slen.data(), swhere.data(),
+                                    (int)sseq.size(), max_errors, sub_mo, DMX_FRONT | rcflag, hp,
+                                    *dp);
         if (brc) return brc;
     } else {   // restricted adapters only: no screen, no scan
         hp = HostPanel();
@@ -943,16 +931,17 @@ static int set_panel_ends(dmx_ctx* c, int round, const char* const* seqs, const 
             c->err = "adapter " + std::to_string(a) + ": minimum overlap must be >= 1";
             return DMX_E_INVALID;
         }
-        Ctx tmp;   // never opened: one adapter's tables, no filter blocks
-        tmp.no_filter = tmp.no_verify = tmp.no_pieces = true;
+        PanelSwitches one;   // one adapter's tables, no filter blocks
+        one.no_filter = one.no_verify = one.no_pieces = true;
+        std::string err1;
         HostPanel h1;
         std::unique_ptr<DevPanel> d1(new DevPanel());
         const char* s1[1] = {seqs[a]};
         const int l1[1] = {lens[a]};
-        const int brc = build_panel(&tmp, s1, l1, nullptr, 1, max_errors, mo,
+        const int brc = build_panel(one, err1, s1, l1, nullptr, 1, max_errors, mo,
                                     front ? DMX_FRONT : DMX_BACK, h1, *d1);
         if (brc) {
-            c->err = "adapter " + std::to_string(a) + ": " + tmp.err;
+            c->err = "adapter " + std::to_string(a) + ": " + err1;
             return brc;
         }
         const DevAdapter& src = h1.ad[0];
@@ -1131,13 +1120,12 @@ int dmx_panel_pieces(const char* const* seqs, const int* lens, int n, double max
                      int min_overlap, int flags, int32_t* out, int n_out, uint64_t* entries,
                      int cap) {
     if (!out || n_out < 8) return DMX_E_INVALID;
-    Ctx tmp;   // never opened: build_panel reads only the A/B switches dmx_open would set
-    const char* np = std::getenv("DMX_NO_PIECES");
-    tmp.no_pieces = np && np[0] == '1';
+    const PanelSwitches sw = panel_switches_env();   // the switches dmx_open would set
+    std::string err;                                 // (no context to keep it in)
     HostPanel hp;
     DevPanel dp;
-    const int rc = build_panel(&tmp, seqs, lens, nullptr, n, max_errors, min_overlap, flags, hp,
-                               dp);
+    const int rc = build_panel(sw, err, seqs, lens, nullptr, n, max_errors, min_overlap, flags,
+                               hp, dp);
     for (int i = 0; i < n_out; ++i) out[i] = 0;
     if (rc != DMX_OK) return rc;
     const DevPieces& Q = hp.pieces;
@@ -1153,13 +1141,12 @@ int dmx_panel_piece_pairs(const char* const* seqs, const int* lens, int n, doubl
                           int min_overlap, int flags, uint32_t* pair, uint16_t* rank_base,
                           uint32_t* keys, int cap) {
     if (!pair || !rank_base) return DMX_E_INVALID;
-    Ctx tmp;   // never opened, as in dmx_panel_pieces
-    const char* np = std::getenv("DMX_NO_PIECES");
-    tmp.no_pieces = np && np[0] == '1';
+    const PanelSwitches sw = panel_switches_env();   // the switches dmx_open would set
+    std::string err;                                 // (no context to keep it in)
     HostPanel hp;
     DevPanel dp;
-    const int rc = build_panel(&tmp, seqs, lens, nullptr, n, max_errors, min_overlap, flags, hp,
-                               dp);
+    const int rc = build_panel(sw, err, seqs, lens, nullptr, n, max_errors, min_overlap, flags,
+                               hp, dp);
     if (rc != DMX_OK) return rc;
     const DevPieces& Q = hp.pieces;
     for (int r = 0; r < kPiecePairWords; ++r) pair[r] = Q.pair[r];
@@ -1196,11 +1183,8 @@ int dmx_panel_reach(const char* const* seqs, const int* lens, const int* wheres,
         }
         flags = DMX_FRONT | (flags & DMX_RC);
     }
-    Ctx tmp;   // never opened: build_panel reads only the A/B switches dmx_open would set
-    const char* nf = std::getenv("DMX_NO_FILTER");
-    tmp.no_filter = nf && nf[0] == '1';
-    const char* nv = std::getenv("DMX_NO_VERIFY");
-    tmp.no_verify = nv && nv[0] == '1';
+    const PanelSwitches sw = panel_switches_env();   // the switches dmx_open would set
+    std::string err;                                 // (no context to keep it in)
     HostPanel hp;
     DevPanel dp;
     PanelReach r;
@@ -1211,7 +1195,8 @@ int dmx_panel_reach(const char* const* seqs, const int* lens, const int* wheres,
         for (int i = 0; i < 6; ++i) out[i] = v0[i];
         return DMX_OK;
     }
-    const int rc = build_panel(&tmp, seqs, lens, wheres, n, max_errors, min_overlap, flags, hp, dp);
+    const int rc = build_panel(sw, err, seqs, lens, wheres, n, max_errors, min_overlap, flags, hp,
+                               dp);
     if (rc == DMX_OK) r = hp.reach;
     else if (rc == DMX_E_UNSUPPORTED && hp.set) r = hp.reach;   // refused by the reach check
     else return rc;
@@ -1228,16 +1213,12 @@ int dmx_panel_near_shared(const char* const* seqs, const int* lens, const int* w
             if (wheres[a] != DMX_FRONT && wheres[a] != DMX_BACK) return DMX_E_INVALID;
         flags = DMX_FRONT | (flags & DMX_RC);
     }
-    Ctx tmp;   // never opened, as in dmx_panel_reach
-    const char* nf = std::getenv("DMX_NO_FILTER");
-    tmp.no_filter = nf && nf[0] == '1';
-    const char* nv = std::getenv("DMX_NO_VERIFY");
-    tmp.no_verify = nv && nv[0] == '1';
-    const char* na = std::getenv("DMX_NEAR_ALL");
-    tmp.near_all = na && na[0] == '1';
+    const PanelSwitches sw = panel_switches_env();   // the switches dmx_open would set
+    std::string err;                                 // (no context to keep it in)
     HostPanel hp;
     DevPanel dp;
-    const int rc = build_panel(&tmp, seqs, lens, wheres, n, max_errors, min_overlap, flags, hp, dp);
+    const int rc = build_panel(sw, err, seqs, lens, wheres, n, max_errors, min_overlap, flags, hp,
+                               dp);
     if (rc != DMX_OK) return rc;
     int kk = -1;
     for (int a = 0; a < n; ++a) kk = std::max(kk, (int)hp.ad[a].kk);
@@ -1451,14 +1432,6 @@ int dmx_debug_fetch(dmx_ctx* c, int what, int round, void* out, size_t cap_bytes
         const size_t take = out ? std::min(nb, cap_bytes > done ? cap_bytes - done : 0) : 0;
         if (take) CK(hipMemcpy((char*)out + done, base + s * scap * rec, take, hipMemcpyDeviceToHost));
         done += nb;
-    }
-    if (out) {   // records name their window code slot in off's top bits: clear them
-        for (size_t r = 0; (r + 1) * rec <= std::min(done, cap_bytes); ++r) {
-            uint64_t off;
-            std::memcpy(&off, (char*)out + r * rec + 32, 8);
-            off &= kOffMask;
-            std::memcpy((char*)out + r * rec + 32, &off, 8);
-        }
     }
     return (int)std::min<size_t>(done, (size_t)1 << 30);
 }

@@ -457,23 +457,10 @@ struct Packed {
     const uint32_t* seq;
     const uint32_t* nmask;
     Bounds bd;
-    const uint32_t* stage = nullptr;   // window code slots (kStageWords each, wstage_kernel)
 };
-
-// Window code slots: the codes and no-match bits of 128 view columns of one
-// verified window, gathered once by wstage_kernel for the index screen, the window scan and the
-// band.  Words 0..7: codes of columns base + 16 i .. (2 bits each, view orientation), 8..11:
-// no-match bits of columns base + 32 i .., 12: base, 13: columns filled (16 per gathered chunk).
-// A window, task or candidate names its slot in the top bits of its `off` (slot + 1, 0 = none).
-constexpr int kStageWords = 16;
-// Window code slots are an A/B build (make variant NAME=stage
-// DEFS=-DDMX_STAGE_SLOTS=1, then DMX_STAGE=1 at run time): measured slower, and compiled in they
-// cost every gathering stage registers for the slot test (window scan 43 instead of 31 spilled
-// VGPRs at 4 waves, index screen 7 instead of 2, band list 0 18 instead of 2).
-#ifndef DMX_STAGE_SLOTS
-#define DMX_STAGE_SLOTS 0
-#endif
-constexpr int kOffBits = 36;                              // batch nt offsets < 2^36
+// A record's `off` keeps its 36 offset bits (batch nt offsets are < 2^36); see view_off in
+// dmx_kernels.hip for why the mask stays.
+constexpr int kOffBits = 36;
 constexpr uint64_t kOffMask = (1ull << kOffBits) - 1ull;
 
 __device__ __forceinline__ uint32_t window32(const uint32_t* __restrict__ w, int64_t bitpos,
@@ -485,12 +472,8 @@ __device__ __forceinline__ uint32_t window32(const uint32_t* __restrict__ w, int
 #else
     (void)bd, (void)buf;
 #endif
-#ifdef DMX_WINDOW32_SPLIT   // A/B build: two 4-byte loads
-    const uint64_t v = ((uint64_t)w[q + 1] << 32) | (uint64_t)w[q];
-#else
     uint64_t v;   // words q and q + 1 as ONE 8-byte load (global_load_dwordx2 at a 4-byte
     __builtin_memcpy(&v, w + q, 8);   // aligned address: one request instead of two)
-#endif
     return (uint32_t)(v >> sh);
 }
 // 16 codes (32 bits) and 32 no-match bits from global nt position g

@@ -252,11 +252,6 @@ __global__ __launch_bounds__(kLgBlock) void lg_scatter_kernel(LgCompact A) {
 
 constexpr uint32_t kLgHistClasses = 1024;   // the most classes: the block's LDS counters
 constexpr uint32_t kLgHistBlocks = 1024;    // the most blocks of a launch (grid-stride beyond)
-// DMX_HIST_WAVE_AGG=1 (make variant): the lanes of a wave that hold the same class add once.
-// Measured on the bins of profiles/speciesgroups_bench.json; the record says which is built.
-#ifndef DMX_HIST_WAVE_AGG
-#define DMX_HIST_WAVE_AGG 0
-#endif
 enum LgHistBad : uint32_t { kLgBadRead = 1, kLgBadBin = 2, kLgBadClass = 4 };
 
 struct LgHist {
@@ -282,7 +277,6 @@ __global__ __launch_bounds__(kLgBlock) void lg_hist_kernel(LgHist A) {
     __syncthreads();
     uint32_t bad = 0u;
     const uint32_t stride = gridDim.x * kLgBlock;
-    // every lane of a wave runs the same number of rounds: the ballots below see whole waves
     for (uint32_t base = blockIdx.x * kLgBlock; base < A.n_pairs; base += stride) {
         const uint32_t i = base + threadIdx.x;
         uint32_t cls = DMX_LG_NONE;
@@ -304,18 +298,8 @@ __global__ __launch_bounds__(kLgBlock) void lg_hist_kernel(LgHist A) {
                 }
             }
         }
-#if DMX_HIST_WAVE_AGG
-        uint64_t todo = __ballot(cls != DMX_LG_NONE);
-        while (todo) {
-            const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
-            const uint32_t x = (uint32_t)__shfl((int)cls, (int)lead);
-            const uint64_t same = __ballot(cls == x);
-            if ((threadIdx.x & 63u) == lead) atomicAdd(&h[x], (uint32_t)__popcll(same));
-            todo &= ~same;
-        }
-#else
+        // (one LDS add per hit; per-wave aggregation of equal classes was slower)
         if (cls != DMX_LG_NONE) atomicAdd(&h[cls], 1u);
-#endif
     }
     if (bad) atomicOr(A.bad, bad);
     __syncthreads();

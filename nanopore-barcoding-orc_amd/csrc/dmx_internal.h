@@ -54,6 +54,15 @@ struct PanelReach {
     int need_post = 0;   // guard nt needed past n_words for reads keeping kMinTail nt of tail
 };
 
+struct PanelSwitches {        // the run-time switches a panel's tables depend on (build_panel)
+    bool no_filter = false;   // DMX_NO_FILTER=1: always full scans (A/B testing)
+    bool no_verify = false;   // DMX_NO_VERIFY=1: skip the shared-prefix window verification
+    bool no_pieces = false;   // DMX_NO_PIECES=1: the full filter pass instead of the piece screen
+    bool near_all = false;    // DMX_NEAR_ALL=1: near pieces keep every adapter's columns
+};
+bool env_on(const char* name);        // an on/off run-time switch: NAME=1 in the environment
+PanelSwitches panel_switches_env();   // the four above, as the environment has them now
+
 struct HostPanel {
     bool screen = false;      // index screen usable (filter + verify, index blocks 1..32)
     int n = 0;                // adapters of the internal pipeline (the unrestricted ones)
@@ -66,10 +75,6 @@ struct HostPanel {
     bool nonpos = false;      // an accepted match may score <= 0 (needs per-orientation winners)
     PanelReach reach;
     DevAdapter ad[kMaxAdapters];
-    int pre_len = 0;          // DevPanel::pre_len (0: no verification, the window scan reads
-                              // the filter's windows)
-    int stage_back = 0;       // window code slots start this many columns before j1 (m + k + 1),
-    int stage_lo = 0;         // and not before this view position
     int piece_step = 0;       // piece screen sampling stride (0 = off: the full filter pass)
     DevPieces pieces;         // its tables
 };
@@ -79,9 +84,7 @@ struct Ctx {
     hipStream_t stream = nullptr;
     std::string err;
     int mode = DMX_MODE_SINGLE;
-    bool no_filter = false;   // DMX_NO_FILTER=1: always full scans (A/B testing)
-    bool no_verify = false;   // DMX_NO_VERIFY=1: skip the shared-prefix window verification
-    bool no_pieces = false;   // DMX_NO_PIECES=1: the full filter pass instead of the piece screen
+    PanelSwitches sw;         // read by dmx_open
     HostPanel panel[2];
     DevPanel* d_panel[2] = {nullptr, nullptr};
     DevPieces* d_pieces[2] = {nullptr, nullptr};
@@ -134,7 +137,7 @@ struct Ctx {
     bool ring_small[2] = {true, true};
     bool band_ok[2] = {true, true};
     bool band_wide[2] = {true, true};      // some adapter has kk 6..7: list 1 needs 15 diagonals
-    bool orient_slot[2] = {false, false};   // per round: one winner slot per (item, orientation)   // every adapter has kk <= 7: banded resolve
+    bool orient_slot[2] = {false, false};   // per round: one winner slot per (item, orientation)
     bool force_ring = false;          // DMX_RESOLVE=ring (A/B testing)
     size_t slot_cap = 0;
     Cluster* d_cl[2] = {nullptr, nullptr};
@@ -154,9 +157,6 @@ struct Ctx {
     unsigned long long* d_linked = nullptr;
     Window* d_tasks = nullptr;           // index screen survivors (window piece of one adapter)
     size_t task_cap = 0;
-    uint32_t* d_stage = nullptr;         // window code slots (wstage_kernel), kStageWords each
-    size_t stage_cap = 0;
-    bool use_stage = false;              // DMX_STAGE=1 (A/B, measured slower: DESIGN.md §3.13)
     FTask* d_ftask = nullptr;            // piece screen -> filter tasks
     size_t ftask_cap = 0;
     // flat piece scan (prepare_flat): one scan of the batch against the flat rounds' combined
@@ -173,7 +173,6 @@ struct Ctx {
     size_t cells_words = 0;
     bool no_screen = false;              // DMX_NO_SCREEN=1: every window runs every adapter
     bool screen_v1 = false;              // DMX_SCREEN_V1=1: one lane per (window, adapter) screen
-    bool near_all = false;               // DMX_NEAR_ALL=1: near pieces keep every adapter's columns
     size_t n_counts = 0;
     hipEvent_t ev[21] = {};   // [3r..3r+2] round r stages, [6+r] finalize, [8] start,
                               // [9+2r] after filter, [10+2r] after verify, [13+r] after screen,

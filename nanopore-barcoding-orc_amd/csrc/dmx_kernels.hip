@@ -61,8 +61,6 @@ struct RoundArgs {
     FTask* ftask;                // piece screen -> filter tasks
     uint32_t* ftask_count;       // [kShards]: shard s at ftask + s * ftask_scap
     uint32_t ftask_scap;
-    uint32_t* stage;             // window code slots (wstage_kernel), stage_cap of them
-    uint32_t stage_cap;
     // flat piece scan: cell bitmaps [2 round + strand], kCellGuardWords words before index 0
     uint32_t n_words;
     uint32_t nsb;                // 4096-nt superblocks of the packed batch
@@ -74,20 +72,16 @@ struct RoundArgs {
 // conditions that only compare lower bounds of edit costs with thresholds.  Reading a read's
 // non-ACGT bases as the 2-bit code packed for them (A) instead of "matches nothing" can only turn
 // a mismatch into a match, so every cost they compute can only go down: they stay necessary
-// conditions, and the exact stages (window scan, band DP) still see the no-match mask.  So by
-// default those three never use the mask (DMX_MASK_SKIP=0: the round-4 behaviour, for A/B).
-#ifndef DMX_MASK_SKIP
-#define DMX_MASK_SKIP 1
-#endif
-constexpr bool kNecessaryMask = !DMX_MASK_SKIP;
+// conditions, and the exact stages (window scan, band DP) still see the no-match mask.  So
+// those three never use the mask.
 
 struct TaskView {
     uint32_t read, n, strand, start, len;
     uint64_t off;
     int o, a;
     bool clean = false;   // the exact stages may skip the no-match mask (Window kWinClean)
-    uint32_t tag = 0;     // window code slot + 1 (0: gather from the packed batch)
-    uint32_t sbl = 0;     // the slot's base column + kViewReachPre (bits 0..23), filled columns
+    uint32_t tag = 0;     // always 0, and sbl with it: what is left of the window code slots
+    uint32_t sbl = 0;     // (view_off below)
 };
 
 // A pointer moved into SGPRs (readfirstlane) in the global address space: a per-lane select
@@ -118,43 +112,19 @@ __device__ __forceinline__ void store_cand(__attribute__((address_space(1))) Can
     *reinterpret_cast<__attribute__((address_space(1))) u32x2_t*>(d + 32) = c;
 }
 
-// A record's `off` field -> the view's first nt and its window code slot (kStageWords).
-__device__ __forceinline__ void view_off(const Packed& pk, uint64_t off, TaskView& tv) {
+// A record's `off` field -> the view's first nt.  The mask, TaskView's two zero words and the OR in
+// make_cand are kept from the removed window code slots on purpose: without them
+// verify, both screens, pcompact, the window scan and the band compile to other instructions, and
+// their stage times move against the parent's.
+__device__ __forceinline__ void view_off(uint64_t off, TaskView& tv) {
     tv.off = off & kOffMask;
-    tv.tag = DMX_STAGE_SLOTS ? (uint32_t)(off >> kOffBits) : 0u;
+    tv.tag = 0;
     tv.sbl = 0;
-    if (DMX_STAGE_SLOTS && tv.tag) {
-        const uint2 h = *reinterpret_cast<const uint2*>(pk.stage + (size_t)(tv.tag - 1) *
-                                                                      kStageWords + 12);
-        tv.sbl = (h.x + kViewReachPre) | (h.y << 24);
-    }
 }
 
-// 16 view positions from p out of the view's window code slot, when it holds them: the same
-// codes and no-match bits as the gather (wstage_kernel filled the slot with fetch16s).
-__device__ __forceinline__ bool staged16(const Packed& pk, const TaskView& tv, int p, bool mask,
-                                         uint32_t& codes, uint32_t& nbits) {
-    if (!DMX_STAGE_SLOTS || !tv.tag) return false;
-    const int rel = p + kViewReachPre - (int)(tv.sbl & 0xFFFFFFu);
-    if (rel < 0 || rel + 16 > (int)(tv.sbl >> 24)) return false;
-    const uint32_t* sl = pk.stage + (size_t)(tv.tag - 1) * kStageWords;
-    uint64_t c;
-    __builtin_memcpy(&c, sl + (rel >> 4), 8);
-    codes = (uint32_t)(c >> (2 * (rel & 15)));
-    if (mask) {
-        uint64_t m;
-        __builtin_memcpy(&m, sl + 8 + (rel >> 5), 8);
-        nbits = (uint32_t)(m >> (rel & 31)) & 0xFFFFu;
-    } else {
-        nbits = 0u;
-    }
-    return true;
-}
-
-// fetch16 of a view that may have a window code slot
+// fetch16 of a view
 __device__ __forceinline__ void fetch16t(const Packed& pk, const TaskView& tv, uint32_t p,
                                          uint32_t& codes, uint32_t& nbits, bool load_mask = true) {
-    if (staged16(pk, tv, (int)p, load_mask, codes, nbits)) return;
     fetch16(pk, tv.off, tv.n, tv.strand, tv.start, p, codes, nbits, load_mask);
 }
 
@@ -467,12 +437,9 @@ struct ShardMap {
     }
 };
 
-#ifndef DMX_WSCAN_LANE_ROWS   // window-scan per-lane match-vector rows (A/B, off: see wscan_task)
-#define DMX_WSCAN_LANE_ROWS 0
+#ifndef DMX_WAVE_CAND_CAP   // rare: cells of earlier 64-column segments (32 vs 16: 46.51 vs
+#define DMX_WAVE_CAND_CAP 32   // 46.85 ms, profiles/r5_ab_wscan_waves_candcap.txt)
 #endif
-#ifndef DMX_WAVE_CAND_CAP   // rare: cells of earlier 64-column segments (16 with the window
-#define DMX_WAVE_CAND_CAP (DMX_WSCAN_LANE_ROWS ? 16 : 32)   // scan's per-lane rows, to make room
-#endif   // in LDS; 32 vs 16: 46.51 vs 46.85 ms, profiles/r5_ab_wscan_waves_candcap.txt)
 #ifndef DMX_WAVE_CAND_FLUSH
 #define DMX_WAVE_CAND_FLUSH (DMX_WAVE_CAND_CAP / 2)
 #endif
@@ -498,7 +465,7 @@ __device__ __forceinline__ Cand make_cand(const TaskView& tv, uint32_t item, int
     c.o = (uint8_t)tv.o;
     c.a = (uint8_t)tv.a;
     c.clean = tv.clean ? 1 : 0;
-    c.off = tv.off | ((uint64_t)tv.tag << kOffBits);
+    c.off = tv.off | ((uint64_t)tv.tag << kOffBits);   // (tag is 0: see view_off)
     return c;
 }
 
@@ -521,7 +488,6 @@ template <bool MASK = true>
 __device__ __forceinline__ void fetch16s(const Packed& pk, const TaskView& tv, int p,
                                          uint32_t& codes, uint32_t& nbits) {
     p = max(p, -kViewReachPre);
-    if (staged16(pk, tv, p, MASK && !tv.clean, codes, nbits)) return;
     if (tv.strand == 0) {
         const int64_t g = (int64_t)tv.off + (int64_t)tv.start + p;
         codes = code32(pk, g);
@@ -710,10 +676,7 @@ __device__ __forceinline__ void emit_cands(const RoundArgs& R, const CandOut& co
         put(co.mlist, make_cand(tv, item, sub, m, col_cost(co.pv, co.mv, m), tv.len));
 }
 
-// PSTRIDE: u64 between a match vector table's code rows; ZROW: the table has one code row per
-// read code 0..3 plus an all-zero row 4 for non-ACGT (the window scan's per-lane rows) instead
-// of the panel table's rows 4..7.
-template <int HB, class Sink, int PSTRIDE = kPeqStride, bool ZROW = false>
+template <int HB, class Sink>
 __device__ __forceinline__ int scan_task_cand_hb(const RoundArgs& R, const Sink& sink,
                                                  const TaskView& tv, uint32_t item, int sub,
                                                  const uint64_t* peq, int A, AdLite ad,
@@ -779,7 +742,7 @@ __device__ __forceinline__ int scan_task_cand_hb(const RoundArgs& R, const Sink&
 #define DMX_CAND_EQ                                                                       \
     const auto eqv = [&](int q) __attribute__((always_inline)) {                          \
         const uint32_t cq = (codes >> (2 * q)) & 3u, nq = (nb >> q) & 1u;                 \
-        return peq[(ZROW ? (nq ? 4u : cq) : (cq | (nq << 2))) * PSTRIDE];                 \
+        return peq[(cq | (nq << 2)) * kPeqStride];                                        \
     };
 
     uint32_t p0 = js;
@@ -900,7 +863,7 @@ __device__ __forceinline__ int scan_task_cand_hb(const RoundArgs& R, const Sink&
 
 // The last adapter row's bit sits in the low or the high word of the 64-bit vectors; both
 // variants are compiled so the step needs no per-column select.
-template <class Sink, int PSTRIDE = kPeqStride, bool ZROW = false>
+template <class Sink>
 __device__ __forceinline__ int scan_task_cand(const RoundArgs& R, const Sink& sink,
                                               const TaskView& tv, uint32_t item, int sub,
                                               const uint64_t* peq, int A, AdLite ad,
@@ -909,10 +872,10 @@ __device__ __forceinline__ int scan_task_cand(const RoundArgs& R, const Sink& si
                                               uint32_t jhi, bool lastcol,
                                               CandOut* out = nullptr) {
     if (ad.m > 32)
-        return scan_task_cand_hb<1, Sink, PSTRIDE, ZROW>(R, sink, tv, item, sub, peq, A, ad, acc,
-                                                         pacc, js, real, jlo, jhi, lastcol, out);
-    return scan_task_cand_hb<0, Sink, PSTRIDE, ZROW>(R, sink, tv, item, sub, peq, A, ad, acc,
-                                                     pacc, js, real, jlo, jhi, lastcol, out);
+        return scan_task_cand_hb<1, Sink>(R, sink, tv, item, sub, peq, A, ad, acc, pacc, js, real,
+                                          jlo, jhi, lastcol, out);
+    return scan_task_cand_hb<0, Sink>(R, sink, tv, item, sub, peq, A, ad, acc, pacc, js, real, jlo,
+                                      jhi, lastcol, out);
 }
 
 #define DMX_CAND_STAGE                                                                    \
@@ -1190,10 +1153,7 @@ struct SegState {
 
 // The filter's clean-flag history spans clean_reach (<= 128) positions before the segment and
 // the segment itself in 16-position chunks: 64 bits hold it for spans up to 768.
-#ifndef DMX_CLEAN_OFF   // A/B: 1 = no clean flags (every window loads the mask, round 4)
-#define DMX_CLEAN_OFF 0
-#endif
-constexpr bool kCleanHist = !DMX_CLEAN_OFF && (kSegSpan + 128) / 16 + 4 <= 64;
+constexpr bool kCleanHist = (kSegSpan + 128) / 16 + 4 <= 64;
 
 // Is the no-match mask zero over the view positions an exact stage reads for window [w1, w2]
 // (columns): [w1 - rb, w2 - 1], clipped at the view start?  (Positions outside the view are
@@ -1244,28 +1204,22 @@ __device__ __forceinline__ uint32_t spread_codes(uint32_t codes, uint32_t sel) {
 // and the prefix-max acceptance pf[j + kf] near the view start; beyond them every column's
 // threshold is kf_far (the host checks pf[j + kf] >= kf_far for j > 64).
 template <bool CAREFUL>
-__device__ __forceinline__ void filter_chunk(uint32_t codes, uint32_t nb, uint32_t p0, int cnt,
-                                             SegState& S, const uint32_t* s_fpeq,
-                                             const int8_t* s_thr, int kf_far, uint32_t gap,
+__device__ __forceinline__ void filter_chunk(uint32_t codes, uint32_t p0, int cnt, SegState& S,
+                                             const uint32_t* s_fpeq, const int8_t* s_thr,
+                                             int kf_far, uint32_t gap,
                                              uint32_t hit_from, int rb,
                                              const WaveStage<Window, kWaveWinCap>& st,
                                              uint32_t item, int o,
                                              const TaskView& tv) {
     uint32_t eq[16];
-    // N read as A unless kNecessaryMask: the spread path for every chunk
-    if (!kNecessaryMask || __builtin_amdgcn_ballot_w64(nb != 0u) == 0) {   // byte offsets
-        const uint32_t lo = spread_codes(codes, 0x0c010c00u);
-        const uint32_t hi = spread_codes(codes, 0x0c030c02u);
-        const char* base = reinterpret_cast<const char*>(s_fpeq);
+    // N read as A: the codes spread to LDS byte offsets, for every chunk
+    const uint32_t lo = spread_codes(codes, 0x0c010c00u);
+    const uint32_t hi = spread_codes(codes, 0x0c030c02u);
+    const char* base = reinterpret_cast<const char*>(s_fpeq);
 #pragma unroll
-        for (int q = 0; q < 16; ++q)
-            eq[q] = *reinterpret_cast<const uint32_t*>(
-                base + __builtin_amdgcn_ubfe(q < 8 ? lo : hi, 4 * (q & 7), 4));
-    } else {
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-            eq[q] = s_fpeq[((codes >> (2 * q)) & 3u) | (((nb >> q) & 1u) << 2)];
-    }
+    for (int q = 0; q < 16; ++q)
+        eq[q] = *reinterpret_cast<const uint32_t*>(
+            base + __builtin_amdgcn_ubfe(q < 8 ? lo : hi, 4 * (q & 7), 4));
     uint4 tw = {0u, 0u, 0u, 0u};
     if constexpr (CAREFUL)   // 16 per-position thresholds (s_thr: 16-byte aligned rows)
         tw = *reinterpret_cast<const uint4*>(s_thr + (hit_from == 0 ? p0 : 240u));
@@ -1285,10 +1239,8 @@ __device__ __forceinline__ void filter_chunk(uint32_t codes, uint32_t nb, uint32
         cm = min(cm, S.e);
     }
     hits &= cnt >= 16 ? 0xFFFFu : (cnt > 0 ? (0xFFFFu << (16 - cnt)) & 0xFFFFu : 0u);
-#ifdef DMX_FILTER_NO_HITS   // timing A/B only (results invalid): the filter without windows.
-    asm volatile("" ::"v"(hits), "v"(cm));   // The scan stays live.  Round 5: filter 11.45 /
-    hits = 0;                                // 11.69 -> 10.91 / 10.90 ms, i.e. forming windows
-#endif                                       // costs ~0.6 ms (profiles/r5_ab_filter_no_hits.txt)
+    // (forming the windows below costs ~0.6 ms of the filter's 11.5 ms: round 5,
+    // profiles/r5_ab_filter_no_hits.txt)
     if constexpr (!CAREFUL) {   // warm-up columns (j <= hit_from) of a later segment never hit
         const int nw = (int)hit_from - (int)p0;
         hits &= nw >= 16 ? 0u : (nw <= 0 ? 0xFFFFu : (0xFFFFu >> nw));
@@ -1352,17 +1304,14 @@ __device__ __forceinline__ void filter_segment(const RoundArgs& R, const TaskVie
             const uint32_t pc = p0 + 16u * (uint32_t)c;
             const int cnt = (int)P1 - (int)pc;
             if (careful)
-                filter_chunk<true>(vc[0], vn[0], pc, cnt, S, s_fpeq, s_thr, kf_far, gap,
-                                   hit_from, rb, st, item, o, tv);
+                filter_chunk<true>(vc[0], pc, cnt, S, s_fpeq, s_thr, kf_far, gap, hit_from, rb,
+                                   st, item, o, tv);
             else
-                filter_chunk<false>(vc[0], vn[0], pc, cnt, S, s_fpeq, s_thr, kf_far, gap,
-                                    hit_from, rb, st, item, o, tv);
+                filter_chunk<false>(vc[0], pc, cnt, S, s_fpeq, s_thr, kf_far, gap, hit_from, rb,
+                                    st, item, o, tv);
             vc[0] = vc[1];
             vc[1] = vc[2];
             vc[2] = vc[3];
-            vn[0] = vn[1];
-            vn[1] = vn[2];
-            vn[2] = vn[3];
         }
     }
 }
@@ -1895,9 +1844,6 @@ ps_lookups(const uint32_t* pr, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w
            uint32_t w5) {
     using HitT = typename std::conditional<S == 1, uint64_t, uint32_t>::type;
     HitT hits = 0;
-#if defined(DMX_PS_AB) && DMX_PS_AB == 2   // timing A/B only (results invalid): no lookups
-    asm volatile("" ::"v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(w4), "v"(w5));
-#else
     const uint32_t wv6[6] = {w0, w1, w2, w3, w4, w5};
     const auto row = [&](int u, uint32_t& K) __attribute__((always_inline)) {
         K = align32(wv6[(u >> 4) + 1], wv6[u >> 4], 2u * (u & 15));
@@ -1930,11 +1876,6 @@ ps_lookups(const uint32_t* pr, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w
             hits = ((uint64_t)hi << 32) | lo;
         }
     }
-#endif
-#if defined(DMX_PS_AB) && (DMX_PS_AB == 1 || DMX_PS_AB == 2)   // timing A/B: no checks
-    asm volatile("" ::"v"(hits));
-    hits = 0;
-#endif
     return hits;
 }
 
@@ -2187,11 +2128,7 @@ __device__ __forceinline__ void flat_check(const RoundArgs& R, const CellPtrs& c
                     p1 = cells + w;
                     b1 = bits;
                 } else {
-#if defined(DMX_PS_AB) && DMX_PS_AB == 3   // timing A/B only: no marks
-                    asm volatile("" ::"v"(bits), "v"(cells + w));
-#else
                     __hip_atomic_fetch_or(cells + w, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
                 }
                 c = cend + 1;
             }
@@ -2203,11 +2140,7 @@ __device__ __forceinline__ void flat_check(const RoundArgs& R, const CellPtrs& c
     const uint32_t bl = __shfl_up(b1, 1u, 64);
     const bool dup = (threadIdx.x & 63u) != 0u && pl == pa && (bl & b1) == b1;
     if (p1 && !dup) {
-#if defined(DMX_PS_AB) && DMX_PS_AB == 3
-        asm volatile("" ::"v"(b1), "v"(p1));
-#else
         __hip_atomic_fetch_or(p1, b1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     }
 }
 
@@ -2262,11 +2195,7 @@ __global__ __launch_bounds__(kPScanBlock) void pscan_kernel(RoundArgs R) {
             const uint32_t wi = t >> 4, sh = 2u * (t & 15u);
             const uint64_t lo = ((uint64_t)sbw[wi + 1] << 32) | sbw[wi];
             const uint64_t cw = sh ? (lo >> sh) | ((uint64_t)sbw[wi + 2] << (64u - sh)) : lo;
-#if defined(DMX_PS_AB) && DMX_PS_AB == 4   // timing A/B only: queue without checks
-            asm volatile("" ::"v"(cw));
-#else
             flat_check(R, cp, tb, cw, C0 + p, v);
-#endif
             __builtin_amdgcn_wave_barrier();
         }
     }
@@ -2501,13 +2430,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
     // FRONT panels: a wave costs its widest window (filter windows are ~11 columns wide, a few
     // over 100), so each block takes kSortGroup consecutive windows at a time and runs them in
     // order of their column range, as the screen and the window scan do.
-#ifndef DMX_VERIFY_SORT
-#define DMX_VERIFY_SORT 1
-#endif
-#ifndef DMX_VERIFY_PREFETCH
-#define DMX_VERIFY_PREFETCH 0
-#endif
-    const bool sorted = DMX_VERIFY_SORT && front;
+    const bool sorted = front;
     __shared__ uint32_t s_ord[kSortGroup];
     __shared__ uint32_t s_bin[kSortBins];
     for (uint32_t gb = blockIdx.x * kSortGroup; gb < total; gb += gridDim.x * kSortGroup) {
@@ -2546,22 +2469,13 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
         }
         __syncthreads();
       }
-      // DMX_VERIFY_PREFETCH (A/B, off): the next stride's window record is loaded before this
-      // stride's scan.  Measured slower: 108 VGPRs drop verify to 4 waves, and forcing 5 spills
-      // (verify 1.39 / 1.44 -> 1.47 / 1.51 ms, profiles/r5_ab_verify_prefetch.txt)
-      Window wn{};
-      if (DMX_VERIFY_PREFETCH && threadIdx.x < gn)
-          wn = R.win[sm.phys(gb + (sorted ? s_ord[threadIdx.x] : threadIdx.x))];
+      // (Loading the next stride's window record before this stride's scan measured slower: 108
+      // VGPRs drop verify to 4 waves, and forcing 5 spills: verify 1.39 / 1.44 -> 1.47 / 1.51 ms,
+      // profiles/r5_ab_verify_prefetch.txt)
       for (uint32_t sb = 0; sb < gn; sb += kScanBlock) {   // block-uniform
         const uint32_t li = sb + threadIdx.x;
-        Window wcur{};
-        if (DMX_VERIFY_PREFETCH) {
-            wcur = wn;
-            const uint32_t ln = li + kScanBlock;
-            if (ln < gn) wn = R.win[sm.phys(gb + (sorted ? s_ord[ln] : ln))];
-        }
         if (li < gn) {
-            Window w = DMX_VERIFY_PREFETCH ? wcur : R.win[sm.phys(gb + (sorted ? s_ord[li] : li))];
+            Window w = R.win[sm.phys(gb + (sorted ? s_ord[li] : li))];
             const int len = (int)w.len;
             const bool rows_free = (front && (int)w.j1 <= P->max_mk) || w.bmin == 255;
             // column ranges the prefix block must be evaluated on
@@ -2586,7 +2500,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
                 tv.strand = w.strand & 1u;
                 tv.start = w.start;
                 tv.len = w.len;
-                view_off(R.pk, w.off, tv);
+                view_off(w.off, tv);
                 tv.o = w.o;
                 tv.a = 0;
                 int js = lo - L - kf - 1;              // restricted start: exact from lo on
@@ -2607,7 +2521,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
                 // the columns js + 1 .. hi as 64-position stretches of whole aligned blocks
                 // (one lane per window: the block loads are scattered, so few and wide)
                 const int nst = (hi - js + 63) >> 6;
-                ViewBlocks<kNecessaryMask> vb;   // N read as A: a lower bound of D_pre
+                ViewBlocks<false> vb;   // N read as A: a lower bound of D_pre
                 if (nst > 0) vb.init(R, tv, js);
                 for (int st_i = 0; st_i < nst; ++st_i) {
                     uint32_t vc[4], vn[4];
@@ -2791,18 +2705,18 @@ __global__ __launch_bounds__(kScanBlock) void iscreen_kernel(RoundArgs R) {
                 tv.strand = w.strand & 1u;
                 tv.start = w.start;
                 tv.len = w.len;
-                view_off(R.pk, w.off, tv);
+                view_off(w.off, tv);
                 tv.o = w.o;
                 tv.a = a;
                 uint32_t c0 = 0, n0 = 0, c1 = 0, n1 = 0;   // two chunks in flight
-                if (nch > 0) fetch16s<kNecessaryMask>(R.pk, tv, jb, c0, n0);
-                if (nch > 1) fetch16s<kNecessaryMask>(R.pk, tv, jb + 16, c1, n1);
+                if (nch > 0) fetch16s<false>(R.pk, tv, jb, c0, n0);
+                if (nch > 1) fetch16s<false>(R.pk, tv, jb + 16, c1, n1);
                 for (int k = 0; k < nch && !pass; ++k) {
                     const int p0 = jb + 16 * k;
                     const uint32_t codes = c0, nb = n0;
                     c0 = c1;
                     n0 = n1;
-                    if (k + 2 < nch) fetch16s<kNecessaryMask>(R.pk, tv, p0 + 32, c1, n1);
+                    if (k + 2 < nch) fetch16s<false>(R.pk, tv, p0 + 32, c1, n1);
                     // this chunk's columns p0+1 .. p0+16: the threshold of the regions it touches
                     // and the first column counted (earlier ones are warm-up)
                     const bool inR = rows && p0 + 16 >= xr_lo && p0 + 1 <= xrh;
@@ -2861,56 +2775,6 @@ __global__ __launch_bounds__(kScanBlock) void iscreen_kernel(RoundArgs R) {
     st.flush();
     __syncthreads();
     if (threadIdx.x == 0 && s_nend) atomicAdd(&R.diag[3], s_nend);     // by 3' cells only
-}
-
-// ---------------------------------------------------------------------------------------------
-// Window code slots: the index screen, the window scan and the band each read
-// the codes around a verified window; without slots each gathers them from the packed batch (a
-// few random 64-B lines per window and stage).  One lane per (window, 16-column chunk) gathers
-// them once, with the same fetch16s, into the window's slot (kStageWords, dense list order), and
-// tags the record's `off` with slot + 1; tasks and candidates inherit the tag.  The slot covers
-// columns [base, base + 128), base = max(j1 - back, lo) with back = the panel's largest m + k + 1
-// and lo = -min(kViewReachPre, m_max + 7) (no gather reaches further before a view than the
-// band's own), chunks starting at or before the view end (later ones keep the gather).
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kScanBlock) void wstage_kernel(RoundArgs R, Window* wl,
-                                                            const uint32_t* counts, int back,
-                                                            int lo) {
-    __shared__ uint32_t s_spre[kShards + 1];
-    ShardMap sm{s_spre, 0u};
-    sm.load(counts, R.win_scap);
-    const uint32_t nwin = min(sm.total(), R.stage_cap);
-    const uint32_t k = threadIdx.x & 7u;            // the lane's chunk
-    const uint32_t step = (gridDim.x * blockDim.x) >> 3;
-    for (uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) >> 3; g < nwin; g += step) {
-        const uint32_t phys = sm.phys(g);
-        Window* wp = wl + phys;
-        const Window w = *wp;
-        TaskView tv;
-        tv.read = 0;
-        tv.n = w.n;
-        tv.strand = w.strand & 1u;
-        tv.clean = false;                           // the no-match bits always (exact stages)
-        tv.start = w.start;
-        tv.len = w.len;
-        tv.off = w.off & kOffMask;
-        tv.o = w.o;
-        tv.a = 0;
-        const int base = max((int)w.j1 - back, lo);
-        const int nfill = min(max(((int)w.len - base) / 16 + 1, 0), 8);
-        uint32_t codes = 0, nb = 0;
-        if ((int)k < nfill) fetch16s<true>(R.pk, tv, base + 16 * (int)k, codes, nb);
-        uint32_t* sl = R.stage + (size_t)g * kStageWords;
-        sl[k] = codes;
-        const uint32_t nbn = __shfl_down(nb, 1u, 64);   // (the 8 lanes of a window run together)
-        if (!(k & 1u)) sl[8 + (k >> 1)] = nb | (nbn << 16);
-        if (k == 0) {
-            sl[12] = (uint32_t)base;
-            sl[13] = 16u * (uint32_t)nfill;
-            if (base + kViewReachPre < (1 << 24))
-                wp->off = tv.off | ((uint64_t)(g + 1) << kOffBits);
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3266,18 +3130,18 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
                 tv.strand = w.strand & 1u;
                 tv.start = w.start;
                 tv.len = w.len;
-                view_off(R.pk, w.off, tv);
+                view_off(w.off, tv);
                 tv.o = w.o;
                 tv.a = 0;
                 const char* qb = reinterpret_cast<const char*>(s_q);
                 const uint32_t q8 = 8u * (uint32_t)q;   // the lane's quad within a code row
                 Chunk16 nx;                                  // the next chunk, in flight
-                if (nch > 0) nx = chunk16_load<kNecessaryMask>(R.pk, tv, jb);
+                if (nch > 0) nx = chunk16_load<false>(R.pk, tv, jb);
                 for (int kc = 0; kc < nch && (need & ~pass_m); ++kc) {
                     const int p0 = jb + 16 * kc;
                     uint32_t codes, nb;
-                    chunk16_codes<kNecessaryMask>(tv, p0, nx, codes, nb);
-                    if (kc + 1 < nch) nx = chunk16_load<kNecessaryMask>(R.pk, tv, p0 + 16);
+                    chunk16_codes<false>(tv, p0, nx, codes, nb);
+                    if (kc + 1 < nch) nx = chunk16_load<false>(R.pk, tv, p0 + 16);
                     const bool inR = rows && p0 + 16 >= xr_lo && p0 + 1 <= xrh;
                     const bool inE = lastc && p0 + 16 >= xe_lo;
                     const int qlo = min(inR ? xr_lo : (1 << 30), inE ? xe_lo : (1 << 30)) - p0 - 1;
@@ -3401,20 +3265,17 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
 // One (window or piece, adapter) task of the window scan.
 // Window-scan match vectors: the 64 lanes of a wave scan random (task,
 // adapter, code) triples, and a gather of 64-bit vectors from the panel's [code][adapter] table
-// conflicts ~2 extra LDS cycles per read.  DMX_WSCAN_LANE_ROWS=1 (A/B): a lane copies its task's
-// adapter vectors into rows of its own (s_lrow[code][thread], plus a zero row 4 for non-ACGT
-// codes), so the 32 lanes of a ds_read_b64 group read 32 distinct bank pairs.  Measured (round
-// 5, profiles/r5_ab_wscan_lane_rows.txt): conflict cycles per LDS instruction 1.94 / 2.01 ->
+// conflicts ~2 extra LDS cycles per read.  Per-lane copies of the task's adapter vectors
+// (conflict-free rows, 10 KB more LDS) were tried in round 5 and not kept
+// (profiles/r5_ab_wscan_lane_rows.txt): conflict cycles per LDS instruction 1.94 / 2.01 ->
 // 0.62 / 0.83, window scan time unchanged (3.64 / 2.18 vs 3.62 / 2.16 ms): LDS waits are 0.1 %
-// of its wave cycles, it waits on its global gathers.  Off by default (10 KB more LDS).
-constexpr int kLaneRows = 5;
-
+// of its wave cycles, it waits on its global gathers.
 template <bool BAND, class ClStage, class Sink>
 __device__ __forceinline__ void wscan_task(const RoundArgs& R, const Window& w, int a, int A,
                                            const uint64_t* s_peq, const int8_t* s_acc,
                                            const int8_t* s_pacc, const uint32_t* s_amk,
                                            const ClStage& st, const Sink& sink, CandOut& co,
-                                           TaskView& tv, int& sub, uint64_t* lrow) {
+                                           TaskView& tv, int& sub) {
     sub = w.o * A + a;
     tv.read = 0;
     tv.n = w.n;
@@ -3422,7 +3283,7 @@ __device__ __forceinline__ void wscan_task(const RoundArgs& R, const Window& w, 
     tv.clean = (w.strand & kWinClean) != 0;
     tv.start = w.start;
     tv.len = w.len;
-    view_off(R.pk, w.off, tv);
+    view_off(w.off, tv);
     tv.o = w.o;
     tv.a = a;
     const AdLite ad = ad_lite(s_amk[a]);
@@ -3430,14 +3291,7 @@ __device__ __forceinline__ void wscan_task(const RoundArgs& R, const Window& w, 
     const bool real = js <= 0;
     if (real) js = 0;
     int lb;
-    if constexpr (BAND && DMX_WSCAN_LANE_ROWS) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) lrow[c * kScanBlock] = s_peq[c * kPeqStride + a];
-        lb = scan_task_cand<Sink, kScanBlock, true>(R, sink, tv, w.item, sub, lrow, A, ad,
-                                                    s_acc + 72 * a, s_pacc + 72 * a,
-                                                    (uint32_t)js, real, w.j1, w.j2,
-                                                    w.lastcol != 0, &co);
-    } else if constexpr (BAND) {
+    if constexpr (BAND) {
         lb = scan_task_cand(R, sink, tv, w.item, sub, s_peq + a, A, ad, s_acc + 72 * a,
                             s_pacc + 72 * a, (uint32_t)js, real, w.j1, w.j2,
                             w.lastcol != 0, &co);
@@ -3465,14 +3319,6 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
     __shared__ uint32_t s_clcnt, s_clbase;
     __shared__ Cand s_wcand[BAND ? kScanBlock / 64 : 1][2][kWaveCandCap];
     __shared__ uint32_t s_wcn[kScanBlock / 64][2];
-    constexpr bool kRows = BAND && DMX_WSCAN_LANE_ROWS;
-    __shared__ uint64_t s_lrow[kRows ? kLaneRows * kScanBlock : 1];   // [code][thread]
-    if constexpr (kRows) s_lrow[4 * kScanBlock + threadIdx.x] = 0ull;   // non-ACGT: no match
-    uint64_t* const lrow = s_lrow + (kRows ? threadIdx.x : 0u);
-#ifdef DMX_WSCAN_LDS_PAD   // A/B: occupancy cap through LDS
-    __shared__ uint32_t s_pad[DMX_WSCAN_LDS_PAD / 4];
-    if (threadIdx.x == 0) s_pad[R.n_items & 7] = 0;
-#endif
     if (threadIdx.x == 0) s_clcnt = 0;
     if (threadIdx.x < 2 * (kScanBlock / 64)) (&s_wcn[0][0])[threadIdx.x] = 0;
     const Stage<Cluster> st{s_cl, &s_clcnt, &s_clbase, R.cl, R.cl_count, R.cl_cap, R.flags, 1u};
@@ -3560,7 +3406,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
                     const Window w = tl[sm.phys(gb + (sorted ? s_ord[li] : li))];
                     item = w.item;
                     wscan_task<BAND>(R, w, (int)w.info, A, s_peq, s_acc, s_pacc, s_amk, st, sink, co,
-                                     tv, sub, lrow);
+                                     tv, sub);
                 }
                 if constexpr (BAND) {
                     emit_cands(R, co, tv, item, sub, (int)(s_amk[tv.a] & 255u));
@@ -3594,8 +3440,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(DMX_
             const Window w = wl[sm.phys((uint32_t)(t / A))];
             const int a = (int)(t % A);
             item = w.item;
-            wscan_task<BAND>(R, w, a, A, s_peq, s_acc, s_pacc, s_amk, st, sink, co, tv, sub,
-                             lrow);
+            wscan_task<BAND>(R, w, a, A, s_peq, s_acc, s_pacc, s_amk, st, sink, co, tv, sub);
         }
         if constexpr (BAND) {                        // wave-uniform: no block barrier
             emit_cands(R, co, tv, item, sub, (int)(s_amk[tv.a] & 255u));
@@ -4061,10 +3906,6 @@ __device__ __forceinline__ void band_dp_cost(int wc, bool fast, const uint8_t* r
 // wave runs the narrowest band its cells allow (band_dp_cost).  The slot's best is the minimum
 // key over all its candidates (key order = locate's / best_match's / ReverseComplementer's order);
 // the key carries the cell's origin (make_key_o), so the atomicMin is all a cell ever writes.
-#ifndef DMX_BAND_SPLIT   // list 1 in two launches, cost 4 then cost 5 (0: one launch)
-#define DMX_BAND_SPLIT 1
-#endif
-constexpr bool kBandSplit = DMX_BAND_SPLIT != 0;
 template <int CMIN, int CMAX>
 // Occupancy floors of list 0 (costs 1..3) and list 1 with kk <= 5: the DP passes wait on their
 // cells' loads, and 8 / 6 waves per SIMD (64 / 80 VGPRs) measured 8.44 -> 8.28 ms
@@ -4164,16 +4005,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
                 tv.clean = c.clean != 0;
                 tv.start = c.start;
                 tv.len = c.len;
-                view_off(R.pk, c.off, tv);
+                view_off(c.off, tv);
                 tv.o = c.o;
                 tv.a = c.a;
                 int c2, origin, score;
-#ifdef DMX_BAND_SKIP_DP   // timing A/B only (results invalid): the band stage without its DPs
-                c2 = cst;
-                origin = (int)(c.j) - iend;
-                score = (int)wc;
-                if (false)
-#endif
                 if (e == 0)
                     band_dp_cost<CMIN == 0 ? 1 : CMIN, CMAX, false>(
                         wc, fast, s_rm + c.a, R.pk, tv, ad.front, iend, j, c2,
@@ -4843,12 +4678,6 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
     R.ftask = c->d_ftask;
     R.ftask_count = c->d_shard + (kShFtask + round) * kShards * kShardStride;
     R.ftask_scap = (uint32_t)(c->ftask_cap / kShards);
-    // window code slots: band-mode window scans of this pipeline, offsets that leave tag bits
-    R.stage = (DMX_STAGE_SLOTS && c->d_stage && !linked && hp.filter && band && c->use_stage &&
-               (uint64_t)c->n_words * 16 < (1ull << kOffBits))
-                  ? c->d_stage : nullptr;
-    R.stage_cap = (uint32_t)c->stage_cap;
-    R.pk.stage = c->d_stage;
     R.n_words = (uint32_t)c->n_words;
     R.nsb = (uint32_t)((c->n_words + kSuperNt / 16 - 1) / (kSuperNt / 16));
     R.round = round;
@@ -4917,14 +4746,6 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
         if (hp.verify)
             hipLaunchKernelGGL(verify_kernel, dim3(256 * 8), dim3(kScanBlock), 0, st, R);
         DMX_DBG_SYNC("verify_kernel");
-        if (R.stage) {   // window code slots for the screen, the window scan and the band
-            set_kid(R.pk.bd, kKerVerify);
-            const bool v = hp.pre_len != 0;   // the window scan's list (wscan_kernel)
-            hipLaunchKernelGGL(wstage_kernel, dim3(256 * 8), dim3(kScanBlock), 0, st, R,
-                               v ? c->d_win2 : c->d_win, v ? R.win2_count : R.win_count,
-                               hp.stage_back, hp.stage_lo);
-            DMX_DBG_SYNC("wstage_kernel");
-        }
         hipEventRecord(c->ev[10 + 2 * round], st);
         if (R.screen) {   // packed quads for panels of <= 32 adapters (DMX_SCREEN_V1: A/B)
             if (hp.n <= 4 * kScreenQuads && !c->screen_v1) {
@@ -4961,13 +4782,11 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
         hipLaunchKernelGGL((band_cand_kernel<0, 3>), dim3(256 * 8), dim3(256), 0, st, R, 0, 0);
         DMX_DBG_SYNC("band_cand_kernel<0, 3>");
         set_kid(R.pk.bd, kKerBand1);
-        if (c->band_wide[round] && kBandSplit) {   // costs 4, 5, then 6..7 (as below)
+        if (c->band_wide[round]) {   // costs 4, 5, then 6..7 (as below)
             hipLaunchKernelGGL((band_cand_kernel<4, 7>), dim3(256 * 4), dim3(256), 0, st, R, 1, 16);
             hipLaunchKernelGGL((band_cand_kernel<4, 7>), dim3(256 * 4), dim3(256), 0, st, R, 1, 32);
             hipLaunchKernelGGL((band_cand_kernel<4, 7>), dim3(256 * 4), dim3(256), 0, st, R, 1, 192);
-        } else if (c->band_wide[round]) {
-            hipLaunchKernelGGL((band_cand_kernel<4, 7>), dim3(256 * 4), dim3(256), 0, st, R, 1, 0);
-        } else if (kBandSplit) {
+        } else {
             // every cost in list 1 is <= 5 (a band of 2 * 5 + 1 diagonals is exact).  The cost-4
             // cells first: their exact keys are in the winner slots when the cost-5 launch
             // screens its cells (a cost-5 cell's score is at most 49 of 59, below a cost-4
@@ -4975,8 +4794,6 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
             // -> 2.98 / 2.15 ms per round, profiles/r6_ab_band_list1_split.txt).
             hipLaunchKernelGGL((band_cand_kernel<4, 5>), dim3(256 * 4), dim3(256), 0, st, R, 1, 16);
             hipLaunchKernelGGL((band_cand_kernel<4, 5>), dim3(256 * 4), dim3(256), 0, st, R, 1, 32);
-        } else {
-            hipLaunchKernelGGL((band_cand_kernel<4, 5>), dim3(256 * 4), dim3(256), 0, st, R, 1, 0);
         }
         DMX_DBG_SYNC("band_cand_kernel<4, 5|7>");
         // (no selection pass: the winning key carries its origin, make_key_o)

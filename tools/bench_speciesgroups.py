@@ -10,7 +10,7 @@ groups, 10 by default; 0 skips it).  The gene groups are sorter.gene_groups', ma
       dmx_pairhits_cross, dmx_hitgroups_within), with the device times of the histogram, the last
       compaction and the components run from dmx_hitgroups_stats, and the number of cross hits.
 Medians of --reps calls after --warmup.  Writes one JSON record; `library` names the libdmx it
-ran on (DMX_LIBDMX selects a variant build, e.g. the histogram's per-wave aggregation)."""
+ran on (DMX_LIBDMX selects another build of it)."""
 import argparse
 import json
 import os
