@@ -322,6 +322,49 @@ def same_records(a: np.ndarray, b: np.ndarray) -> np.ndarray:
                        b.view(np.uint8).reshape(len(b), -1)).any(axis=1))[0]
 
 
+def _pack_at(reads, offsets):
+    """Caller-packed batch with read i at nt offset offsets[i] (dmx_run's layout contract)."""
+    end = max(o + len(r) for o, r in zip(offsets, reads)) + 64
+    words = (end + 15) // 16 + 1
+    code = np.zeros(words * 16, dtype=np.uint32)
+    mask = np.zeros(words * 32, dtype=np.uint8)
+    lut = np.full(256, 4, dtype=np.uint8)
+    lut[np.frombuffer(b"ACGT", dtype=np.uint8)] = np.arange(4, dtype=np.uint8)
+    for o, r in zip(offsets, reads):
+        c = lut[np.frombuffer(r.encode("ascii"), dtype=np.uint8)]
+        code[o:o + len(r)] = c & 3
+        code[o:o + len(r)][c == 4] = 0
+        mask[o:o + len(r)] = c == 4
+    seq = (code.reshape(words, 16) << (2 * np.arange(16, dtype=np.uint32))).sum(
+        axis=1, dtype=np.uint64).astype(np.uint32)
+    nm = np.packbits(mask.reshape(words, 32), axis=1, bitorder="little").view("<u4").reshape(words)
+    return lib.Packed(seq, np.ascontiguousarray(nm), np.array(offsets, dtype=np.uint64),
+                      np.array([len(r) for r in reads], dtype=np.uint32))
+
+
+def host_round(seqs, wheres, reads, rc: bool, e: float, overlap: int) -> np.ndarray:
+    """One single round by the host twin, with demux's signature."""
+    blob, offs, lens = oracle.pack_ascii(reads)
+    return lib.ends_host(seqs, wheres, lib.pack(blob, offs, lens), rc, e, overlap)
+
+
+def two_round_expected(reads, r0, r1, single=host_round) -> np.ndarray:
+    """DMX_MODE_TWO_ROUND as two single rounds: round 0 on the reads, the reads it matched
+    trimmed in Python, round 1 on those.  r0, r1 = (seqs, wheres, rc, e, overlap); `single` is
+    host_round (the host twin) or demux (the Python oracle)."""
+    s0, w0, rc0, e0, o0 = r0
+    s1, w1, rc1, e1, o1 = r1
+    exp = single(s0, w0, reads, rc0, e0, o0).copy()
+    keep = np.nonzero(exp["bin1"] >= 0)[0]
+    t1 = [trimmed(reads[i], exp[i], w0) for i in keep]
+    x1 = single(s1, w1, t1, rc1, e1, o1)
+    for f in ("rstart", "rstop", "astart", "astop", "score", "errors"):
+        exp["m2_" + f][keep] = x1["m1_" + f]
+    exp["bin2"][keep] = x1["bin1"]
+    exp["rc2"][keep] = x1["rc1"]
+    return exp
+
+
 def run_group(ctx, g: Group) -> np.ndarray:
     ctx.set_panel_ex(0, g.seqs, g.wheres, g.rc, g.e, g.overlap)
     ctx.set_mode(lib.MODE_SINGLE)

@@ -24,23 +24,6 @@ def test_kernels_equal_the_host_twin_on_the_case_set(ctx):
     assert n > 1500
 
 
-def _pack_at(reads, offsets):
-    """Caller-packed batch with read i at nt offset offsets[i] (dmx_run's layout contract)."""
-    end = max(o + len(r) for o, r in zip(offsets, reads)) + 64
-    words = (end + 15) // 16 + 1
-    seq = np.zeros(words, dtype=np.uint32)
-    nm = np.zeros(words, dtype=np.uint32)
-    for o, r in zip(offsets, reads):
-        for x, ch in enumerate(r):
-            g = o + x
-            if ch in "ACGT":
-                seq[g >> 4] |= np.uint32("ACGT".index(ch) << (2 * (g & 15)))
-            else:
-                nm[g >> 5] |= np.uint32(1 << (g & 31))
-    return lib.Packed(seq, nm, np.array(offsets, dtype=np.uint64),
-                      np.array([len(r) for r in reads], dtype=np.uint32))
-
-
 def test_views_at_word_boundaries(ctx):
     """Reads at nt offsets = 0, 15 and 16 mod 16 with 63, 64 and 65 nt, both strands, every
     restricted type, an adapter as long as the window's first gather (16) and longer."""
@@ -59,7 +42,7 @@ def test_views_at_word_boundaries(ctx):
                         pos = (pos + 15) // 16 * 16 + 16 + base
                         offsets.append(pos)
                         pos += n
-        p = _pack_at(reads, offsets)
+        p = ec._pack_at(reads, offsets)
         ctx.set_panel_ex(0, seqs, wheres, True, 0.1, 3)
         ctx.set_mode(lib.MODE_SINGLE)
         got = ctx.run(p)
@@ -124,16 +107,7 @@ def test_two_round_prefix_then_suffix(ctx):
     ctx.load(p)
     ctx.exec()
     got = ctx.fetch()
-    r0 = lib.ends_host(s0, w0, p, True, 0.1, 3)
-    keep = np.nonzero(r0["bin1"] >= 0)[0]
-    t1 = [ec.trimmed(reads[i], r0[i], w0) for i in keep]
-    blob1, offs1, lens1 = oracle.pack_ascii(t1)
-    r1 = lib.ends_host(s1, w1, lib.pack(blob1, offs1, lens1), True, 0.1, 3)
-    exp = r0.copy()
-    for f in ("rstart", "rstop", "astart", "astop", "score", "errors"):
-        exp["m2_" + f][keep] = r1["m1_" + f]
-    exp["bin2"][keep] = r1["bin1"]
-    exp["rc2"][keep] = r1["rc1"]
+    exp = ec.two_round_expected(reads, (s0, w0, True, 0.1, 3), (s1, w1, True, 0.1, 3))
     assert len(ec.same_records(got, exp)) == 0
     assert (exp["bin2"] >= 0).sum() > 100 and exp["rc1"].sum() > 50
     ctx.exec()
