@@ -234,6 +234,10 @@ int dmx_allreduce_counts(dmx_ctx* ctx, uint64_t* out_counts, size_t n_out);
 int dmx_load(dmx_ctx* ctx, const uint32_t* seq2b, const uint32_t* nmask, const uint64_t* offsets,
              const uint32_t* lens, size_t n_words, size_t n_reads);
 int dmx_exec(dmx_ctx* ctx);
+/* dmx_exec as dmx_run runs it: waits for the pipeline, and when an intermediate list overflowed
+ * grows it and runs again (never a truncated result); DMX_E_STATE on an exactness flag.  For
+ * hosts that keep the batch resident (the view runs below) and want dmx_run's guarantees. */
+int dmx_exec_checked(dmx_ctx* ctx);
 int dmx_sync(dmx_ctx* ctx);
 int dmx_fetch(dmx_ctx* ctx, dmx_result* out);
 
@@ -351,6 +355,48 @@ int dmx_chop_fetch(dmx_ctx* ctx, uint32_t* n_seg, uint32_t* n_hit, dmx_chop_seg*
  * overflowed), [1] the read-order compaction.  Returns the number of 64-read blocks redone with
  * global hit lists (more primer hits than the 512-entry LDS list holds). */
 int dmx_chop_stats(dmx_ctx* ctx, float* ms, int n_ms);
+
+/* ---- Views of the resident reads ----------------------------------------------
+ * Run the demultiplexer on oriented sub-ranges of the resident reads instead of on the reads:
+ * rescued segments, caller-chosen windows, or pychopper's PASS segments without repacking them
+ * (the fused 01 -> 02 loop).  View k is read[k][start[k]:stop[k]] of the batch made resident by
+ * dmx_load, on the read as given, taken reverse-complemented when strand[k] == 1 (the
+ * conventions of dmx_batch_pack_views and dmx_chop_seg).  With a view list set, round 0 of
+ * dmx_exec runs on the views: item k is view k, dmx_fetch writes one result per view (m1 in view
+ * coordinates, m2 on the round-1 output of view k: what dmx_run returns for the batch
+ * dmx_batch_pack_views makes of the same list), dmx_counts counts views.  Views may repeat,
+ * overlap, come in any order, be empty or shorter than min_overlap, and outnumber the reads.
+ * DMX_MODE_SINGLE and DMX_MODE_TWO_ROUND, every adapter type; DMX_MODE_LINKED with views set is
+ * refused by dmx_exec (DMX_E_UNSUPPORTED).  dmx_load, dmx_run, dmx_run_sparse and dmx_run_multi
+ * drop the list (whole-read runs again); dmx_run_multi and the chunked dmx_run are whole-read only.
+ * Everything is checked on the host before anything is uploaded or launched, and a refused call
+ * leaves the context and its current list as they were: no resident batch is DMX_E_STATE; a read
+ * index outside the batch, start < 0, start > stop, stop past the read's end or strand > 1 is
+ * DMX_E_INVALID naming the view; more than 2^31 views is DMX_E_UNSUPPORTED.  (A failed device
+ * allocation, DMX_E_HIP, leaves no list: whole-read runs.)
+ * dmx_fetch copies as many results as the last dmx_exec's round 0 had items, whatever list was
+ * set or cleared since that exec: size its buffer by the list the exec ran on. */
+int dmx_set_views(dmx_ctx* ctx, const uint32_t* read, const int32_t* start, const int32_t* stop,
+                  const uint8_t* strand, size_t n_views);
+/* Back to whole-read runs (no-op without a list). */
+int dmx_clear_views(dmx_ctx* ctx);
+/* The view list made on the device from the last dmx_chop_exec, in read order: read r gives its
+ * segment as a view iff it has exactly one segment, qc_ok == NULL or qc_ok[r] != 0 (one byte per
+ * read) and stop - start >= min_len: pychopper's PASS records.  The segments are not fetched; the
+ * list and its length stay on the device for dmx_exec, *n_views (optional) receives the length.
+ * DMX_E_STATE without a dmx_chop_exec on the current batch. */
+int dmx_chop_views(dmx_ctx* ctx, const uint8_t* qc_ok, int32_t min_len, uint64_t* n_views);
+/* The current list in dmx_set_views' convention, first `cap` views written (any pointer may be
+ * NULL); returns its length (0 without a list), negative on error. */
+int dmx_views_fetch(dmx_ctx* ctx, uint32_t* read, int32_t* start, int32_t* stop,
+                    uint8_t* strand, size_t cap);
+/* Host only (no GPU; tests): dmx_chop_views' rule in plain sequential C++ on dmx_chop_fetch's
+ * arrays (n_seg: per-read segment counts, segs: the records in read order).  First `cap` views
+ * written (any out pointer may be NULL); returns the list's length, negative on error
+ * (dmx_last_error(NULL)). */
+int dmx_chop_views_host(const uint32_t* n_seg, const dmx_chop_seg* segs, const uint8_t* qc_ok,
+                        int32_t min_len, size_t n_reads, uint32_t* read, int32_t* start,
+                        int32_t* stop, uint8_t* strand, size_t cap);
 
 /* ---- Pairwise read distance: the amplicon-sorting stage's similarity pass --------------------
  * Replaces: the edlib.align(A1, A2, task='distance', mode=...) calls of

@@ -79,7 +79,8 @@ size_t counts_size(const Ctx* c) {
 }
 
 int ensure_pipeline(Ctx* c) {
-    const size_t n = c->n_reads;
+    // a view run has one item, winner slot and result per view, and views may outnumber the reads
+    const size_t n = c->views_on ? std::max(c->n_reads, c->n_views) : c->n_reads;
     const bool linked = c->mode == DMX_MODE_LINKED;
     const size_t slots0 = linked ? n * (size_t)std::max(1, c->panel[0].n) : n;
     const size_t items = linked ? slots0 : n;
@@ -123,6 +124,11 @@ int ensure_pipeline(Ctx* c) {
         c->item_alloc = items;
     }
     c->item_cap = items;
+    if (c->views_on && c->mode != DMX_MODE_SINGLE && c->item_src_alloc < items) {
+        int rc;
+        if ((rc = dev_alloc(c, &c->d_item_src, items))) return rc;
+        c->item_src_alloc = items;
+    }
     const size_t want_cl = 4 * std::max(slots0, n) + 65536;
     if (c->cl_cap < want_cl) {
         int rc;
@@ -292,6 +298,20 @@ int reset_counts(Ctx* c) {
     return DMX_OK;
 }
 
+int views_reserve(Ctx* c, size_t n) {
+    CK(hipSetDevice(c->device));
+    if (!c->d_view_n) CK(hipMalloc((void**)&c->d_view_n, sizeof(uint32_t)));
+    if (c->view_alloc < n || !c->d_views) {
+        // the last exec may still read the old list
+        CK(hipStreamSynchronize(c->stream));
+        int rc;
+        c->view_alloc = 0;
+        if ((rc = dev_alloc(c, &c->d_views, n))) return rc;
+        c->view_alloc = std::max<size_t>(n, 1);
+    }
+    return DMX_OK;
+}
+
 bool env_on(const char* name) {
     const char* e = std::getenv(name);
     return e && e[0] == '1';
@@ -356,7 +376,7 @@ void dmx_close(dmx_ctx* c) {
                     c->d_counts,    c->d_panel[0],  c->d_panel[1], c->d_pieces[0], c->d_pieces[1],
                     c->d_ftask, c->d_pieces_flat, c->d_cells[0], c->d_cells[1], c->d_cells[2],
                     c->d_cells[3], c->d_ends[0], c->d_ends[1], c->d_panel_all[0],
-                    c->d_panel_all[1]};
+                    c->d_panel_all[1], c->d_views, c->d_view_n, c->d_item_src};
     for (void* b : bufs)
         if (b) hipFree(b);
     for (int r = 0; r < 2; ++r)
@@ -1099,6 +1119,8 @@ int load_impl(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& mask, const uint
     CK(hipStreamSynchronize(c->stream));
     c->executed = false;
     c->chunked = false;
+    c->views_on = false;   // whole-read runs again (dmx_set_views / dmx_chop_views set a list)
+    c->h_lens.assign(lens, lens + n_reads);   // view lists are checked and rendered against it
     chop_invalidate(c);
     lg_invalidate(c);
     return DMX_OK;
@@ -1255,6 +1277,10 @@ int dmx_exec(dmx_ctx* c) {
         c->err = "linked mode does not take anchored / non-internal adapters";
         return DMX_E_UNSUPPORTED;
     }
+    if (c->mode == DMX_MODE_LINKED && c->views_on) {
+        c->err = "linked mode does not run on views (dmx_clear_views first)";
+        return DMX_E_UNSUPPORTED;
+    }
     CK(hipSetDevice(c->device));
     int rc = ensure_pipeline(c);
     if (rc) return rc;
@@ -1271,7 +1297,7 @@ int dmx_exec(dmx_ctx* c) {
         c->orient_slot[r] = c->mode != DMX_MODE_LINKED && c->panel[r].n_orient == 2 &&
                             c->panel[r].nonpos;
     const size_t slots0 = c->mode == DMX_MODE_LINKED ? c->n_reads * (size_t)c->panel[0].n
-                                                     : c->n_reads * (c->orient_slot[0] ? 2 : 1);
+                                                     : round0_items(c) * (c->orient_slot[0] ? 2 : 1);
     CK(hipMemsetAsync(c->d_winner[0], 0xFF, slots0 * sizeof(unsigned long long), st));
     if ((rc = prepare_flat(c, st))) return rc;
     if ((rc = run_round(c, 0, st))) return rc;
@@ -1283,6 +1309,7 @@ int dmx_exec(dmx_ctx* c) {
         if ((rc = launch_finalize(c, 1, st))) return rc;
     }
     c->executed = true;
+    c->exec_items = round0_items(c);
     return bounds_check(c, "dmx_exec");   // DMX_DEBUG_BOUNDS builds only (else DMX_OK)
 }
 
@@ -1293,7 +1320,7 @@ int dmx_sync(dmx_ctx* c) {
 }
 
 int dmx_fetch(dmx_ctx* c, dmx_result* out) {
-    if (!c || (!out && c->n_reads)) return DMX_E_INVALID;
+    if (!c || (!out && (c->executed ? c->exec_items : c->n_reads))) return DMX_E_INVALID;
     if (!c->executed) {
         c->err = "dmx_fetch before dmx_exec";
         return DMX_E_STATE;
@@ -1303,11 +1330,89 @@ int dmx_fetch(dmx_ctx* c, dmx_result* out) {
         return DMX_E_STATE;
     }
     CK(hipSetDevice(c->device));
-    if (c->n_reads)
-        CK(hipMemcpyAsync(out, c->d_res, c->n_reads * sizeof(dmx_result), hipMemcpyDeviceToHost,
-                          c->stream));
+    if (c->exec_items)   // one result per item of round 0: reads, or the views of a view run
+        CK(hipMemcpyAsync(out, c->d_res, c->exec_items * sizeof(dmx_result),
+                          hipMemcpyDeviceToHost, c->stream));
     CK(hipStreamSynchronize(c->stream));
     return DMX_OK;
+}
+
+int dmx_set_views(dmx_ctx* c, const uint32_t* read, const int32_t* start, const int32_t* stop,
+                  const uint8_t* strand, size_t n_views) {
+    if (!c || (n_views && (!read || !start || !stop || !strand))) return DMX_E_INVALID;
+    if (!c->d_seq || !c->d_lens || c->chunked || c->h_lens.size() != c->n_reads) {
+        c->err = "dmx_set_views: no resident batch (dmx_load first)";
+        return DMX_E_STATE;
+    }
+    if (n_views >= (1ull << 31)) {
+        c->err = "dmx_set_views: too many views in one list";
+        return DMX_E_UNSUPPORTED;
+    }
+    CK(hipSetDevice(c->device));
+    const std::vector<uint32_t>& lens = c->h_lens;   // dmx_load's copy: no device round trip
+    // ItemView's start counts on the view's strand: strand 1 is the reverse complement of the read
+    std::vector<ItemView> v(n_views);
+    for (size_t k = 0; k < n_views; ++k) {
+        const char* why = nullptr;
+        if (read[k] >= c->n_reads) why = "names a read outside the batch";
+        else if (start[k] < 0 || start[k] > stop[k]) why = "has start < 0 or start > stop";
+        else if ((uint32_t)stop[k] > lens[read[k]]) why = "ends past its read";
+        else if (strand[k] > 1) why = "has a strand other than 0 or 1";
+        if (why) {
+            c->err = "dmx_set_views: view " + std::to_string(k) + " " + why;
+            return DMX_E_INVALID;
+        }
+        v[k].read = read[k];
+        v[k].len = (uint32_t)(stop[k] - start[k]);
+        v[k].start = strand[k] ? lens[read[k]] - (uint32_t)stop[k] : (uint32_t)start[k];
+        v[k].strand = strand[k];
+        v[k].pad = 0;
+        v[k].only_adapter = -1;
+    }
+    int rc = views_reserve(c, n_views);
+    if (rc) {
+        c->views_on = false;
+        return rc;
+    }
+    const uint32_t nv = (uint32_t)n_views;
+    if (n_views)
+        CK(hipMemcpyAsync(c->d_views, v.data(), n_views * sizeof(ItemView), hipMemcpyHostToDevice,
+                          c->stream));
+    CK(hipMemcpyAsync(c->d_view_n, &nv, sizeof nv, hipMemcpyHostToDevice, c->stream));
+    CK(hipStreamSynchronize(c->stream));
+    c->n_views = n_views;
+    c->views_on = true;
+    return DMX_OK;
+}
+
+int dmx_clear_views(dmx_ctx* c) {
+    if (!c) return DMX_E_INVALID;
+    c->views_on = false;
+    return DMX_OK;
+}
+
+int dmx_views_fetch(dmx_ctx* c, uint32_t* read, int32_t* start, int32_t* stop,
+                    uint8_t* strand, size_t cap) {
+    if (!c) return DMX_E_INVALID;
+    if (!c->views_on) return 0;
+    const size_t n = std::min(c->n_views, cap);
+    if (n) {
+        CK(hipSetDevice(c->device));
+        std::vector<ItemView> v(n);
+        const std::vector<uint32_t>& lens = c->h_lens;
+        CK(hipMemcpyAsync(v.data(), c->d_views, n * sizeof(ItemView), hipMemcpyDeviceToHost,
+                          c->stream));
+        CK(hipStreamSynchronize(c->stream));
+        for (size_t k = 0; k < n; ++k) {
+            const uint32_t len = v[k].read < lens.size() ? lens[v[k].read] : 0u;
+            const uint32_t a = v[k].strand ? len - v[k].start - v[k].len : v[k].start;
+            if (read) read[k] = v[k].read;
+            if (start) start[k] = (int32_t)a;
+            if (stop) stop[k] = (int32_t)(a + v[k].len);
+            if (strand) strand[k] = v[k].strand;
+        }
+    }
+    return (int)c->n_views;
 }
 
 int dmx_counts(dmx_ctx* c, uint64_t* out, size_t n_out) {
@@ -1606,6 +1711,8 @@ int run_chunked(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& nmask,
         swap_inputs(c);
     }
     c->n_reads = maxn;
+    c->views_on = false;
+    c->h_lens.clear();
     chop_invalidate(c);
     lg_invalidate(c);
     c->chunked = false;
@@ -1676,6 +1783,31 @@ int run_chunked(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& nmask,
 
 namespace {
 
+// dmx_exec until every list held its records: an overflowed list is grown and the pipeline run
+// again, never truncated (dmx_run's one-shot path, dmx_exec_checked).  Synchronises.
+int exec_checked(dmx_ctx* c) {
+    int rc;
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        if ((rc = dmx_exec(c))) return rc;
+        uint64_t cl[8];
+        int flags = 0;
+        float ms[7];
+        if ((rc = dmx_stats(c, ms, 7, cl, 8, &flags))) return rc;
+        if (flags & 18) {
+            c->err = (flags & 2) ? "internal: traceback left the exact window (please report)"
+                                 : "internal: filter task invariant violated (please report)";
+            return DMX_E_STATE;
+        }
+        if (!(flags & 13)) return DMX_OK;
+        // candidate overflow: retry with more room, never truncate
+        if ((flags & 1) && (rc = grow_clusters(c))) return rc;
+        if ((flags & 4) && (rc = grow_windows(c))) return rc;
+        if ((flags & 8) && (rc = grow_cands(c))) return rc;
+    }
+    c->err = "candidate cluster buffer overflow";
+    return DMX_E_NOMEM;
+}
+
 int run_impl(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& mask, const uint64_t* offsets,
              const uint32_t* lens, size_t n_words, size_t n_reads, dmx_result* out) {
     size_t per = (size_t)1 << 21;   // reads per chunk of an overlapped run
@@ -1715,28 +1847,16 @@ int run_impl(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& mask, const uint6
         return run_chunked(c, seq2b, mask, offsets, lens, n_words, n_reads, out, per);
     int rc = load_impl(c, seq2b, mask, offsets, lens, n_words, n_reads);
     if (rc) return rc;
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        if ((rc = dmx_exec(c))) return rc;
-        uint64_t cl[8];
-        int flags = 0;
-        float ms[7];
-        if ((rc = dmx_stats(c, ms, 7, cl, 8, &flags))) return rc;
-        if (flags & 18) {
-            c->err = (flags & 2) ? "internal: traceback left the exact window (please report)"
-                                 : "internal: filter task invariant violated (please report)";
-            return DMX_E_STATE;
-        }
-        if (!(flags & 13)) return dmx_fetch(c, out);
-        // candidate overflow: retry with more room, never truncate
-        if ((flags & 1) && (rc = grow_clusters(c))) return rc;
-        if ((flags & 4) && (rc = grow_windows(c))) return rc;
-        if ((flags & 8) && (rc = grow_cands(c))) return rc;
-    }
-    c->err = "candidate cluster buffer overflow";
-    return DMX_E_NOMEM;
+    if ((rc = exec_checked(c))) return rc;
+    return dmx_fetch(c, out);
 }
 
 }  // namespace
+
+int dmx_exec_checked(dmx_ctx* c) {
+    if (!c) return DMX_E_INVALID;
+    return exec_checked(c);
+}
 
 int dmx_run(dmx_ctx* c, const uint32_t* seq2b, const uint32_t* nmask, const uint64_t* offsets,
             const uint32_t* lens, size_t n_words, size_t n_reads, dmx_result* out) {

@@ -619,6 +619,97 @@ __global__ __launch_bounds__(256) void chop_order_kernel(ChopOrderArgs O) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// PASS segments -> the demultiplexer's view list (dmx_chop_views).  One lane per
+// read, one wave per 64-read block of chop_kernel, so a read's first segment record sits at the
+// block's read-order offset plus the segment counts of the lanes before it.  Order-stable
+// compaction in three launches, as above: per-block counts (COUNT), an exclusive scan over the
+// blocks, then the scatter; a view's place is its block's offset plus the passing lanes below it
+// (ballot, popcount), so no atomic decides the order.
+// ---------------------------------------------------------------------------------------------
+struct ChopViewsArgs {
+    const uint32_t* nseg;      // per read
+    const dmx_chop_seg* segs;  // read order
+    const uint32_t* blkoff;    // per chop block: (hit offset, segment offset)
+    const uint8_t* qc;         // per read, or nullptr (every read passes QC)
+    const uint32_t* lens;
+    uint32_t n_reads;
+    int32_t min_len;
+    uint64_t n_segs;           // records in segs
+    uint32_t* cnt;            // per block: views (COUNT writes it)
+    const uint32_t* off;       // per block: exclusive scan of cnt
+    ItemView* views;
+    uint32_t* err;             // set when a read's segment record lies past n_segs
+    Bounds bd;                 // DMX_DEBUG_BOUNDS: reads, items = segment records, views
+};
+
+template <bool COUNT>
+__global__ __launch_bounds__(64) void chop_views_kernel(ChopViewsArgs A) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    const uint32_t r = b * kChopReads + lane;
+    const bool in = r < A.n_reads && DMX_BOUND(A.bd, reads, r, kBufRead);
+    const uint32_t ns = in ? A.nseg[r] : 0u;
+    // segment records of the lanes below (inclusive scan by shuffles, then made exclusive)
+    uint32_t pre = ns;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t x = __shfl_up(pre, d, 64);
+        if ((int)lane >= d) pre += x;
+    }
+    pre -= ns;
+    bool pass = false;
+    dmx_chop_seg sg{};
+    if (ns == 1 && (!A.qc || A.qc[r])) {
+        const uint64_t si = (uint64_t)A.blkoff[2 * b + 1] + pre;
+        if (si >= A.n_segs) {
+            atomicOr(A.err, 1u);   // the counts and the records disagree: the call fails
+        } else if (DMX_BOUND(A.bd, items, si, kBufChop)) {
+            sg = A.segs[si];
+            pass = sg.stop - sg.start >= A.min_len;
+        }
+    }
+    const uint64_t m = __ballot(pass);
+    if (COUNT) {
+        if (lane == 0) A.cnt[b] = (uint32_t)__popcll(m);
+        return;
+    }
+    if (!pass) return;
+    const uint64_t k = (uint64_t)A.off[b] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (!DMX_BOUND(A.bd, views, k, kBufItem)) return;
+    ItemView v;   // start counts on the view's strand (strand 1: the read reverse-complemented)
+    v.read = r;
+    v.len = (uint32_t)(sg.stop - sg.start);
+    v.strand = sg.strand ? 1 : 0;
+    v.start = sg.strand ? A.lens[r] - (uint32_t)sg.stop : (uint32_t)sg.start;
+    v.pad = 0;
+    v.only_adapter = -1;
+    A.views[k] = v;
+}
+
+// Exclusive scan of the per-block view counts (one block, chop_blkscan_kernel's shape: a run of
+// consecutive blocks per thread); the total goes to *total, round 0's item count.
+__global__ __launch_bounds__(1024) void chop_views_scan_kernel(const uint32_t* cnt, uint32_t nb,
+                                                               uint32_t* off, uint32_t* total) {
+    __shared__ uint32_t s_v[1024];
+    const uint32_t per = (nb + 1023u) / 1024u;
+    const uint32_t lo = min(nb, threadIdx.x * per), hi = min(nb, lo + per);
+    uint32_t v = 0;
+    for (uint32_t b = lo; b < hi; ++b) v += cnt[b];
+    s_v[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t dlt = 1; dlt < 1024u; dlt <<= 1) {
+        const uint32_t x = threadIdx.x >= dlt ? s_v[threadIdx.x - dlt] : 0u;
+        __syncthreads();
+        s_v[threadIdx.x] += x;
+        __syncthreads();
+    }
+    if (threadIdx.x == 1023u) *total = s_v[1023];
+    v = threadIdx.x ? s_v[threadIdx.x - 1] : 0u;
+    for (uint32_t b = lo; b < hi; ++b) {
+        off[b] = v;
+        v += cnt[b];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 struct ChopState {
@@ -648,6 +739,8 @@ struct ChopState {
     bool done = false;
     hipEvent_t ev[4] = {};
     float ms[2] = {0.f, 0.f};
+    DevBuf<uint8_t> qc;              // dmx_chop_views: the QC bytes, per-block counts and offsets
+    DevBuf<uint32_t> vcnt, voff, verr;
     size_t n_big = 0;   // blocks redone by chop_big_kernel in the last exec
     int hb = -1;   // chop_kernel variant: last-row bit in the high (1) / low (0) half, or mixed
 };
@@ -1003,4 +1096,99 @@ extern "C" int dmx_chop_stats(dmx_ctx* c, float* ms, int n_ms) {
     }
     for (int i = 0; i < n_ms && i < 2; ++i) ms[i] = s->ms[i];
     return (int)s->n_big;
+}
+
+extern "C" int dmx_chop_views(dmx_ctx* c, const uint8_t* qc_ok, int32_t min_len,
+                              uint64_t* n_views) {
+    if (!c) return DMX_E_INVALID;
+    ChopState* s = c->chop;
+    if (!s || !s->done || s->n_reads != c->n_reads) {
+        c->err = "dmx_chop_views before dmx_chop_exec on the resident batch";
+        return DMX_E_STATE;
+    }
+    const size_t n = s->n_reads;
+    int rc = views_reserve(c, n);   // at most one view per read
+    if (rc) {
+        c->views_on = false;
+        return rc;
+    }
+    hipStream_t st = c->stream;
+    const uint32_t nb = (uint32_t)((n + kChopReads - 1) / kChopReads);
+    CHOP_CK(s->vcnt.reserve(nb));
+    CHOP_CK(s->voff.reserve(nb));
+    if (qc_ok && n) {
+        CHOP_CK(s->qc.reserve(n));
+        CHOP_CK(hipMemcpyAsync(s->qc.p, qc_ok, n, hipMemcpyHostToDevice, st));
+    }
+    uint32_t total = 0, bad = 0;
+    CHOP_CK(s->verr.reserve(1));
+    CHOP_CK(hipMemsetAsync(s->verr.p, 0, sizeof(uint32_t), st));
+    CHOP_CK(hipMemsetAsync(c->d_view_n, 0, sizeof(uint32_t), st));
+    if (nb) {
+        ChopViewsArgs A;
+        A.nseg = s->d_nseg;
+        A.segs = s->d_segs;
+        A.blkoff = s->d_blkoff;
+        A.qc = qc_ok ? s->qc.p : nullptr;
+        A.lens = c->d_lens;
+        A.n_reads = (uint32_t)n;
+        A.min_len = min_len;
+        A.n_segs = std::min<uint64_t>(s->n_segs, s->seg_cap);
+        A.cnt = s->vcnt.p;
+        A.off = s->voff.p;
+        A.views = c->d_views;
+        A.err = s->verr.p;
+        A.bd = make_bounds(c, kKerChopViews);
+#ifdef DMX_DEBUG_BOUNDS
+        A.bd.items = s->seg_cap;
+#endif
+        CHOP_CK(bounds_reset(c, st));
+        hipLaunchKernelGGL(chop_views_kernel<true>, dim3(nb), dim3(64), 0, st, A);
+        hipLaunchKernelGGL(chop_views_scan_kernel, dim3(1), dim3(1024), 0, st,
+                           (const uint32_t*)s->vcnt.p, nb, s->voff.p, c->d_view_n);
+        hipLaunchKernelGGL(chop_views_kernel<false>, dim3(nb), dim3(64), 0, st, A);
+        CHOP_CK(hipGetLastError());
+        CHOP_CK(hipMemcpyAsync(&total, c->d_view_n, sizeof total, hipMemcpyDeviceToHost, st));
+        CHOP_CK(hipMemcpyAsync(&bad, s->verr.p, sizeof bad, hipMemcpyDeviceToHost, st));
+    }
+    CHOP_CK(hipStreamSynchronize(st));
+    if (const int brc = bounds_check(c, "dmx_chop_views")) return brc;
+    if (bad) {   // never a shorter list: no list at all
+        c->views_on = false;
+        c->err = "dmx_chop_views: internal: segment counts and records disagree (please report)";
+        return DMX_E_STATE;
+    }
+    c->n_views = total;
+    c->views_on = true;
+    if (n_views) *n_views = total;
+    return DMX_OK;
+}
+
+extern "C" int dmx_chop_views_host(const uint32_t* n_seg, const dmx_chop_seg* segs,
+                                   const uint8_t* qc_ok, int32_t min_len, size_t n_reads,
+                                   uint32_t* read, int32_t* start, int32_t* stop,
+                                   uint8_t* strand, size_t cap) {
+    if ((n_reads && !n_seg) || n_reads >= (1ull << 31)) {
+        set_process_error("dmx_chop_views_host: null segment counts or too many reads");
+        return DMX_E_INVALID;
+    }
+    size_t si = 0;
+    int k = 0;
+    for (size_t r = 0; r < n_reads; si += n_seg[r], ++r) {
+        if (n_seg[r] != 1 || (qc_ok && !qc_ok[r])) continue;
+        if (!segs) {
+            set_process_error("dmx_chop_views_host: segment counts without records");
+            return DMX_E_INVALID;
+        }
+        const dmx_chop_seg& g = segs[si];
+        if (g.stop - g.start < min_len) continue;
+        if ((size_t)k < cap) {
+            if (read) read[k] = (uint32_t)r;
+            if (start) start[k] = g.start;
+            if (stop) stop[k] = g.stop;
+            if (strand) strand[k] = g.strand ? 1 : 0;
+        }
+        ++k;
+    }
+    return k;
 }

@@ -402,7 +402,8 @@ enum BoundsKernel : int32_t {
     kKerFin2L, kKerChop, kKerChopBig, kKerChopStart, kKerSelfTest, kKerPieces, kKerPairdist,
     kKerPairalign, kKerPairalignTb, kKerGroupalign, kKerGroupalignTb, kKerGroupalignMerge,
     kKerRowdist, kKerRowpair, kKerRowpairRc, kKerHithist, kKerRowassign,
-    kKerRowassignDecide, kKerRowassignFinish, kKerEnds, kKerEndsOrigin, kKerEndsRemap
+    kKerRowassignDecide, kKerRowassignFinish, kKerEnds, kKerEndsOrigin, kKerEndsRemap,
+    kKerChopViews
 };
 constexpr int kBoundsRec = 24;     // d_counters[24..27]: kernel id + 1, buffer, index lo / hi
 
@@ -410,6 +411,7 @@ struct Bounds {
 #ifdef DMX_DEBUG_BOUNDS
     int64_t lo, hi;                // valid u32 word indices of d_seq / d_nmask (guards included)
     uint64_t slots, items, reads, counts, linked;   // element counts of the other buffers
+    uint64_t res, views, srcs;     // view runs: results, the view list, the round-1 item sources
     uint32_t* rec;                 // d_counters
     int32_t kid;                   // the launch's kernel (BoundsKernel)
 #endif

@@ -37,7 +37,8 @@ struct EndsArgs {
     Packed pk;
     const uint64_t* offs;
     const uint32_t* lens;
-    const ItemView* items;        // round 1: the views round 0 left; round 0: nullptr (whole reads)
+    const ItemView* items;        // round 1: the views round 0 left; round 0: the view list of a
+                                  // view run, else nullptr (whole reads)
     const uint32_t* n_items_dev;  // device count of items (with items)
     uint32_t n_items;             // host count / upper bound
     const DevEnds* E;
@@ -384,7 +385,14 @@ int launch_ends(Ctx* c, int round, hipStream_t st) {
     A.pk.bd = make_bounds(c, kKerEnds);
     A.offs = c->d_offs;
     A.lens = c->d_lens;
-    if (round == 0) {
+    if (round == 0 && c->views_on) {   // a view run: round 0's items like round 1's
+        A.items = c->d_views;
+        A.n_items_dev = c->d_view_n;
+        A.n_items = (uint32_t)c->n_views;
+#ifdef DMX_DEBUG_BOUNDS
+        A.pk.bd.items = c->view_alloc;
+#endif
+    } else if (round == 0) {
         A.items = nullptr;
         A.n_items_dev = nullptr;
         A.n_items = (uint32_t)c->n_reads;

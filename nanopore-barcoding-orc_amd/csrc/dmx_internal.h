@@ -151,6 +151,16 @@ struct Ctx {
     ItemView* d_items = nullptr;
     size_t item_cap = 0;                 // round-2 items of the current mode and batch
     size_t item_alloc = 0;               // entries allocated in d_items (>= item_cap)
+    // view runs (dmx_set_views / dmx_chop_views): round 0's item list.  A buffer
+    // of its own: finalize0 reads view k while it writes the round-1 list d_items.
+    bool views_on = false;
+    size_t n_views = 0;
+    ItemView* d_views = nullptr;
+    size_t view_alloc = 0;
+    std::vector<uint32_t> h_lens;        // the resident batch's read lengths (dmx_load's copy)
+    uint32_t* d_view_n = nullptr;        // the list's length on the device (round 0's n_items_dev)
+    uint32_t* d_item_src = nullptr;      // round-1 item -> the view it came from (its result)
+    size_t item_src_alloc = 0;
     uint32_t* d_shard = nullptr;      // [kShLists][kShards] per-shard list counters (dmx_device.h)
     uint32_t* d_counters = nullptr;   // [0..1] clusters, [2] items, [3] flags, [4..5] windows, [6+2r..] candidates, [10+r] verified windows, [16+4r..] diag, [24..27] DMX_DEBUG_BOUNDS record
     unsigned long long* d_counts = nullptr;
@@ -179,6 +189,7 @@ struct Ctx {
                               // [15+r] after the piece screen (its filter tasks follow),
                               // [17+2r] / [18+2r] before / after the end-window stage
     bool executed = false;
+    size_t exec_items = 0;       // results of the last dmx_exec (round 0's items)
     ChopState* chop = nullptr;   // dmx_chop_* state, created by dmx_chop_set
     PdState* pd = nullptr;       // dmx_pairdist buffers, created by its first call
     PaState* pa = nullptr;       // dmx_pairalign buffers, created by its first call
@@ -204,6 +215,10 @@ int reset_counts(Ctx* c);      // size d_counts for the current panels/mode and 
 // returned by dmx_last_error(NULL).
 void set_process_error(const std::string& msg);
 std::string process_error();
+// Items of round 0: the views of a view run, else the resident reads.
+inline size_t round0_items(const Ctx* c) { return c->views_on ? c->n_views : c->n_reads; }
+// Room for a view list of n entries in d_views (content not kept) and its device count.
+int views_reserve(Ctx* c, size_t n);
 void chop_invalidate(Ctx* c);   // a new dmx_load makes the last dmx_chop_exec's results stale
 void lg_invalidate(Ctx* c);     // ... and the last dmx_pairhits' outcomes
 // dmx_pairhits (dmx_pairdist.hip) runs the distance form's launches; what becomes of a launch's

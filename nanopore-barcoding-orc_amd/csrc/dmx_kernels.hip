@@ -4146,7 +4146,10 @@ struct FinalArgs {
     const int32_t* origin0;
     int32_t okey0;                       // round 0's keys carry their origin
     unsigned long long* linked_best;     // per read: best pair key
-    Bounds bd;                           // DMX_DEBUG_BOUNDS: extents of the buffers above
+    // view runs: round 0's items, and per round-1 item the view it came from
+    const ItemView* views;
+    uint32_t* item_src;
+    Bounds bd;                          // DMX_DEBUG_BOUNDS: extents of the buffers above
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -4283,6 +4286,10 @@ __device__ __forceinline__ uint32_t pick_winner(const FinalArgs& F, uint32_t i, 
 #define DMX_FINAL_GRID 2048
 #endif
 constexpr uint32_t kFinalGrid = DMX_FINAL_GRID;
+// VIEWS (a view run): item r is view F.views[r] instead of read r as given, the
+// round-1 view is a sub-range of the oriented view (the device twin of view_coords in
+// dmx/loop.py), and F.item_src records which view a queued round-1 item belongs to.
+template <bool VIEWS>
 __global__ __launch_bounds__(256) void finalize0_kernel(FinalArgs F) {
     __shared__ unsigned int s_hist[2 * (kMaxAdapters + 1) + 1];
     __shared__ uint32_t s_nq, s_qbase;
@@ -4295,7 +4302,9 @@ __global__ __launch_bounds__(256) void finalize0_kernel(FinalArgs F) {
         const uint32_t r = base + threadIdx.x;
         ItemView v;
         uint32_t qi = ~0u;             // this read's slot in the block's share of the item list
-        if (r < F.n_reads && DMX_BOUND(F.bd, reads, r, kBufRes)) {
+        if (r < F.n_reads && (VIEWS ? DMX_BOUND(F.bd, res, r, kBufRes) &&
+                                          DMX_BOUND(F.bd, views, r, kBufItem)
+                                    : DMX_BOUND(F.bd, reads, r, kBufRes))) {
             dmx_result out;
             out.bin1 = -1;
             out.bin2 = -1;
@@ -4310,20 +4319,35 @@ __global__ __launch_bounds__(256) void finalize0_kernel(FinalArgs F) {
             out.rc1 = (uint8_t)o;
             if (key != ~0ull) {
                 int a;
-                const uint32_t n = F.lens[r];
+                // round 0's view: (read, strand, start, length); whole-read runs: (r, 0, 0, n)
+                ItemView v0;
+                if (VIEWS) {
+                    v0 = F.views[r];
+                } else {
+                    v0.read = r;
+                    v0.strand = 0;
+                    v0.start = 0;
+                    v0.len = F.lens[r];
+                }
+                const uint32_t n = v0.len;
                 decode_match(key, F.okey, F.origin, ws, n, F.p0, out.m1, a, o);
                 out.bin1 = (int16_t)a;
                 out.rc1 = (uint8_t)o;
                 if (F.mode == DMX_MODE_TWO_ROUND) {
-                    v.read = r;
-                    v.strand = (uint8_t)o;
+                    // the view as round 0's winner saw it (task_view's orientation rule): on
+                    // strand v0.strand ^ o, from position s0 of that strand of the read
+                    uint32_t s0 = v0.start;
+                    if (VIEWS && o && DMX_BOUND(F.bd, reads, v0.read, kBufRead))
+                        s0 = F.lens[v0.read] - v0.start - v0.len;
+                    v.read = v0.read;
+                    v.strand = (uint8_t)(v0.strand ^ (uint8_t)o);
                     v.pad = 0;
                     v.only_adapter = -1;
                     if (F.p0->ad[a].where == kFront) {
-                        v.start = (uint32_t)out.m1.rstop;
+                        v.start = s0 + (uint32_t)out.m1.rstop;
                         v.len = n - (uint32_t)out.m1.rstop;
                     } else {
-                        v.start = 0;
+                        v.start = s0;
                         v.len = (uint32_t)out.m1.rstart;
                     }
                     qi = atomicAdd(&s_nq, 1u);    // LDS; one global atomic per pass below
@@ -4343,6 +4367,8 @@ __global__ __launch_bounds__(256) void finalize0_kernel(FinalArgs F) {
         }
         __syncthreads();
         if (qi != ~0u && DMX_BOUND(F.bd, items, s_qbase + qi, kBufItem)) F.items[s_qbase + qi] = v;
+        if (VIEWS && qi != ~0u && DMX_BOUND(F.bd, srcs, s_qbase + qi, kBufItem))
+            F.item_src[s_qbase + qi] = r;
     }
     // reads taken reverse-complemented: one LDS atomic per wave
     n_rc = wave_sum(n_rc);
@@ -4360,6 +4386,8 @@ __global__ __launch_bounds__(256) void finalize0_kernel(FinalArgs F) {
 }
 
 // Round 1 epilogue (one thread per queued item): m2/bin2 and the (bin1, bin2) histogram.
+// VIEWS: the result belongs to the view the item came from (F.item_src), not to its read.
+template <bool VIEWS>
 __global__ __launch_bounds__(256) void finalize1_kernel(FinalArgs F) {
     extern __shared__ unsigned int s_hist2[];
     const int nbins = (F.A0 + 1) * (F.A1 + 1);
@@ -4371,8 +4399,15 @@ __global__ __launch_bounds__(256) void finalize1_kernel(FinalArgs F) {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_items; i += gridDim.x * 256u) {
         if (!DMX_BOUND(F.bd, items, i, kBufItem)) break;
         const ItemView v = F.items[i];
-        if (!DMX_BOUND(F.bd, reads, v.read, kBufRes)) continue;
-        dmx_result& out = F.res[v.read];
+        uint32_t ri = v.read;
+        if (VIEWS) {
+            if (!DMX_BOUND(F.bd, srcs, i, kBufItem)) continue;
+            ri = F.item_src[i];
+            if (!DMX_BOUND(F.bd, res, ri, kBufRes)) continue;
+        } else if (!DMX_BOUND(F.bd, reads, v.read, kBufRes)) {
+            continue;
+        }
+        dmx_result& out = F.res[ri];
         uint64_t key;
         int o;
         const uint32_t ws = pick_winner(F, i, key, o);
@@ -4434,6 +4469,9 @@ Bounds make_bounds(const Ctx* c, int kid) {
     b.reads = c->n_reads;
     b.counts = c->n_counts;
     b.linked = c->cap_reads;
+    b.res = c->res_cap;
+    b.views = c->view_alloc;
+    b.srcs = c->item_src_alloc;
     b.rec = c->d_counters;
     b.kid = kid;
 #else
@@ -4462,7 +4500,8 @@ int bounds_check(Ctx* c, const char* where) {
         "pairalign_traceback_kernel", "groupalign_kernel", "groupalign_traceback_kernel",
         "groupalign_merge_kernel", "rowdist_kernel", "rowpair_kernel", "rowpair_rc_kernel",
         "lg_hist_kernel", "rowassign_kernel", "rowassign_decide_kernel",
-        "rowassign_finish_kernel", "ends_kernel", "ends_origin_kernel", "ends_remap_kernel"};
+        "rowassign_finish_kernel", "ends_kernel", "ends_origin_kernel", "ends_remap_kernel",
+        "chop_views_kernel"};
     static const char* const kBuf[] = {"?", "seq", "nmask", "winner slots", "items", "results",
                                        "counts", "reads", "linked keys", "candidates", "chop",
                                        "pairdist scratch", "pairalign trace", "pairalign ops",
@@ -4627,7 +4666,15 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
     const bool linked = c->mode == DMX_MODE_LINKED;
     R.per_task_slot = (linked && round == 0) ? 1 : 0;
     R.slot_div = c->orient_slot[round] ? hp.n : 0;
-    if (round == 0) {
+    if (round == 0 && c->views_on) {   // a view run: round 0 over the view list, as round 1
+        R.items = c->d_views;          // runs over finalize0's (never linked: dmx_exec)
+        R.n_items_dev = c->d_view_n;
+        R.n_items = (uint32_t)c->n_views;
+        R.T = hp.n * hp.n_orient;
+#ifdef DMX_DEBUG_BOUNDS
+        R.pk.bd.items = c->view_alloc;
+#endif
+    } else if (round == 0) {
         R.items = nullptr;
         R.n_items_dev = nullptr;
         R.n_items = (uint32_t)c->n_reads;
@@ -4890,14 +4937,23 @@ int launch_finalize(Ctx* c, int round, hipStream_t st) {
         hipEventRecord(c->ev[6 + round], st);
         return hipGetLastError() == hipSuccess ? DMX_OK : DMX_E_HIP;
     }
+    F.views = c->d_views;
+    F.item_src = c->d_item_src;
+    if (c->views_on) F.n_reads = (uint32_t)c->n_views;   // round 0's items: one result each
     if (round == 0) {
-        const uint32_t grid = (uint32_t)std::min<size_t>((c->n_reads + 255) / 256, kFinalGrid);
-        if (grid) hipLaunchKernelGGL(finalize0_kernel, dim3(grid), dim3(256), 0, st, F);
+        const uint32_t grid = (uint32_t)std::min<size_t>((F.n_reads + 255) / 256, kFinalGrid);
+        if (grid && c->views_on)
+            hipLaunchKernelGGL(finalize0_kernel<true>, dim3(grid), dim3(256), 0, st, F);
+        else if (grid)
+            hipLaunchKernelGGL(finalize0_kernel<false>, dim3(grid), dim3(256), 0, st, F);
     } else {
         const uint32_t grid = (uint32_t)std::min<size_t>((c->item_cap + 255) / 256, kFinalGrid);
         const size_t shm = sizeof(unsigned int) * ((size_t)(F.A0 + 1) * (F.A1 + 1) + 1);
         set_kid(F.bd, kKerFin1);
-        if (grid) hipLaunchKernelGGL(finalize1_kernel, dim3(grid), dim3(256), shm, st, F);
+        if (grid && c->views_on)
+            hipLaunchKernelGGL(finalize1_kernel<true>, dim3(grid), dim3(256), shm, st, F);
+        else if (grid)
+            hipLaunchKernelGGL(finalize1_kernel<false>, dim3(grid), dim3(256), shm, st, F);
     }
     DMX_DBG_SYNC("finalize");
     hipEventRecord(c->ev[6 + round], st);

@@ -51,7 +51,9 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_rowhits", "dmx_rowhits_host", "dmx_panel_piece_pairs", "dmx_hithist",
            "dmx_pairhits_cross", "dmx_hitgroups_within", "dmx_hithist_host",
            "dmx_pairhits_cross_host", "dmx_hitgroups_within_host", "dmx_panel_near_shared",
-           "dmx_rowassign", "dmx_rowassign_host", "dmx_set_panel_ex", "dmx_ends_host"]
+           "dmx_rowassign", "dmx_rowassign_host", "dmx_set_panel_ex", "dmx_ends_host",
+           "dmx_set_views", "dmx_clear_views", "dmx_chop_views", "dmx_views_fetch",
+           "dmx_chop_views_host", "dmx_exec_checked"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -146,6 +148,13 @@ def load() -> ctypes.CDLL:
     L.dmx_chop_exec.argtypes = [P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.dmx_chop_fetch.argtypes = [P, P, P, P, c_size, P, c_size]
     L.dmx_chop_stats.argtypes = [P, ctypes.POINTER(ctypes.c_float), c_int]
+    if hasattr(L, "dmx_set_views"):
+        L.dmx_set_views.argtypes = [P, P, P, P, P, c_size]
+        L.dmx_clear_views.argtypes = [P]
+        L.dmx_exec_checked.argtypes = [P]
+        L.dmx_chop_views.argtypes = [P, P, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]
+        L.dmx_views_fetch.argtypes = [P, P, P, P, P, c_size]
+        L.dmx_chop_views_host.argtypes = [P, P, P, ctypes.c_int32, c_size, P, P, P, P, c_size]
     L.dmx_comm_unique_id.argtypes = [P]
     L.dmx_comm_init_rank.argtypes = [P, P, c_int, c_int]
     L.dmx_comm_init_all.argtypes = [ctypes.POINTER(P), c_int]
@@ -333,6 +342,9 @@ class Context:
         self.device = device
         self.panel_sizes = [0, 0]
         self.mode = MODE_SINGLE
+        self._n_loaded = 0
+        self._n_views = None   # views of a view run (set_views / chop_views), None: whole reads
+        self._n_exec = None    # items of the last exec's round 0: what fetch returns
 
     def close(self):
         if getattr(self, "_h", None):
@@ -421,6 +433,8 @@ class Context:
                                     p.offsets.ctypes.data, p.lengths.ctypes.data, p.n_words,
                                     p.n_reads, out.ctypes.data), "dmx_run")
         self._n_loaded = p.n_reads
+        self._n_views = None
+        self._n_exec = p.n_reads
         self._resident = None
         return out
 
@@ -433,6 +447,8 @@ class Context:
                                            p.lengths.ctypes.data, p.n_words, p.n_reads,
                                            out.ctypes.data), "dmx_run_sparse")
         self._n_loaded = p.n_reads
+        self._n_views = None
+        self._n_exec = p.n_reads
         self._resident = None
         return out
 
@@ -441,18 +457,81 @@ class Context:
                                      p.offsets.ctypes.data, p.lengths.ctypes.data, p.n_words,
                                      p.n_reads), "dmx_load")
         self._n_loaded = p.n_reads
+        self._n_views = None
+        self._n_exec = None
         self._lengths = np.array(p.lengths, dtype=np.uint32)   # pairalign sizes its output by them
         self._resident = None   # sorter.assign's tag of the list whose batch is loaded
 
+    def _round0_items(self) -> int:
+        return self._n_views if self._n_views is not None else self._n_loaded
+
     def exec(self):
         self._check(self._L.dmx_exec(self._h), "dmx_exec")
+        self._n_exec = self._round0_items()
+
+    def exec_checked(self):
+        """exec, waited for, run again with larger lists when one overflowed (what run does)."""
+        self._check(self._L.dmx_exec_checked(self._h), "dmx_exec_checked")
+        self._n_exec = self._round0_items()
 
     def sync(self):
         self._check(self._L.dmx_sync(self._h), "dmx_sync")
 
     def fetch(self) -> np.ndarray:
-        out = np.zeros(self._n_loaded, dtype=RESULT_DTYPE)
-        self._check(self._L.dmx_fetch(self._h, out.ctypes.data), "dmx_fetch")
+        """Results of the last exec: as many as its round 0 had items (the reads, or the views
+        of a view run), recorded when it ran: a list set or cleared since does not change it."""
+        n = self._n_exec   # dmx_fetch copies what the last exec computed, whatever was set since
+        if n is None:      # no exec on this batch: the library refuses (DMX_E_STATE)
+            n = self._n_loaded
+        out = np.zeros(n, dtype=RESULT_DTYPE)
+        self._check(self._L.dmx_fetch(self._h, out.ctypes.data if n else None), "dmx_fetch")
+        return out
+
+    # ---- views of the resident reads (include/dmx.h dmx_set_views; DESIGN.md §3.17) -----------
+    def set_views(self, read, start, stop, strand):
+        """Run on views of the resident reads from now on: view k = read[k][start[k]:stop[k]],
+        reverse-complemented when strand[k] (Batch.pack_views' convention)."""
+        arrs = [np.ascontiguousarray(read, dtype=np.uint32),
+                np.ascontiguousarray(start, dtype=np.int32),
+                np.ascontiguousarray(stop, dtype=np.int32),
+                np.ascontiguousarray(strand, dtype=np.uint8)]
+        n = len(arrs[0])
+        if any(len(a) != n for a in arrs):
+            raise ValueError("set_views: read, start, stop and strand differ in length")
+        self._check(self._L.dmx_set_views(self._h, *[a.ctypes.data if n else None for a in arrs],
+                                          n), "dmx_set_views")
+        self._n_views = n
+
+    def clear_views(self):
+        self._check(self._L.dmx_clear_views(self._h), "dmx_clear_views")
+        self._n_views = None
+
+    def chop_views(self, qc_ok=None, min_len: int = 0) -> int:
+        """The view list made on the device from the last chop_exec: the segment of every read
+        with exactly one, qc_ok[r] (None: every read) and at least min_len nt, in read order
+        (pychopper's PASS records).  Returns the number of views."""
+        qc = None
+        if qc_ok is not None:
+            qc = np.ascontiguousarray(np.asarray(qc_ok) != 0, dtype=np.uint8)
+            if len(qc) != self._n_loaded:
+                raise ValueError("chop_views: one qc_ok byte per resident read")
+        nv = ctypes.c_uint64()
+        self._check(self._L.dmx_chop_views(self._h, qc.ctypes.data if qc is not None and len(qc)
+                                           else None, int(min_len), ctypes.byref(nv)),
+                    "dmx_chop_views")
+        self._n_views = int(nv.value)
+        return self._n_views
+
+    def views(self):
+        """The current view list as (read u32, start i32, stop i32, strand u8) arrays."""
+        n = self._n_views or 0
+        out = (np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(n, np.int32),
+               np.zeros(n, np.uint8))
+        got = self._L.dmx_views_fetch(self._h, *[a.ctypes.data if n else None for a in out], n)
+        if got < 0:
+            self._check(int(got), "dmx_views_fetch")
+        if got != n:
+            raise DmxError(f"dmx_views_fetch: {got} views on the device, {n} expected")
         return out
 
     def locate(self, patterns, ascii_blob: np.ndarray, offsets: np.ndarray, lengths: np.ndarray,

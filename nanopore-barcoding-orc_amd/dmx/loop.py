@@ -23,7 +23,10 @@ batch it finds the primer segments on the GPU (bin/pychopper's semantics, dmx/ch
 pychopper's outputs (pychopped/<base>_{pass,rescued,unclass,short}.fastq, <base>_stats.out;
 01_pychopper.sh:45-57) and demultiplexes the PASS records straight from the resident batch —
 packed from the batch as oriented views (dmx_batch_pack_views), never written and read back —
-with the same outputs as bin/pychopper followed by this loop on its PASS file.  `--no-cleanup` also writes the `unknown` and
+with the same outputs as bin/pychopper followed by this loop on its PASS file.  With
+`--device-views` the PASS segments are not packed at all: one context holds the primers and both
+panels, and the demultiplexer runs on views of the resident raw batch (dmx_chop_views; same
+outputs, one device).  `--no-cleanup` also writes the `unknown` and
 SP27_009..012 files the script deletes.  Options mirror the script's variables (e_rate,
 threads, adapter FASTAs); GPUs as in the CLI (DMX_GPUS / DMX_DEVICE, default all visible).
 """
@@ -104,6 +107,10 @@ def build_parser():
     p.add_argument("--reorient", action="store_true",
                    help="INFILE = raw reads: run 01_pychopper.sh's pychopper step first (its "
                         "outputs in --pychopper-dir) and demultiplex its PASS records")
+    p.add_argument("--device-views", action="store_true",
+                   help="with --reorient: keep the PASS segments on the GPU as views of the "
+                        "resident raw batch (dmx_chop_views) instead of packing and uploading "
+                        "them as a second batch; one device, same outputs")
     p.add_argument("--pychopper-dir", default=None, help="default: $(dirname IN)/pychopped")
     p.add_argument("--primers", default=None, help="pychopper -b (M13_seqs_for_pychopper.fa)")
     p.add_argument("--layout", default=None, help="pychopper -c (M13_config_for_pychopper.txt)")
@@ -172,6 +179,8 @@ def run(argv=None) -> int:
         ds = dataset_name(infile)
         demux_in = infile
     why = check_template(args.template)
+    if args.device_views and not args.reorient:
+        why = "--device-views goes with --reorient"
     if why:
         print(f"dmx-demux-loop: error: {why}", file=sys.stderr)
         return 2
@@ -244,7 +253,16 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
     """The fused loop after the reader is open; `ctxs` is filled in place so that the caller can
     close the device contexts when anything here raises (sinks and the reorienter are closed
     below on every path)."""
-    ctxs.extend(lib.open_group(_devices(args)))
+    # --device-views: one context holds the chop primers and both panels (view runs are
+    # single-device: dmx_run_multi stays whole-read only)
+    dev_views = bool(args.reorient and args.device_views)
+    devices = _devices(args)
+    if dev_views and len(devices) > 1:
+        print(f"dmx-demux-loop: --device-views runs on one device: using GPU {devices[0]} of "
+              f"{len(devices)} (view runs are not sharded; drop the flag to use them all)",
+              file=sys.stderr)
+        devices = devices[:1]
+    ctxs.extend(lib.open_group(devices))
     reo = sink1 = sink2 = None
     marks.append(("open", time.perf_counter() - _T_IMPORT))
     for ctx in ctxs:
@@ -265,7 +283,7 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
         st2.append(s)
     try:
         if args.reorient:
-            reo = Reorienter(args, pych_dir, base)
+            reo = Reorienter(args, pych_dir, base, ctxs[0] if dev_views else None)
         t0 = time.perf_counter()
         marks.append(("outputs", t0 - _T_IMPORT))
         print("Round 1: Demultiplexing with SP5 adapters...")
@@ -289,6 +307,8 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
     prof.update(pw_plan=0.0, pw_write1=0.0, pw_write2=0.0, pw_stats=0.0)
     if reo is not None:   # parts of "gpu": pychopper step, view packing
         prof.update(reo=0.0, pack=0.0)
+    if dev_views:         # ... and the view run (exec, fetch, views) in place of pack + run
+        prof.update(views=0.0)
     n2_out = np.zeros(len(n1), np.int64)
     totals = np.zeros((len(n1) + 1, len(n2) + 1), dtype=np.int64)   # device bin counts
     try:
@@ -302,9 +322,26 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
                 if not len(batch):
                     continue
                 tw = time.perf_counter()
-                views = None
+                views = vstrand = None
                 packed, lens = batch.packed, batch.lens
-                if reo is not None:   # the PASS records of 01_pychopper.sh, as views
+                if dev_views:   # the PASS records stay on the device, as views of the raw batch
+                    nv = reo.batch(batch, device_views=True)
+                    tp = time.perf_counter()
+                    prof["reo"] += tp - tw
+                    if not nv:
+                        continue
+                    ctxs[0].exec_checked()
+                    res, cnt = ctxs[0].fetch(), ctxs[0].counts()
+                    views = ctxs[0].views()
+                    prof["views"] += time.perf_counter() - tp   # both rounds, results, the list
+                    lens = (views[2] - views[1]).astype(np.uint32)
+                    # view k as a "read" of the raw packed batch, for the statistics' base
+                    # lookups: its first nt and length; positions count on strand vstrand[k]
+                    raw = batch.packed
+                    packed = lib.Packed(raw.seq2b, raw.nmask,
+                                        raw.offsets[views[0]] + views[1].astype(np.uint64), lens)
+                    vstrand = views[3]
+                elif reo is not None:   # the PASS records of 01_pychopper.sh, as views
                     views = reo.batch(batch)
                     tp = time.perf_counter()
                     prof["reo"] += tp - tw
@@ -314,7 +351,8 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
                     lens = packed.lengths
                     if not len(lens):
                         continue
-                res, cnt = lib.run_batch(ctxs, packed)
+                if not dev_views:
+                    res, cnt = lib.run_batch(ctxs, packed)
                 totals += lib.bin_totals(cnt, len(n1), len(n2))
                 prof["gpu"] += time.perf_counter() - tw
                 tw = time.perf_counter()
@@ -357,7 +395,7 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
                 tr = time.perf_counter()
                 prof["pw_write2"] += tr - tq
                 _round_stats(st1, st2, res, lens, m1, m2, b1, b2, s1, s2w, e2w,
-                             bp2_out, n2_out, packed)
+                             bp2_out, n2_out, packed, vstrand)
                 tq = time.perf_counter()
                 prof["pw_stats"] += tq - tr
                 prof["plan_write"] += tq - tw
@@ -415,7 +453,9 @@ class Reorienter:
     outputs written, and the PASS records (one segment, QC pass, >= -z nt) returned as views
     (read, start, stop, strand) for the demultiplexer."""
 
-    def __init__(self, args, pych_dir: str, base: str):
+    def __init__(self, args, pych_dir: str, base: str, ctx=None):
+        """ctx (--device-views): the demultiplexer's own context, which then also holds the chop
+        primers and keeps every raw batch resident; None: a context of this step's own."""
         from . import chop
         self.chop = chop
         self.args = args
@@ -425,7 +465,8 @@ class Reorienter:
             rules = chop.parse_config(fh.read(), [p[0] for p in primers])
         dev = args.device if args.device is not None else int(os.environ.get("DMX_DEVICE", "0")
                                                                or 0)
-        self.ctx = lib.Context(dev)
+        self.own_ctx = ctx is None
+        self.ctx = lib.Context(dev) if ctx is None else ctx
         self.ch = chop.Chopper(self.ctx, primers, rules, not args.no_keep_primers)
         # 01_pychopper.sh:47-57: -w rescued, -u unclass, -l short, -S stats, PASS to stdout
         self.paths = [os.path.join(pych_dir, f"{base}_{k}.fastq")
@@ -443,7 +484,10 @@ class Reorienter:
         self.prof[key] += now - t
         return now
 
-    def batch(self, b):
+    def batch(self, b, device_views: bool = False):
+        """The batch's PASS records as (read, start, stop, strand) arrays; device_views: as the
+        context's view list (dmx_chop_views: made on the device from the segments, none of them
+        packed or uploaded again), and their number is returned."""
         chop, a = self.chop, self.args
         if self.sink is None:
             self.sink = nio.Sink(self.paths, b.fasta, 1, threads=a.threads)
@@ -463,6 +507,8 @@ class Reorienter:
         self.sink.write_rows(b, *chop.plan_rows(nseg, segs, b.lens, qc_ok, a.min_len, self.outs))
         self.stats.add(nseg, segs, qc_ok, a.min_len)
         self._tick("rows", t)
+        if device_views:
+            return self.ctx.chop_views(qc_ok, a.min_len)
         sread = segs["read"].astype(np.int64)
         sstart = segs["start"].astype(np.int64)
         sstop = segs["stop"].astype(np.int64)
@@ -482,11 +528,14 @@ class Reorienter:
               f"{time.perf_counter() - self.t0:.3f} s, cutoff {self.cutoff}: {s.n_found} with "
               f"primers, {s.n_rescue} rescued, {s.n_unclass} unclassified, {s.n_qcfail} QC fail",
               file=sys.stderr)
-        self.ctx.close()
+        if self.own_ctx:
+            self.ctx.close()
 
 
 def _round_stats(st1, st2, res, lens, m1, m2, b1, b2, s1, s2w, e2w, bp2_out, n2_out,
-                 packed=None):
+                 packed=None, vstrand=None):
+    """vstrand (--device-views): `packed` describes view k by its first nt and length on the raw
+    read as given, and the view itself is on strand vstrand[k] of that range."""
     lens = lens.astype(np.int64)
     n = len(res)
     rc1 = res["rc1"] == 1
@@ -508,7 +557,10 @@ def _round_stats(st1, st2, res, lens, m1, m2, b1, b2, s1, s2w, e2w, bp2_out, n2_
         p = res["m2_rstart"].astype(np.int64)[hit_all] - 1
         r1 = res["rc1"].astype(np.int64)[hit_all]
         two = res["rc2"].astype(np.int64)[hit_all] == 1
-        codes = report.view_codes(packed, hit_all, np.where(two, 1 - r1, r1),
+        strand = np.where(two, 1 - r1, r1)
+        if vstrand is not None:   # orientations compose by XOR (view_coords)
+            strand = strand ^ vstrand.astype(np.int64)[hit_all]
+        codes = report.view_codes(packed, hit_all, strand,
                                   np.where(two, p, np.where(p >= 0, s1[hit_all] + p, -1)))
         adj = np.full(n, 4, np.int64)
         adj[hit_all] = codes
