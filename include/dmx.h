@@ -23,8 +23,8 @@ extern "C" {
 
 /* 4 also covers the calls added since without a bump, all additive (no existing signature or
  * behaviour changed): the amplicon-sorting entry points below, and dmx_set_panel_ex,
- * dmx_ends_host, DMX_ANCHORED and DMX_NONINTERNAL.  A caller that needs one of them checks for
- * the symbol. */
+ * dmx_ends_host, DMX_ANCHORED, DMX_NONINTERNAL and the operand-table calls.  A caller that needs
+ * one of them checks for the symbol. */
 #define DMX_ABI_VERSION 4
 
 /* Panel flags (dmx_set_panel.flags). */
@@ -397,6 +397,74 @@ int dmx_views_fetch(dmx_ctx* ctx, uint32_t* read, int32_t* start, int32_t* stop,
 int dmx_chop_views_host(const uint32_t* n_seg, const dmx_chop_seg* segs, const uint8_t* qc_ok,
                         int32_t min_len, size_t n_reads, uint32_t* read, int32_t* start,
                         int32_t* stop, uint8_t* strand, size_t cap);
+
+/* ---- Operand tables: the sorting calls on sub-ranges of the resident reads ----
+ * The demultiplexer leaves every base of every well in HBM, as a sub-range of a resident read in
+ * a known orientation.  With an operand table set, the amplicon-sorting calls below run on such
+ * sub-ranges without a second pack and dmx_load.  Operand k is read[k][start[k]:stop[k]] of the
+ * batch made resident by dmx_load, on the read as given, taken reverse-complemented when
+ * strand[k] == 1 (the conventions of dmx_set_views).
+ * Contract with a table set: every index that dmx_pairdist, dmx_pairhits (and dmx_pairhits_fetch,
+ * dmx_hitgroups, dmx_hithist, dmx_pairhits_cross, dmx_hitgroups_within on its outcomes),
+ * dmx_groupalign, dmx_groupalign_strands, dmx_rowdist and dmx_rowassign document as "a read of
+ * the resident batch" names an operand, every per-read array (best, tie, label, cap2, bin_off,
+ * labels, n_nodes >= n_reads and the like) has one entry per operand, and the results are those
+ * the same call returns on a batch whose reads are the operands' sequences, packed by dmx_pack.
+ * dmx_pairhits' rev bit is the caller's view: 1 = the retry against the reverse-complemented
+ * target hit.  dmx_pairalign with a table set is DMX_E_UNSUPPORTED; dmx_rowpairdist and
+ * dmx_rowhits read no batch and are unchanged.
+ * Everything is checked on the host before anything is uploaded, and a refused call leaves the
+ * context and its current table as they were: no resident batch is DMX_E_STATE; a read index
+ * outside the batch, start < 0, start > stop, stop past the read's end or strand > 1 is
+ * DMX_E_INVALID naming the operand; more than 2^31 operands is DMX_E_UNSUPPORTED.  (A device
+ * failure, DMX_E_HIP, while a table is being set or built leaves no table; one in a call that
+ * only reads the table, dmx_operands_fetch or a sorting call, leaves it as it was.)  Operands may repeat, overlap, outnumber the
+ * reads and be empty; an empty operand is refused only by a call that names it, as a 0-nt read is.
+ * dmx_load, dmx_run, dmx_run_sparse, dmx_run_multi and dmx_clear_operands drop the table.  Setting,
+ * replacing or dropping a table drops the outcomes of dmx_pairhits, which name its operands.  The
+ * table is independent of the demultiplexer's view list (dmx_set_views); both may be set. */
+int dmx_set_operands(dmx_ctx* ctx, const uint32_t* read, const int32_t* start, const int32_t* stop,
+                     const uint8_t* strand, size_t n_operands);
+/* Back to whole reads (no-op without a table). */
+int dmx_clear_operands(dmx_ctx* ctx);
+/* The current table in dmx_set_operands' convention, first `cap` operands written (any pointer
+ * may be NULL); returns its length (0 without a table), negative on error. */
+int dmx_operands_fetch(dmx_ctx* ctx, uint32_t* read, int32_t* start, int32_t* stop,
+                       uint8_t* strand, size_t cap);
+/* Test-only (host, no GPU; not for callers, who get the same answers from dmx_set_operands):
+ * dmx_set_operands' argument checks against the read lengths of a batch, so that the CPU suite
+ * reaches them.  DMX_OK, or the code dmx_set_operands returns, with the message in dmx_last_error(NULL). */
+int dmx_operands_check_host(const uint32_t* lens, size_t n_reads, const uint32_t* read,
+                            const int32_t* start, const int32_t* stop, const uint8_t* strand,
+                            size_t n_operands);
+/* The table of a demultiplexer run, made on the device.  After a dmx_exec / dmx_exec_checked in
+ * DMX_MODE_SINGLE or DMX_MODE_TWO_ROUND on the current batch and view list (DMX_E_STATE
+ * otherwise; DMX_MODE_LINKED is DMX_E_UNSUPPORTED): one operand per item of round 0 (a read, or
+ * view k of a view run) whose bin is kept, the bin index being dmx_counts' index.  An item is kept
+ * when keep == NULL and it is matched in every round, or when keep[index] != 0; n_keep must equal
+ * the number of bins (dmx_counts' length less its two trailing entries).  The operand is the
+ * final trimmed, oriented record the fused loop writes for the item: rc1, m1's trim, rc2 and m2's
+ * trim composed ([rstop:] for a 5' adapter, [:rstart] for a 3' adapter; a round without a match
+ * keeps its whole input in the orientation it was taken), on the read as given.  Items whose
+ * final length is below min_len (>= 1) are dropped.  Operands are ordered by bin and, inside a
+ * bin, by item.  bin_first[b] is the first operand of bin b; it has one more entry than there are
+ * bins (n_first is checked), the last being the table's length, which *n_operands (optional)
+ * receives too.  Only bin_first leaves the device; dmx_operands_fetch brings the table down. */
+int dmx_result_operands(dmx_ctx* ctx, const uint8_t* keep, size_t n_keep, int32_t min_len,
+                        uint64_t* bin_first, size_t n_first, uint64_t* n_operands);
+/* Host only (no GPU; tests): the same table in plain sequential C++ from dmx_fetch's results
+ * (n_items of them), round 0's item list in dmx_set_views' convention (v_read == NULL: item k is
+ * read k), the batch's read lengths, the mode and both panels' adapter types (wheres as
+ * dmx_set_panel_ex takes them; wheres1 / n1 are not read in DMX_MODE_SINGLE).  First `cap`
+ * operands written (any of read, start, stop, strand may be NULL).  Errors:
+ * dmx_last_error(NULL). */
+int dmx_result_operands_host(const dmx_result* res, size_t n_items, const uint32_t* v_read,
+                             const int32_t* v_start, const int32_t* v_stop,
+                             const uint8_t* v_strand, const uint32_t* lens, size_t n_reads,
+                             int mode, const int* wheres0, int n0, const int* wheres1, int n1,
+                             const uint8_t* keep, size_t n_keep, int32_t min_len, uint32_t* read,
+                             int32_t* start, int32_t* stop, uint8_t* strand, size_t cap,
+                             uint64_t* bin_first, size_t n_first, uint64_t* n_operands);
 
 /* ---- Pairwise read distance: the amplicon-sorting stage's similarity pass --------------------
  * Replaces: the edlib.align(A1, A2, task='distance', mode=...) calls of

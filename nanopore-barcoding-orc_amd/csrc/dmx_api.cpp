@@ -300,6 +300,7 @@ int reset_counts(Ctx* c) {
 
 int views_reserve(Ctx* c, size_t n) {
     CK(hipSetDevice(c->device));
+    ++c->view_gen;   // the list is about to change: an earlier exec's items are no longer d_views
     if (!c->d_view_n) CK(hipMalloc((void**)&c->d_view_n, sizeof(uint32_t)));
     if (c->view_alloc < n || !c->d_views) {
         // the last exec may still read the old list
@@ -1120,6 +1121,8 @@ int load_impl(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& mask, const uint
     c->executed = false;
     c->chunked = false;
     c->views_on = false;   // whole-read runs again (dmx_set_views / dmx_chop_views set a list)
+    ++c->view_gen;
+    ops_drop(c);           // ... and the sorting calls index reads again
     c->h_lens.assign(lens, lens + n_reads);   // view lists are checked and rendered against it
     chop_invalidate(c);
     lg_invalidate(c);
@@ -1310,6 +1313,9 @@ int dmx_exec(dmx_ctx* c) {
     }
     c->executed = true;
     c->exec_items = round0_items(c);
+    c->exec_views = c->views_on;
+    c->exec_view_gen = c->view_gen;
+    c->exec_panel_gen = c->panel_gen;
     return bounds_check(c, "dmx_exec");   // DMX_DEBUG_BOUNDS builds only (else DMX_OK)
 }
 
@@ -1388,6 +1394,7 @@ int dmx_set_views(dmx_ctx* c, const uint32_t* read, const int32_t* start, const 
 int dmx_clear_views(dmx_ctx* c) {
     if (!c) return DMX_E_INVALID;
     c->views_on = false;
+    ++c->view_gen;
     return DMX_OK;
 }
 
@@ -1712,6 +1719,8 @@ int run_chunked(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& nmask,
     }
     c->n_reads = maxn;
     c->views_on = false;
+    ++c->view_gen;
+    ops_drop(c);
     c->h_lens.clear();
     chop_invalidate(c);
     lg_invalidate(c);

@@ -287,6 +287,41 @@ struct ItemView {
     int16_t only_adapter;   // linked mode: the pair index, else -1
 };
 
+// What a round leaves of the view it ran on.  `v0` is the view the round was given, `read_len` the
+// length of its read, `o` the orientation the winner took (1 = the view reverse-complemented),
+// `n` the view's length and (rstart, rstop) the match on the oriented view.  A 5' adapter keeps
+// [rstop:], a 3' adapter [:rstart].  The one statement of the trim composition on the device:
+// finalize0_kernel queues its result as the round-1 item, and the operand builder
+// (dmx_operands.hip) applies it once per round to find the record the loop writes.
+__device__ __forceinline__ ItemView trimmed_view(const ItemView& v0, uint32_t read_len, int o,
+                                                 bool front, uint32_t n, int32_t rstart,
+                                                 int32_t rstop) {
+    // the view as the winner saw it (task_view's orientation rule): on strand v0.strand ^ o, from
+    // position s0 of that strand of the read
+    const uint32_t s0 = o ? read_len - v0.start - v0.len : v0.start;
+    ItemView v;
+    v.read = v0.read;
+    v.strand = (uint8_t)(v0.strand ^ (uint8_t)o);
+    v.pad = 0;
+    v.only_adapter = -1;
+    if (front) {
+        v.start = s0 + (uint32_t)rstop;
+        v.len = n - (uint32_t)rstop;
+    } else {
+        v.start = s0;
+        v.len = (uint32_t)rstart;
+    }
+    return v;
+}
+
+// One operand of the amplicon-sorting calls (dmx_set_operands):
+// read[start:stop] on the read as given, taken reverse-complemented when strand == 1.
+struct OperandRec {
+    uint32_t read;
+    int32_t start, stop;
+    uint32_t strand;
+};
+
 struct Cluster {      // candidate columns [j1, j2] of one task (item, orientation, adapter)
     uint32_t item;
     uint16_t sub;     // o * A + a (or a in linked mode)
@@ -403,7 +438,7 @@ enum BoundsKernel : int32_t {
     kKerPairalign, kKerPairalignTb, kKerGroupalign, kKerGroupalignTb, kKerGroupalignMerge,
     kKerRowdist, kKerRowpair, kKerRowpairRc, kKerHithist, kKerRowassign,
     kKerRowassignDecide, kKerRowassignFinish, kKerEnds, kKerEndsOrigin, kKerEndsRemap,
-    kKerChopViews
+    kKerChopViews, kKerOperands
 };
 constexpr int kBoundsRec = 24;     // d_counters[24..27]: kernel id + 1, buffer, index lo / hi
 

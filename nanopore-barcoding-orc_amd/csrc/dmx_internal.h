@@ -161,6 +161,26 @@ struct Ctx {
     uint32_t* d_view_n = nullptr;        // the list's length on the device (round 0's n_items_dev)
     uint32_t* d_item_src = nullptr;      // round-1 item -> the view it came from (its result)
     size_t item_src_alloc = 0;
+    // operand table (dmx_set_operands / dmx_result_operands): with a table set the
+    // amplicon-sorting calls index operands, not reads.  d_op_off / d_op_len stand in for d_offs /
+    // d_lens in their launches (the sub-range as it lies in memory); d_op holds the table itself
+    // (OperandRec) for dmx_operands_fetch.  The table lives on the device only.
+    bool ops_on = false;
+    size_t n_ops = 0;
+    DevBuf<OperandRec> d_op;
+    DevBuf<uint64_t> d_op_off;
+    DevBuf<uint32_t> d_op_len;
+    DevBuf<uint8_t> d_op_strand;
+    // the host's mirror of d_op_len / d_op_strand for the calls' argument checks and the strand
+    // folding: filled by dmx_set_operands, or on first need after dmx_result_operands (one copy per
+    // table, not per call); h_op_any: some operand is on strand 1
+    bool h_op_valid = false, h_op_any = false;
+    std::vector<uint32_t> h_op_len;
+    std::vector<uint8_t> h_op_strand;
+    // dmx_result_operands' scratch: [block][bin] places, bin_first, the caller's keep flags
+    DevBuf<uint32_t> d_op_hist;
+    DevBuf<uint64_t> d_op_first;
+    DevBuf<uint8_t> d_op_keep;
     uint32_t* d_shard = nullptr;      // [kShLists][kShards] per-shard list counters (dmx_device.h)
     uint32_t* d_counters = nullptr;   // [0..1] clusters, [2] items, [3] flags, [4..5] windows, [6+2r..] candidates, [10+r] verified windows, [16+4r..] diag, [24..27] DMX_DEBUG_BOUNDS record
     unsigned long long* d_counts = nullptr;
@@ -190,6 +210,10 @@ struct Ctx {
                               // [17+2r] / [18+2r] before / after the end-window stage
     bool executed = false;
     size_t exec_items = 0;       // results of the last dmx_exec (round 0's items)
+    bool exec_views = false;     // ... which were the views of d_views as of exec_view_gen
+    uint64_t view_gen = 0;       // bumped whenever the view list changes or goes
+    uint64_t exec_view_gen = 0;
+    uint64_t exec_panel_gen = 0; // panel_gen at that exec: its results were decoded by those panels
     ChopState* chop = nullptr;   // dmx_chop_* state, created by dmx_chop_set
     PdState* pd = nullptr;       // dmx_pairdist buffers, created by its first call
     PaState* pa = nullptr;       // dmx_pairalign buffers, created by its first call
@@ -221,6 +245,11 @@ inline size_t round0_items(const Ctx* c) { return c->views_on ? c->n_views : c->
 int views_reserve(Ctx* c, size_t n);
 void chop_invalidate(Ctx* c);   // a new dmx_load makes the last dmx_chop_exec's results stale
 void lg_invalidate(Ctx* c);     // ... and the last dmx_pairhits' outcomes
+// No operand table: the sorting calls index reads again, and the outcomes of dmx_pairhits, which
+// were made under the table, go with it (dmx_operands.hip).
+void ops_drop(Ctx* c);
+// The host mirror of the table's lengths and strands (h_op_*), copied down once per table.
+int ops_mirror(Ctx* c, const char* who);
 // dmx_pairhits (dmx_pairdist.hip) runs the distance form's launches; what becomes of a launch's
 // distances stays on the device and is dmx_groups.hip's:
 // lg_hits_begin uploads the call's pair list and caps and clears the outcomes;

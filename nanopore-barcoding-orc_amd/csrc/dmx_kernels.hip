@@ -4334,22 +4334,12 @@ __global__ __launch_bounds__(256) void finalize0_kernel(FinalArgs F) {
                 out.bin1 = (int16_t)a;
                 out.rc1 = (uint8_t)o;
                 if (F.mode == DMX_MODE_TWO_ROUND) {
-                    // the view as round 0's winner saw it (task_view's orientation rule): on
-                    // strand v0.strand ^ o, from position s0 of that strand of the read
-                    uint32_t s0 = v0.start;
+                    // a whole read's view covers it: its length is the read's, no second load
+                    uint32_t rl = v0.start + v0.len;
                     if (VIEWS && o && DMX_BOUND(F.bd, reads, v0.read, kBufRead))
-                        s0 = F.lens[v0.read] - v0.start - v0.len;
-                    v.read = v0.read;
-                    v.strand = (uint8_t)(v0.strand ^ (uint8_t)o);
-                    v.pad = 0;
-                    v.only_adapter = -1;
-                    if (F.p0->ad[a].where == kFront) {
-                        v.start = s0 + (uint32_t)out.m1.rstop;
-                        v.len = n - (uint32_t)out.m1.rstop;
-                    } else {
-                        v.start = s0;
-                        v.len = (uint32_t)out.m1.rstart;
-                    }
+                        rl = F.lens[v0.read];
+                    v = trimmed_view(v0, rl, o, F.p0->ad[a].where == kFront, n, out.m1.rstart,
+                                     out.m1.rstop);
                     qi = atomicAdd(&s_nq, 1u);    // LDS; one global atomic per pass below
                 } else {
                     atomicAdd(&s_hist[a + 1], 1u);
@@ -4501,7 +4491,7 @@ int bounds_check(Ctx* c, const char* where) {
         "groupalign_merge_kernel", "rowdist_kernel", "rowpair_kernel", "rowpair_rc_kernel",
         "lg_hist_kernel", "rowassign_kernel", "rowassign_decide_kernel",
         "rowassign_finish_kernel", "ends_kernel", "ends_origin_kernel", "ends_remap_kernel",
-        "chop_views_kernel"};
+        "chop_views_kernel", "operands kernels"};
     static const char* const kBuf[] = {"?", "seq", "nmask", "winner slots", "items", "results",
                                        "counts", "reads", "linked keys", "candidates", "chop",
                                        "pairdist scratch", "pairalign trace", "pairalign ops",

@@ -224,16 +224,18 @@ struct GaState : PdBufs<GaPair> {
     }
 };
 
-struct RdState : PdBufs<RdPair> {   // DESIGN.md §8h
-    DevBuf<uint8_t> mask;        // the rows of the last call
-    float ms = 0.f;
-};
-
 // A row of dmx_rowpairdist on the device: where it starts in the mask array and its length.
 struct RrRow {
     uint64_t off;
     uint32_t n, pad;
 };
+struct RdState : PdBufs<RdPair> {   // DESIGN.md §8h
+    DevBuf<uint8_t> mask;        // the rows of the last call (then their reverse complements, when
+                                 // a query is an operand on strand 1)
+    DevBuf<RrRow> rows;          // the uploaded rows (rowpair_rc_kernel)
+    float ms = 0.f;
+};
+
 struct RrState : PdBufs<RrPair> {   // DESIGN.md §8j; PdBufs::out holds the whole list's distances
     DevBuf<uint8_t> mask;        // the rows of the last call, then their reverse complements
     DevBuf<RrRow> rows;          // the uploaded rows (rowpair_rc_kernel)
@@ -1054,14 +1056,44 @@ void pd_parallel(size_t n_pairs, int n_threads, F work) {
 }
 
 // The lengths of the resident batch, for the validation on the host before anything is
-// launched (a copy, no kernel).
+// launched (a copy, no kernel).  With an operand table the lengths are the
+// operands', one entry each: every index of the call names an operand.
 int pd_fetch_lens(Ctx* c, const char* who, size_t n_pairs, std::vector<uint32_t>& lens) {
+    if (c->d_seq && c->ops_on) {   // the table's host mirror: one copy per table, not per call
+        if (const int rc = ops_mirror(c, who)) return rc;
+        lens = c->h_op_len;
+        return DMX_OK;
+    }
     lens.resize(c->d_seq ? c->n_reads : 0);
     if (!lens.empty() && n_pairs) {
         PD_CK(who, hipSetDevice(c->device));
         PD_CK(who, hipMemcpy(lens.data(), c->d_lens, lens.size() * 4, hipMemcpyDeviceToHost));
     }
     return DMX_OK;
+}
+
+// The operands' strands, one byte each; left empty without a table or when every operand is on
+// strand 0 (the calls then run as they do on reads).  A strand is never seen by a kernel as such:
+// the host folds it into the pair's DMX_PD_RC (read against read, a group's member) or into the
+// copy of the row a pair is compared with (read against row).
+int pd_fetch_strands(Ctx* c, const char* who, std::vector<uint8_t>& strands) {
+    strands.clear();
+    if (!c->d_seq || !c->ops_on || !c->n_ops) return DMX_OK;
+    if (const int rc = ops_mirror(c, who)) return rc;
+    if (c->h_op_any) strands = c->h_op_strand;
+    return DMX_OK;
+}
+
+// Where the forms find their reads: the batch's offsets and lengths, or the operand table's.
+inline const uint64_t* pd_offs(const Ctx* c) { return c->ops_on ? c->d_op_off.p : c->d_offs; }
+inline const uint32_t* pd_lens(const Ctx* c) { return c->ops_on ? c->d_op_len.p : c->d_lens; }
+// make_bounds for a kernel that indexes them (DMX_DEBUG_BOUNDS builds).
+inline Bounds pd_bounds(const Ctx* c, int kid) {
+    Bounds b = make_bounds(c, kid);
+#ifdef DMX_DEBUG_BOUNDS
+    if (c->ops_on) b.reads = c->n_ops;
+#endif
+    return b;
 }
 
 // The context's state of one form, made by the form's first call.
@@ -1164,9 +1196,9 @@ int pd_stage(Ctx* c, const char* who, PdBufs<Pair>& b, const PdPlan<Pair>& pl, s
     PD_CK(who, bounds_reset(c, st));
     A.pk.seq = c->d_seq;
     A.pk.nmask = c->d_nmask;
-    A.pk.bd = make_bounds(c, kid);
-    A.offs = c->d_offs;
-    A.lens = c->d_lens;
+    A.pk.bd = pd_bounds(c, kid);
+    A.offs = pd_offs(c);
+    A.lens = pd_lens(c);
     A.pairs = b.pairs.p;
     A.waves = b.waves.p;
     A.n_waves = (uint32_t)nw;
@@ -1232,6 +1264,15 @@ extern "C" int dmx_pairdist(dmx_ctx* c, int mode, const uint32_t* q, const uint3
                                    &c->err))
         return rc;
     if (!n_pairs) return DMX_OK;
+    // operands: the pair's flag with both strands folded in; the query is never turned
+    std::vector<uint8_t> strands, eff;
+    if (const int rc = pd_fetch_strands(c, who, strands)) return rc;
+    if (!strands.empty()) {
+        eff.resize(n_pairs);
+        for (size_t i = 0; i < n_pairs; ++i)
+            eff[i] = (uint8_t)(((flags ? flags[i] : 0u) ^ strands[q[i]] ^ strands[t[i]]) & DMX_PD_RC);
+        flags = eff.data();
+    }
     if (const int rc = pd_state(c, who, c->pd)) return rc;
     PdState* s = c->pd;
     hipStream_t st = c->stream;
@@ -1278,7 +1319,9 @@ extern "C" int dmx_pairhits(dmx_ctx* c, const uint32_t* q, const uint32_t* t,
     const char* const who = "dmx_pairhits";
     if (!c) return DMX_E_INVALID;
     lg_invalidate(c);
-    const size_t n_reads = c->d_seq ? c->n_reads : 0;
+    // with an operand table the per-read arrays of this call and of those that read its outcomes
+    // have one entry per operand
+    const size_t n_reads = !c->d_seq ? 0 : c->ops_on ? c->n_ops : c->n_reads;
     if (!n_hits || (n_reads && !best) || (n_pairs && (!q || !t || !cap_hit || !cap_half))) {
         c->err = "dmx_pairhits: null pair list, caps or output";
         return DMX_E_INVALID;
@@ -1302,6 +1345,14 @@ extern "C" int dmx_pairhits(dmx_ctx* c, const uint32_t* q, const uint32_t* t,
         fcap[i] = (uint32_t)std::max(std::max(cap_hit[i], cap_half[i]), 0);
     }
     PD_CK(who, hipSetDevice(c->device));
+    // operands: the forward comparison's flag is the two strands', the retry's that flag toggled
+    std::vector<uint8_t> strands, fwd;
+    if (n_pairs)
+        if (const int rc = pd_fetch_strands(c, who, strands)) return rc;
+    if (!strands.empty()) {
+        fwd.resize(n_pairs);
+        for (size_t i = 0; i < n_pairs; ++i) fwd[i] = (uint8_t)((strands[q[i]] ^ strands[t[i]]) & 1u);
+    }
     if (const int rc = lg_hits_begin(c, who, q, t, cap_hit, cap_half, n_pairs, n_reads)) return rc;
     float total_ms = 0.f;
     if (n_pairs) {
@@ -1338,7 +1389,8 @@ extern "C" int dmx_pairhits(dmx_ctx* c, const uint32_t* q, const uint32_t* t,
             return DMX_OK;
         };
         for (size_t lo = 0, hi = 0; lo < n_pairs; lo = hi) {
-            if (const int rc = launch(q, t, nullptr, fcap.data(), n_pairs, lo, nullptr, 0, &hi))
+            if (const int rc = launch(q, t, fwd.empty() ? nullptr : fwd.data(), fcap.data(), n_pairs,
+                                      lo, nullptr, 0, &hi))
                 return rc;
             for (size_t w = 0; w < need.size(); ++w)
                 for (uint32_t bits = need[w]; bits; bits &= bits - 1u) {
@@ -1348,8 +1400,9 @@ extern "C" int dmx_pairhits(dmx_ctx* c, const uint32_t* q, const uint32_t* t,
         }
         const size_t n2 = retry.size();
         std::vector<uint32_t> q2(n2), t2(n2), cap2(n2);
-        const std::vector<uint8_t> rc2(n2, DMX_PD_RC);
+        std::vector<uint8_t> rc2(n2, DMX_PD_RC);
         for (size_t k = 0; k < n2; ++k) {
+            if (!fwd.empty()) rc2[k] = (uint8_t)(DMX_PD_RC ^ fwd[retry[k]]);
             q2[k] = q[retry[k]];
             t2[k] = t[retry[k]];
             cap2[k] = (uint32_t)cap_hit[retry[k]];   // >= 0 where a retry is asked for
@@ -1422,6 +1475,11 @@ extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, c
     if (!op_off || (n_pairs && (!q || !t || !dist || !ops))) {
         c->err = "dmx_pairalign: null pair list or output";
         return DMX_E_INVALID;
+    }
+    if (c->ops_on) {
+        c->err = "dmx_pairalign: not supported with an operand table (dmx_clear_operands first; "
+                 "dmx_groupalign_strands aligns operands)";
+        return DMX_E_UNSUPPORTED;
     }
     if (c->pa) {
         c->pa->ms[0] = c->pa->ms[1] = 0.f;
@@ -1772,6 +1830,19 @@ static int ga_device(const char* who, dmx_ctx* c, size_t n_groups, const uint8_t
     col_off[0] = 0;
     if (ops) op_off[0] = 0;
     if (!n_groups) return DMX_OK;
+    // operands: a member's flag with its strand folded in (a launch with a turned member runs
+    // the strands form, dmx_groupalign's included)
+    std::vector<uint8_t> strands, mflags;
+    if (some)
+        if (const int rc = pd_fetch_strands(c, who, strands)) return rc;
+    if (!strands.empty()) {
+        const uint64_t m0 = member_off[0], m1 = member_off[n_groups];
+        mflags.resize(m1);   // indexed as member_flags is: by the member's place in `members`
+        for (uint64_t x = m0; x < m1; ++x)
+            mflags[x] = (uint8_t)(((member_flags ? member_flags[x] : 0u) ^ strands[members[x]]) &
+                                  DMX_PD_RC);
+        member_flags = mflags.data();
+    }
     if (const int rc = pd_state(c, who, c->ga)) return rc;
     GaState* s = c->ga;
     if (!s->ev_merge) PD_CK(who, hipEventCreate(&s->ev_merge));
@@ -2079,12 +2150,38 @@ extern "C" int dmx_rowdist(dmx_ctx* c, size_t n_rows, const uint8_t* masks, cons
             total += ((uint64_t)rn[i] + 15u) & ~(uint64_t)15u;
         }
     std::vector<uint8_t> rows(total, 0);
+    std::vector<RrRow> used;
     for (size_t g = 0; g < n_rows; ++g)
-        if (goff[g] != ~(uint64_t)0)
+        if (goff[g] != ~(uint64_t)0) {
             std::memcpy(rows.data() + goff[g], masks + row_off[g], row_off[g + 1] - row_off[g]);
-    PD_CK(who, s->mask.reserve(total));
+            used.push_back(RrRow{goff[g], (uint32_t)(row_off[g + 1] - row_off[g]), 0u});
+        }
+    // operands: a query on strand 1 against a row is the sub-range as it lies in memory against
+    // the row's reverse complement, written `total` columns behind the rows as dmx_rowassign's are
+    std::vector<uint8_t> strands;
+    if (const int rc = pd_fetch_strands(c, who, strands)) return rc;
+    bool turned = false;
+    for (size_t i = 0; i < n_pairs && !strands.empty() && !turned; ++i) turned = strands[q[i]] != 0;
+    PD_CK(who, s->mask.reserve(turned ? 2 * total : total));
     PD_CK(who, hipMemcpyAsync(s->mask.p, rows.data(), total, hipMemcpyHostToDevice, st));
-    PD_CK(who, hipStreamSynchronize(st));   // `rows` is pageable
+    if (turned) {
+        PD_CK(who, s->rows.reserve(used.size()));
+        PD_CK(who, hipMemcpyAsync(s->rows.p, used.data(), used.size() * sizeof(RrRow),
+                                  hipMemcpyHostToDevice, st));
+        PD_CK(who, bounds_reset(c, st));
+        RrRcArgs R;
+        R.bd = make_bounds(c, kKerRowpairRc);
+        R.rows = s->rows.p;
+        R.n_rows = (uint32_t)used.size();
+        R.mask = s->mask.p;
+        R.half = total;
+        R.cols = 2 * total;
+        hipLaunchKernelGGL(rowpair_rc_kernel, dim3(R.n_rows), dim3(kRrRcBlock), 0, st, R);
+        PD_CK(who, hipGetLastError());
+    }
+    PD_CK(who, hipStreamSynchronize(st));   // `rows` and `used` are pageable
+    if (turned)
+        if (const int brc = bounds_check(c, who)) return brc;
 
     PdPlan<RdPair> pl;
     std::vector<uint32_t> res;
@@ -2093,7 +2190,7 @@ extern "C" int dmx_rowdist(dmx_ctx* c, size_t n_rows, const uint8_t* masks, cons
         const size_t hi = pd_plan(pl, lens.data(), q, r, nullptr, caps, n_pairs, lo, chunk,
                                   kPdNoBudget, rn.data());
         const size_t np = hi - lo;
-        for (RdPair& P : pl.pairs) P.row = goff[P.t];
+        for (RdPair& P : pl.pairs) P.row = goff[P.t] + (turned && strands[P.q] ? total : 0u);
         RdArgs A;
         if (const int rc = pd_stage(c, who, *s, pl, np, kKerRowdist, A)) return rc;
         A.mask = s->mask.p;
@@ -2730,9 +2827,44 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
     PD_CK(who, hipMemsetAsync(s->cnt.p, 0, sizeof(unsigned long long), st));
     PD_CK(who, hipStreamSynchronize(st));   // `rows` and the caller's tables are pageable
 
+    // operands: for a read on strand 1 the two comparisons swap copies (the forward line is the
+    // sub-range as it lies in memory against the row's reverse complement, the reverse line the
+    // same against the row), so the copies are written before the first pass
+    std::vector<uint8_t> strands;
+    if (const int rc = pd_fetch_strands(c, who, strands)) return rc;
+    bool turned = false, rc_written = false;
+    for (size_t i = 0; i < n && !strands.empty() && !turned; ++i) turned = strands[ps.q[i]] != 0;
+
     PdPlan<RaPair> pl;
     std::vector<uint32_t> need;
     float total_ms = 0.f;
+    // the reverse complement of every uploaded row, `total` columns behind the row
+    auto write_rc = [&]() -> int {
+        PD_CK(who, s->rows.reserve(used.size()));
+        PD_CK(who, hipMemcpyAsync(s->rows.p, used.data(), used.size() * sizeof(RrRow),
+                                  hipMemcpyHostToDevice, st));
+        PD_CK(who, bounds_reset(c, st));
+        RrRcArgs R;
+        R.bd = make_bounds(c, kKerRowpairRc);
+        R.rows = s->rows.p;
+        R.n_rows = (uint32_t)used.size();
+        R.mask = s->mask.p;
+        R.half = total;
+        R.cols = 2 * total;
+        PD_CK(who, hipEventRecord(s->ev[0], st));
+        hipLaunchKernelGGL(rowpair_rc_kernel, dim3(R.n_rows), dim3(kRrRcBlock), 0, st, R);
+        PD_CK(who, hipGetLastError());
+        PD_CK(who, hipEventRecord(s->ev[1], st));
+        PD_CK(who, hipStreamSynchronize(st));   // `used` is pageable
+        if (const int brc = bounds_check(c, who)) return brc;
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
+        total_ms += ms;
+        rc_written = true;
+        return DMX_OK;
+    };
+    if (turned)
+        if (const int rc = write_rc()) return rc;
     // one launch of pairs[lo .. ) of a list and its decision; in[i]: the list's pair i among the
     // call's pairs; pass 0 brings the launch's retry bitmap back (bit b: sorted pair b)
     auto launch = [&](const uint32_t* lq, const uint32_t* lr, const uint32_t* lcap,
@@ -2744,19 +2876,20 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
         for (size_t k = 0; k < np; ++k) {
             RaPair& P = pl.pairs[k];
             const size_t i = lo + pl.place(k);
-            P.row = goff[P.t] + (pass ? total : 0u);
+            const bool rev = (pass != 0) != (turned && strands[P.q] != 0);
+            P.row = goff[P.t] + (rev ? total : 0u);
             P.k = ps.place[in ? in[i] : i];
         }
         RaArgs A;
         if (const int rc = pd_stage(c, who, *s, pl, np, kKerRowassign, A)) return rc;
         A.mask = s->mask.p;
-        A.cols = pass ? 2 * total : total;
+        A.cols = rc_written ? 2 * total : total;
         A.out = s->out.p;
         PD_CK(who, s->need.reserve(words));
         if (pass == 0) PD_CK(who, hipMemsetAsync(s->need.p, 0, words * 4, st));
         RaDecide D;
-        D.bd = make_bounds(c, kKerRowassignDecide);
-        D.pairs = s->pairs.p, D.dist = s->out.p, D.lens = c->d_lens;
+        D.bd = pd_bounds(c, kKerRowassignDecide);
+        D.pairs = s->pairs.p, D.dist = s->out.p, D.lens = pd_lens(c);
         D.np = (uint32_t)np, D.pass = (uint32_t)pass;
         D.cap_hit = s->cap_hit.p, D.cap_half = s->cap_half.p;
         D.bin_off = s->bin_off.p, D.bins = s->bins.p;
@@ -2799,27 +2932,8 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
     }
     const size_t n2 = retry.size();
     if (n2) {
-        // the reverse complement of every uploaded row, `total` columns behind the row
-        PD_CK(who, s->rows.reserve(used.size()));
-        PD_CK(who, hipMemcpyAsync(s->rows.p, used.data(), used.size() * sizeof(RrRow),
-                                  hipMemcpyHostToDevice, st));
-        PD_CK(who, bounds_reset(c, st));
-        RrRcArgs R;
-        R.bd = make_bounds(c, kKerRowpairRc);
-        R.rows = s->rows.p;
-        R.n_rows = (uint32_t)used.size();
-        R.mask = s->mask.p;
-        R.half = total;
-        R.cols = 2 * total;
-        PD_CK(who, hipEventRecord(s->ev[0], st));
-        hipLaunchKernelGGL(rowpair_rc_kernel, dim3(R.n_rows), dim3(kRrRcBlock), 0, st, R);
-        PD_CK(who, hipGetLastError());
-        PD_CK(who, hipEventRecord(s->ev[1], st));
-        PD_CK(who, hipStreamSynchronize(st));   // `used` is pageable
-        if (const int brc = bounds_check(c, who)) return brc;
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-        total_ms += ms;
+        if (!rc_written)
+            if (const int rc = write_rc()) return rc;
         std::sort(retry.begin(), retry.end());
         std::vector<uint32_t> q2(n2), r2(n2), cap2(n2), tn2(n2);
         for (size_t k = 0; k < n2; ++k) {

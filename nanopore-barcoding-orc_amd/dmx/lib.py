@@ -53,7 +53,9 @@ EXPORTS = ["dmx_abi_version", "dmx_open", "dmx_close", "dmx_last_error", "dmx_se
            "dmx_pairhits_cross_host", "dmx_hitgroups_within_host", "dmx_panel_near_shared",
            "dmx_rowassign", "dmx_rowassign_host", "dmx_set_panel_ex", "dmx_ends_host",
            "dmx_set_views", "dmx_clear_views", "dmx_chop_views", "dmx_views_fetch",
-           "dmx_chop_views_host", "dmx_exec_checked"]
+           "dmx_chop_views_host", "dmx_exec_checked", "dmx_set_operands", "dmx_clear_operands",
+           "dmx_operands_fetch", "dmx_operands_check_host", "dmx_result_operands",
+           "dmx_result_operands_host"]
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 
@@ -155,6 +157,17 @@ def load() -> ctypes.CDLL:
         L.dmx_chop_views.argtypes = [P, P, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]
         L.dmx_views_fetch.argtypes = [P, P, P, P, P, c_size]
         L.dmx_chop_views_host.argtypes = [P, P, P, ctypes.c_int32, c_size, P, P, P, P, c_size]
+    if hasattr(L, "dmx_set_operands"):
+        L.dmx_set_operands.argtypes = [P, P, P, P, P, c_size]
+        L.dmx_clear_operands.argtypes = [P]
+        L.dmx_operands_fetch.argtypes = [P, P, P, P, P, c_size]
+        L.dmx_operands_check_host.argtypes = [P, c_size, P, P, P, P, c_size]
+        L.dmx_result_operands.argtypes = [P, P, c_size, ctypes.c_int32, c_u64p, c_size,
+                                          ctypes.POINTER(ctypes.c_uint64)]
+        L.dmx_result_operands_host.argtypes = [P, c_size, P, P, P, P, P, c_size, c_int, P, c_int,
+                                               P, c_int, P, c_size, ctypes.c_int32, P, P, P, P,
+                                               c_size, c_u64p, c_size,
+                                               ctypes.POINTER(ctypes.c_uint64)]
     L.dmx_comm_unique_id.argtypes = [P]
     L.dmx_comm_init_rank.argtypes = [P, P, c_int, c_int]
     L.dmx_comm_init_all.argtypes = [ctypes.POINTER(P), c_int]
@@ -433,6 +446,8 @@ class Context:
                                     p.offsets.ctypes.data, p.lengths.ctypes.data, p.n_words,
                                     p.n_reads, out.ctypes.data), "dmx_run")
         self._n_loaded = p.n_reads
+        self._ops = None
+        self._load_gen = getattr(self, "_load_gen", 0) + 1
         self._n_views = None
         self._n_exec = p.n_reads
         self._resident = None
@@ -447,6 +462,8 @@ class Context:
                                            p.lengths.ctypes.data, p.n_words, p.n_reads,
                                            out.ctypes.data), "dmx_run_sparse")
         self._n_loaded = p.n_reads
+        self._ops = None
+        self._load_gen = getattr(self, "_load_gen", 0) + 1
         self._n_views = None
         self._n_exec = p.n_reads
         self._resident = None
@@ -457,6 +474,8 @@ class Context:
                                      p.offsets.ctypes.data, p.lengths.ctypes.data, p.n_words,
                                      p.n_reads), "dmx_load")
         self._n_loaded = p.n_reads
+        self._ops = None
+        self._load_gen = getattr(self, "_load_gen", 0) + 1
         self._n_views = None
         self._n_exec = None
         self._lengths = np.array(p.lengths, dtype=np.uint32)   # pairalign sizes its output by them
@@ -533,6 +552,81 @@ class Context:
         if got != n:
             raise DmxError(f"dmx_views_fetch: {got} views on the device, {n} expected")
         return out
+
+    # ---- operand tables (include/dmx.h dmx_set_operands) -----------------------
+    def _n_sort(self) -> int:
+        """Entries of the sorting calls' per-read arrays: the operands of a table, else the
+        resident reads."""
+        ops = getattr(self, "_ops", None)
+        return int(ops["n"]) if ops is not None else int(getattr(self, "_n_loaded", 0))
+
+    def _sort_lengths(self):
+        """The lengths the sorting calls' indices name (the operands' with a table set)."""
+        ops = getattr(self, "_ops", None)
+        if ops is None:
+            return getattr(self, "_lengths", None)
+        if ops.get("lengths") is None:
+            _, a, b, _ = self.operands()
+            ops["lengths"] = (b - a).astype(np.uint32)
+        return ops["lengths"]
+
+    def set_operands(self, read, start, stop, strand):
+        """The sorting calls (pairdist, pairhits and what reads its outcomes, groupalign,
+        rowdist, rowassign) index operands from now on: operand k = read[k][start[k]:stop[k]] of
+        the resident batch, reverse-complemented when strand[k]; their results are those of the
+        same call on a batch of the operands' sequences."""
+        arrs = [np.ascontiguousarray(read, dtype=np.uint32),
+                np.ascontiguousarray(start, dtype=np.int32),
+                np.ascontiguousarray(stop, dtype=np.int32),
+                np.ascontiguousarray(strand, dtype=np.uint8)]
+        n = len(arrs[0])
+        if any(len(a) != n for a in arrs):
+            raise ValueError("set_operands: read, start, stop and strand differ in length")
+        self._check(self._L.dmx_set_operands(self._h, *[a.ctypes.data if n else None
+                                                        for a in arrs], n), "dmx_set_operands")
+        self._ops = {"n": n, "lengths": (arrs[2] - arrs[1]).astype(np.uint32)}
+        self._n_hits = 0
+        self._resident = None   # a list tagged resident ran on reads, not on this table
+
+    def clear_operands(self):
+        self._check(self._L.dmx_clear_operands(self._h), "dmx_clear_operands")
+        self._ops = None
+        self._n_hits = 0
+        self._resident = None
+
+    def operands(self):
+        """The current table as (read u32, start i32, stop i32, strand u8) arrays (empty ones
+        without a table)."""
+        ops = getattr(self, "_ops", None)
+        n = int(ops["n"]) if ops is not None else 0
+        out = (np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(n, np.int32),
+               np.zeros(n, np.uint8))
+        got = self._L.dmx_operands_fetch(self._h, *[a.ctypes.data if n else None for a in out], n)
+        if got < 0:
+            self._check(int(got), "dmx_operands_fetch")
+        if got != n:
+            raise DmxError(f"dmx_operands_fetch: {got} operands on the device, {n} expected")
+        return out
+
+    def result_operands(self, keep=None, min_len: int = 1):
+        """The operand table of the last exec, made on the device: per kept item of round 0 the
+        final trimmed, oriented record, grouped by bin (counts()' index) in item order.  keep:
+        None (the items matched in every round) or one flag per bin.  Returns bin_first (uint64,
+        bins + 1 entries: bin b's operands are bin_first[b] .. bin_first[b + 1])."""
+        nb = self.n_counts() - 2
+        ka = None
+        if keep is not None:
+            ka = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        first = np.zeros(nb + 1, dtype=np.uint64)
+        n = ctypes.c_uint64(0)
+        self._check(self._L.dmx_result_operands(
+            self._h, ka.ctypes.data if ka is not None and len(ka) else None,
+            len(ka) if ka is not None else 0, int(min_len), first.ctypes.data, len(first),
+            ctypes.byref(n)), "dmx_result_operands")
+        self._ops = {"n": int(n.value), "lengths": None}
+        self._n_hits = 0
+        self._resident = None
+        return first
 
     def locate(self, patterns, ascii_blob: np.ndarray, offsets: np.ndarray, lengths: np.ndarray,
                ignore_case: bool = False, only_positive: bool = False) -> np.ndarray:
@@ -665,7 +759,7 @@ class Context:
         parallel to groups of 0 / 1 per member; 1 (PD_RC) takes the member reverse-complemented
         (dmx_groupalign_strands), and dist, ops, count and first are then those of the turned
         read."""
-        a = _groupalign_args(getattr(self, "_lengths", None), seeds, groups, max_cols, paths,
+        a = _groupalign_args(self._sort_lengths(), seeds, groups, max_cols, paths,
                              strands=strands)
         if strands is None:
             self._check(self._L.dmx_groupalign(self._h, *a.call), "dmx_groupalign")
@@ -778,7 +872,7 @@ class Context:
         outcomes stay in the context for pairhits_fetch / hitgroups.  Returns (best, n_hits):
         best[r] = the least d over the hits whose target is r (LG_NONE: none), uint32."""
         qa, ta, ha, fa = _pairhits_arrays(q, t, cap_hit, cap_half)
-        best = np.zeros(int(getattr(self, "_n_loaded", 0)), dtype=np.uint32)
+        best = np.zeros(self._n_sort(), dtype=np.uint32)
         n = ctypes.c_uint64(0)
         self._check(self._L.dmx_pairhits(self._h, qa.ctypes.data, ta.ctypes.data, ha.ctypes.data,
                                          fa.ctypes.data, len(qa), best.ctypes.data,
@@ -802,7 +896,7 @@ class Context:
         """Components of the last pairhits' hits with d <= tie[t] (tie: uint32 per resident
         read): per read the smallest read of its group, LG_NONE for a read on no kept hit."""
         ta = np.ascontiguousarray(tie, dtype=np.uint32)
-        if ta.shape != (int(getattr(self, "_n_loaded", 0)),):
+        if ta.shape != (self._n_sort(),):
             raise DmxError("hitgroups: tie must have one entry per resident read")
         labels = np.zeros(len(ta), dtype=np.uint32)
         self._check(self._L.dmx_hitgroups(self._h, ta.ctypes.data, labels.ctypes.data),
@@ -822,7 +916,7 @@ class Context:
         """The histogram of the last pairhits' hits: hist[bins[bin_off[t] + d]] += 1 per hit with
         distance d and target t (bin_off: uint32 per resident read; bins: uint16 classes below
         n_classes <= 1024).  Returns uint64 counts, one per class."""
-        oa, ba = _hist_arrays(bin_off, bins, int(getattr(self, "_n_loaded", 0)))
+        oa, ba = _hist_arrays(bin_off, bins, self._n_sort())
         hist = np.zeros(int(n_classes), dtype=np.uint64)
         self._check(self._L.dmx_hithist(self._h, oa.ctypes.data, ba.ctypes.data, len(ba),
                                         int(n_classes), hist.ctypes.data), "dmx_hithist")
@@ -832,7 +926,7 @@ class Context:
         """The hits of the last pairhits with d <= cap2[t] (int32 per read, -1: none) whose two
         reads carry different labels (uint32 per read, LG_NONE: in no group), in ascending
         place: (pair uint32, d uint32, rev uint8)."""
-        la, ca = _label_arrays(label, cap2, int(getattr(self, "_n_loaded", 0)))
+        la, ca = _label_arrays(label, cap2, self._n_sort())
         n = ctypes.c_size_t(0)
         cap = int(getattr(self, "_n_hits", 0))
         pair, d = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
@@ -846,7 +940,7 @@ class Context:
         """Components over n_nodes nodes (default: the resident reads) of the last pairhits' hits
         with label[q] == label[t] != LG_NONE and d <= tie2[t] (LG_NONE: no edge for t), plus the
         caller's edges {xa, xb}: per node the smallest node of its component, LG_NONE on none."""
-        n_reads = int(getattr(self, "_n_loaded", 0))
+        n_reads = self._n_sort()
         ta, _ = _label_arrays(tie2, None, n_reads)
         la, _ = _label_arrays(label, None, n_reads)
         aa, ba = _edge_arrays(xa, xb)
@@ -1405,6 +1499,69 @@ def hitgroups_within_host(hits, tie2, label, xa=(), xb=(), n_nodes=None) -> np.n
     return labels
 
 
+def operands_check_host(lengths, read, start, stop, strand) -> None:
+    """dmx_set_operands' argument checks against a batch's read lengths, without a device:
+    raises DmxError (.code: the library's code) where set_operands would refuse the table."""
+    L = load()
+    la = np.ascontiguousarray(lengths, dtype=np.uint32)
+    arrs = [np.ascontiguousarray(read, dtype=np.uint32), np.ascontiguousarray(start, dtype=np.int32),
+            np.ascontiguousarray(stop, dtype=np.int32), np.ascontiguousarray(strand, dtype=np.uint8)]
+    n = len(arrs[0])
+    if any(len(a) != n for a in arrs):
+        raise ValueError("operands_check_host: read, start, stop and strand differ in length")
+    rc = L.dmx_operands_check_host(la.ctypes.data if len(la) else None, len(la),
+                                   *[a.ctypes.data if n else None for a in arrs], n)
+    if rc:
+        e = DmxError(f"dmx_set_operands failed ({rc}): "
+                     f"{(L.dmx_last_error(None) or b'').decode()}")
+        e.code = rc
+        raise e
+
+
+def result_operands_host(res, lengths, mode: int, wheres0, wheres1=None, views=None, keep=None,
+                         min_len: int = 1):
+    """Context.result_operands in plain sequential C++ on fetch()'s results: lengths are the
+    batch's read lengths, wheres0 / wheres1 the panels' adapter types (DMX_FRONT / DMX_BACK per
+    adapter), views round 0's item list (read, start, stop, strand) or None for whole reads.
+    Returns ((read, start, stop, strand), bin_first)."""
+    L = load()
+    ra = np.ascontiguousarray(res, dtype=RESULT_DTYPE)
+    la = np.ascontiguousarray(lengths, dtype=np.uint32)
+    w0 = np.ascontiguousarray(wheres0, dtype=np.int32)
+    w1 = np.ascontiguousarray(wheres1 if wheres1 is not None else [], dtype=np.int32)
+    va = [None] * 4
+    if views is not None:
+        va = [np.ascontiguousarray(views[0], dtype=np.uint32),
+              np.ascontiguousarray(views[1], dtype=np.int32),
+              np.ascontiguousarray(views[2], dtype=np.int32),
+              np.ascontiguousarray(views[3], dtype=np.uint8)]
+        if any(len(a) != len(ra) for a in va):
+            raise ValueError("result_operands_host: one view per result")
+        if not len(ra):   # an empty view run: a non-null list all the same
+            va = [np.zeros(1, a.dtype) for a in va]
+    nb = (len(w0) + 1) * ((len(w1) if mode == MODE_TWO_ROUND else 0) + 1)
+    ka = None if keep is None else np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+    n = len(ra)
+    out = (np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(n, np.int32),
+           np.zeros(n, np.uint8))
+    first = np.zeros(nb + 1, dtype=np.uint64)
+    cnt = ctypes.c_uint64(0)
+    rc = L.dmx_result_operands_host(
+        ra.ctypes.data if n else None, n, *[a.ctypes.data if a is not None else None for a in va],
+        la.ctypes.data if len(la) else None, len(la), int(mode), w0.ctypes.data, len(w0),
+        w1.ctypes.data if len(w1) else None, len(w1),
+        ka.ctypes.data if ka is not None and len(ka) else None, len(ka) if ka is not None else 0,
+        int(min_len), *[a.ctypes.data if n else None for a in out], n, first.ctypes.data,
+        len(first), ctypes.byref(cnt))
+    if rc:
+        e = DmxError(f"dmx_result_operands_host failed ({rc}): "
+                     f"{(L.dmx_last_error(None) or b'').decode()}")
+        e.code = rc
+        raise e
+    k = int(cnt.value)
+    return tuple(a[:k] for a in out), first
+
+
 def cigar(ops, extended: bool = False) -> str:
     """edlib's CIGAR of one path (a slice of pairalign's ops), run-length encoded: standard
     (M for a match or a mismatch, I, D) or extended (=, X, I, D)."""
@@ -1607,4 +1764,8 @@ def run_multi(ctxs, p: Packed):
     if rc < 0:
         msg = L.dmx_last_error(ctxs[0]._h)
         raise DmxError(f"dmx_run_multi failed ({rc}): {msg.decode() if msg else ''}")
+    for c in ctxs:   # every context's batch changed, and its operand table went with it
+        c._ops = None
+        c._resident = None
+        c._load_gen = getattr(c, "_load_gen", 0) + 1
     return out, counts

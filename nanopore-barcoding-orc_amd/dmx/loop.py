@@ -120,6 +120,20 @@ def build_parser():
     p.add_argument("-Y", dest="autotune_n", type=int, default=10000, help="pychopper -Y")
     p.add_argument("-L", dest="autotune_samples", type=int, default=None, help="pychopper -L")
     p.add_argument("--no-keep-primers", action="store_true", help="pychopper without -p")
+    # 02 -> 03 without the well files in between: the gene groups of every kept well, from the
+    # wells as they lie in the resident batch
+    p.add_argument("--groups", default=None, metavar="FILE",
+                   help="also sort: the gene groups of every kept well (dmx-similarity --groups) "
+                        "from the resident reads, one line 'well<TAB>record id<TAB>label' per "
+                        "read of the well (label: the first read of its group in the well's "
+                        "order, '-' for none); the whole input must fit one batch; one device; "
+                        "with --reorient it needs --device-views")
+    p.add_argument("--similar-genes", type=float, default=80.0, metavar="N",
+                   help="with --groups: dmx-similarity -sg (default 80.0)")
+    p.add_argument("-min", dest="minlength", type=int, default=300,
+                   help="with --groups: dmx-similarity -min (default 300)")
+    p.add_argument("-max", dest="maxlength", type=int, default=None,
+                   help="with --groups: dmx-similarity -max")
     return p
 
 
@@ -181,6 +195,8 @@ def run(argv=None) -> int:
     why = check_template(args.template)
     if args.device_views and not args.reorient:
         why = "--device-views goes with --reorient"
+    if args.groups and args.reorient and not args.device_views:
+        why = "--groups with --reorient needs --device-views (the wells must lie in one resident batch)"
     if why:
         print(f"dmx-demux-loop: error: {why}", file=sys.stderr)
         return 2
@@ -257,6 +273,10 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
     # single-device: dmx_run_multi stays whole-read only)
     dev_views = bool(args.reorient and args.device_views)
     devices = _devices(args)
+    if args.groups and not dev_views and len(devices) > 1:   # the wells are sorted where they lie
+        print(f"dmx-demux-loop: --groups runs on one device: using GPU {devices[0]} of "
+              f"{len(devices)}", file=sys.stderr)
+        devices = devices[:1]
     if dev_views and len(devices) > 1:
         print(f"dmx-demux-loop: --device-views runs on one device: using GPU {devices[0]} of "
               f"{len(devices)} (view runs are not sharded; drop the flag to use them all)",
@@ -311,6 +331,8 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
         prof.update(views=0.0)
     n2_out = np.zeros(len(n1), np.int64)
     totals = np.zeros((len(n1) + 1, len(n2) + 1), dtype=np.int64)   # device bin counts
+    group_lines = None        # --groups: the lines of the one batch, written when the input ends
+    second_batch = False
     try:
         while True:
             tw = time.perf_counter()
@@ -321,6 +343,9 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
             try:
                 if not len(batch):
                     continue
+                if args.groups and group_lines is not None:
+                    second_batch = True   # the wells of the first batch are no longer resident
+                    break
                 tw = time.perf_counter()
                 views = vstrand = None
                 packed, lens = batch.packed, batch.lens
@@ -351,7 +376,15 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
                     lens = packed.lengths
                     if not len(lens):
                         continue
-                if not dev_views:
+                if not dev_views and args.groups:   # as run_batch, and the batch stays resident
+                    tl = time.perf_counter()
+                    ctxs[0].load(packed)
+                    te = time.perf_counter()
+                    ctxs[0].exec_checked()
+                    prof["groups_load"] = te - tl
+                    prof["groups_exec"] = time.perf_counter() - te   # both rounds, synchronous
+                    res, cnt = ctxs[0].fetch(), ctxs[0].counts()
+                elif not dev_views:
                     res, cnt = lib.run_batch(ctxs, packed)
                 totals += lib.bin_totals(cnt, len(n1), len(n2))
                 prof["gpu"] += time.perf_counter() - tw
@@ -399,6 +432,10 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
                 tq = time.perf_counter()
                 prof["pw_stats"] += tq - tr
                 prof["plan_write"] += tq - tw
+                if args.groups:
+                    rd = views[0] if views is not None else np.arange(len(batch))
+                    group_lines = _well_groups(args, ctxs[0], batch, rd, views, b1, b2, n2,
+                                               idx2, e2w - s2w, p2, prof)
             finally:
                 tf = time.perf_counter()
                 batch.free()
@@ -413,6 +450,16 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
             reo.close()
         prof["drain"] += time.perf_counter() - tw
         marks.append(("drain", time.perf_counter() - _T_IMPORT))
+    if second_batch:
+        print("dmx-demux-loop: error: --groups needs the whole input in one resident batch, and "
+              "the input has a second one (raise --batch-mb); no groups written",
+              file=sys.stderr)
+        for ctx in ctxs:
+            ctx.close()
+        return 3
+    if args.groups:
+        with open(args.groups, "w") as f:
+            f.write("".join(group_lines or []))
     if reo is not None:
         prof.update({"reo_" + k: v for k, v in reo.prof.items()})
     # the devices' (SP5, SP27) bin counts (RCCL-summed over GPUs) vs the per-read results
@@ -445,6 +492,63 @@ def _loop_body(args, argv, infile, outdir, ds, demux_in, pych_dir, base, ads1, a
     print("Pipeline complete!")
     print(f"Results in: {outdir}")
     return 0
+
+
+def _well_groups(args, ctx, batch, rd, views, b1, b2, n2, idx2, final_len, p2, prof):
+    """--groups: sorter.gene_groups of every kept well on the resident batch.  The operand table
+    is made on the device from the run's results (dmx_result_operands) with the script's
+    post-filter as keep: matched in both rounds and not one of INVALID_SP27; well b's operands are
+    its records of at least 1 nt, in input order, which is the order of its file.  Returns the
+    lines 'well<TAB>record id<TAB>label', wells in file-name order, reads in input order; the
+    label is the first read of the read's group, counted among the well's records, or '-'."""
+    from . import sorter
+    t0 = time.perf_counter()
+    a1 = len(n2) + 1
+    keep = np.zeros((ctx.n_counts() - 2) // a1 * a1, dtype=np.uint8).reshape(-1, a1)
+    for j, nm in enumerate(n2):
+        if nm not in INVALID_SP27:
+            keep[1:, j + 1] = 1
+    tb = time.perf_counter()
+    first = ctx.result_operands(keep.reshape(-1), 1)
+    prof["groups_build"] = time.perf_counter() - tb   # the synchronous call: three kernels, bin_first
+    ops = sorter.Operands(ctx, batch.sequence)
+    prof["groups_table"] = time.perf_counter() - t0   # ... and the table's host mirror
+    bins = (b1 + 1) * a1 + (b2 + 1)
+    lines = []
+    kernel_ms = 0.0
+    for b in sorted(np.flatnonzero(keep.reshape(-1)).tolist(),
+                    key=lambda x: os.path.basename(p2[int(idx2[bins == x][0])])
+                    if (bins == x).any() else ""):
+        items = np.flatnonzero(bins == b)
+        if not len(items):
+            continue
+        well = os.path.basename(p2[int(idx2[items[0]])])
+        live = final_len[items] >= 1           # the records that are operands
+        lo, hi = int(first[b]), int(first[b + 1])
+        if hi - lo != int(live.sum()):
+            raise lib.DmxError(f"--groups: well {well} has {int(live.sum())} records of 1 nt or "
+                               f"more and {hi - lo} operands")
+        wops = ops.bin(first, b)
+        lens = [int(x) for x in wops.lengths]
+        kept = sorter.usable(lens, args.minlength, args.maxlength)   # the groups index these
+        groups = sorter.gene_groups(ctx, wops, args.similar_genes, args.minlength,
+                                    args.maxlength)
+        st = ctx.hitgroups_stats()
+        kernel_ms += st["forward"] + st["compact"] + st["components"]
+        place = np.flatnonzero(live)           # operand -> its place among the well's records
+        label = {}
+        for g in groups:
+            mem = [int(place[kept[int(x)]]) for x in g]
+            for m in mem:
+                label[m] = min(mem)
+        for k, it in enumerate(items):
+            name = batch.header(int(rd[it])).split()[0].lstrip(b"@>").decode("ascii", "replace")
+            if views is not None:
+                name = f"{int(views[1][it])}:{int(views[2][it])}|{name}"
+            lines.append(f"{well}\t{name}\t{label.get(k, '-')}\n")
+    prof["groups"] = time.perf_counter() - t0
+    prof["groups_kernel"] = kernel_ms / 1000
+    return lines
 
 
 class Reorienter:

@@ -246,9 +246,94 @@ def revcomp(seq: bytes) -> bytes:
     return seq[::-1].translate(_RC)
 
 
+_NOT_ACGT = bytes(c for c in range(256) if c not in b"ACGT")
+
+
+class Operands:
+    """Reads that are already on the GPU: operands of the batch resident in `ctx` (DESIGN.md
+    §3.18), to be passed wherever the functions here take `reads`.  The functions then skip
+    clean, pack and load: they select by the operands' lengths, set the selected operands as the
+    context's table and run on the resident batch, with the results they return for the list of
+    the operands' sequences.
+    Operands(ctx, seqs_source) takes the context's current table (Context.result_operands or
+    set_operands); a slice is the operands of that range, so with bin_first of result_operands
+    `ops.bin(bin_first, b)` is well b and indices are local to it.  seqs_source is the host copy
+    of the batch: read r's bases are seqs_source[r] (str or bytes), or seqs_source(r) for a
+    callable.  len() is the number of operands; ops[k] the cleaned sequence of operand k (bytes
+    over A/C/G/T/N as the packed batch holds it, the sub-range, reverse-complemented on strand
+    1), materialised on first use: orient()'s duplicate test and the consensus text need it."""
+
+    def __init__(self, ctx, seqs_source, table=None):
+        if ctx is None:
+            raise DmxError("Operands need a Context: the host twins run on packed sequences")
+        self.ctx, self.source = ctx, seqs_source
+        t = ctx.operands() if table is None else table
+        self.read = np.ascontiguousarray(t[0], dtype=np.uint32)
+        self.start = np.ascontiguousarray(t[1], dtype=np.int32)
+        self.stop = np.ascontiguousarray(t[2], dtype=np.int32)
+        self.strand = np.ascontiguousarray(t[3], dtype=np.uint8)
+        self.lengths = (self.stop - self.start).astype(np.int64)
+        self._gen = getattr(ctx, "_load_gen", 0)
+        self._seqs = {}
+
+    def __len__(self):
+        return len(self.read)
+
+    def subset(self, idx):
+        """The operands idx (an index array or a slice), as Operands of their own."""
+        sub = Operands(self.ctx, self.source, (self.read[idx], self.start[idx], self.stop[idx],
+                                               self.strand[idx]))
+        sub._gen = self._gen   # of the batch these operands were made on, not of today's
+        return sub
+
+    def bin(self, bin_first, b):
+        """Bin b of a table made by Context.result_operands, which returned bin_first."""
+        return self.subset(slice(int(bin_first[b]), int(bin_first[b + 1])))
+
+    def __getitem__(self, k):
+        if isinstance(k, slice):
+            return self.subset(k)
+        k = int(k)
+        if k < 0:
+            k += len(self)
+        if k not in self._seqs:
+            r = int(self.read[k])
+            raw = self.source(r) if callable(self.source) else self.source[r]
+            b = raw.encode("ascii", "replace") if isinstance(raw, str) else bytes(raw)
+            b = b[int(self.start[k]):int(self.stop[k])].upper()
+            b = b.translate(bytes.maketrans(_NOT_ACGT, b"N" * len(_NOT_ACGT)))
+            self._seqs[k] = revcomp(b) if self.strand[k] else b
+        return self._seqs[k]
+
+    def activate(self):
+        """These operands become the context's table: index k of a sorting call is operand k."""
+        ctx = self.ctx
+        if getattr(ctx, "_load_gen", 0) != self._gen:
+            raise DmxError("Operands: another batch was loaded since these operands were made")
+        if getattr(ctx, "_resident", None) is not self:
+            ctx.set_operands(self.read, self.start, self.stop, self.strand)
+            ctx._resident = self   # a list's batch is not resident: its next pass loads again
+
+
+def _load(ctx, p):
+    """The plan's batch into ctx: a packed batch is loaded, Operands become the table."""
+    if isinstance(p, Operands):
+        p.activate()
+    else:
+        ctx.load(p)
+
+
 def _pack_reads(ctx, reads):
     """The cleaned reads, their lengths and their batch, packed once and loaded into ctx (when
-    there is one): what orient(), consensus() and make_consensus() run on."""
+    there is one): what orient(), consensus() and make_consensus() run on.  Operands are
+    resident: no clean, no pack, no load; their sequences come on demand."""
+    if isinstance(reads, Operands):
+        if len(reads) and int(reads.lengths.max()) > lib.PD_MAX_LEN:
+            raise DmxError(f"a read is longer than {lib.PD_MAX_LEN} nt")
+        if ctx is not reads.ctx:
+            raise DmxError("Operands run on the Context they were made with")
+        reads.activate()
+        return reads, reads.lengths, None
     seqs = _clean(reads)
     ln = np.array([len(s) for s in seqs], dtype=np.int64)
     if len(ln) and int(ln.max()) > lib.PD_MAX_LEN:
@@ -530,7 +615,10 @@ def assign_best(ctx, reads, unassigned, consensuses, similar: float, n_threads: 
     Returns (best, added): exactly assign()'s second and third return values for the same
     arguments, the same tuples (read, group, iden) with iden = class / 1000, in the same order.
     The batch of an unchanged `reads` list stays resident (ctx._resident), as in assign()."""
-    seqs = _clean(reads)
+    ops = reads if isinstance(reads, Operands) else None
+    if ops is not None and ctx is not ops.ctx:
+        raise DmxError("Operands run on the Context they were made with")
+    seqs = ops if ops is not None else _clean(reads)
     cons = _clean(consensuses, "consensus")
     for g, s in enumerate(cons):
         if not s:
@@ -538,7 +626,7 @@ def assign_best(ctx, reads, unassigned, consensuses, similar: float, n_threads: 
     un = np.asarray(unassigned, dtype=np.int64).reshape(-1)
     if len(un) and (int(un.min()) < 0 or int(un.max()) >= len(seqs)):
         raise DmxError("assign_best: an unassigned index is outside the reads")
-    ln = np.array([len(s) for s in seqs], dtype=np.int64)
+    ln = ops.lengths if ops is not None else np.array([len(s) for s in seqs], dtype=np.int64)
     lc = np.array([len(s) for s in cons], dtype=np.int64)
     if (len(ln) and int(ln.max()) > lib.PD_MAX_LEN) or (len(lc) and int(lc.max()) > lib.PD_MAX_LEN):
         raise DmxError(f"a read or a consensus is longer than {lib.PD_MAX_LEN} nt")
@@ -547,7 +635,9 @@ def assign_best(ctx, reads, unassigned, consensuses, similar: float, n_threads: 
     tables = _assign_tables(np.concatenate([ln[un], lc]), similar)
     rows = [lib.mask_row(s) for s in cons]
     p = None
-    if ctx is None or getattr(ctx, "_resident", None) is not reads:
+    if ops is not None:
+        ops.activate()
+    elif ctx is None or getattr(ctx, "_resident", None) is not reads:
         blob = np.frombuffer(b"".join(seqs), dtype=np.uint8)
         offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
         p = lib.pack(blob, offs, ln.astype(np.uint32))
@@ -621,7 +711,7 @@ def rest_reads(ctx, reads, indexes, groups, consensuses, similar_species: float 
     state = {"kept": [], "groups": groups, "cons": cons}
 
     def tag():   # make_consensus loaded this very list, packed as assign_best packs it
-        if ctx is not None:
+        if ctx is not None and not isinstance(reads, Operands):   # (Operands tag themselves)
             ctx._resident = reads
 
     def process():
@@ -850,11 +940,12 @@ def _similarity_plan(reads, similar_genes, minlength, maxlength, maxreads, allre
     """What similarity() and gene_groups() compare: the length-filtered reads packed, their
     lengths, the pairs (shorter, longer) and, per pair, the largest distance whose identity is
     still >= similar_genes / 100 and >= 0.5 (-1: none).  p is None when there is no pair."""
-    seqs = _clean(reads)
-    idx = usable([len(s) for s in seqs], minlength, maxlength)
-    groups = select_groups([len(s) for s in seqs], minlength, maxlength, maxreads, allreads)
-    seqs = [seqs[i] for i in idx]
-    ln = np.array([len(s) for s in seqs], dtype=np.int64)
+    ops = reads if isinstance(reads, Operands) else None
+    seqs = None if ops is not None else _clean(reads)
+    all_ln = [int(x) for x in ops.lengths] if ops is not None else [len(s) for s in seqs]
+    idx = usable(all_ln, minlength, maxlength)
+    groups = select_groups(all_ln, minlength, maxlength, maxreads, allreads)
+    ln = np.array([all_ln[i] for i in idx], dtype=np.int64)
     if len(ln) and int(ln.max()) > lib.PD_MAX_LEN:
         raise DmxError(f"a read is longer than {lib.PD_MAX_LEN} nt (pass maxlength)")
     q, t = pairs(groups, ln)
@@ -868,7 +959,10 @@ def _similarity_plan(reads, similar_genes, minlength, maxlength, maxreads, allre
     for L in np.unique(ln[t]):
         cap_half[L] = identity_cap(int(L), 0.5)
         cap_sg[L] = identity_cap(int(L), sg)
-    blob = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+    if ops is not None:   # resident: the selected operands stand for the packed batch
+        return (ops.subset(np.asarray(idx, dtype=np.int64)), ln, q, t, cap_sg[ln[t]],
+                cap_half[ln[t]])
+    blob = np.frombuffer(b"".join(seqs[i] for i in idx), dtype=np.uint8)
     offs = np.concatenate([[0], np.cumsum(ln[:-1])]).astype(np.uint64)
     p = lib.pack(blob, offs, ln.astype(np.uint32))
     return p, ln, q, t, cap_sg[ln[t]], cap_half[ln[t]]
@@ -886,7 +980,7 @@ def similarity(ctx, reads, similar_genes: float = 80.0, minlength: int = 300, ma
                                                      maxreads, allreads)
     lines = []
     if len(q):
-        ctx.load(p)
+        _load(ctx, p)
         lt = ln[t]
         # the exact distance is needed wherever the identity is >= 0.5 or >= sg
         fcap = np.maximum(np.maximum(cap_half, cap_sg), 0).astype(np.uint32)
@@ -938,8 +1032,10 @@ def gene_groups(ctx, reads, similar_genes: float = 80.0, minlength: int = 300, m
                                                      maxreads, allreads)
     if not len(q):
         return []
+    if isinstance(p, Operands) and ctx is not p.ctx:
+        raise DmxError("Operands run on the Context they were made with")
     if ctx is not None:
-        ctx.load(p)
+        _load(ctx, p)
         best, _ = ctx.pairhits(q, t, cap_sg, cap_half)
     else:
         hits = lib.pairhits_host(p, q, t, cap_sg, cap_half, n_threads=n_threads)
@@ -969,8 +1065,10 @@ N_CLASSES = 1001   # identity classes of the histogram: thousandths, 0.000 .. 1.
 
 def _run_pairhits(ctx, p, q, t, cap_sg, cap_half, n_threads):
     """pairhits on the plan's batch: (best, hits) with hits the host state, or None on a ctx."""
+    if isinstance(p, Operands) and ctx is not p.ctx:
+        raise DmxError("Operands run on the Context they were made with")
     if ctx is not None:
-        ctx.load(p)
+        _load(ctx, p)
         return ctx.pairhits(q, t, cap_sg, cap_half)[0], None
     hits = lib.pairhits_host(p, q, t, cap_sg, cap_half, n_threads=n_threads)
     return hits.best, hits
