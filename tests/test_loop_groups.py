@@ -76,19 +76,14 @@ def _run(tmp_path, tag, *extra, check=True):
     return out, r
 
 
-def test_groups_equal_dmx_similarity_on_the_well_files(tmp_path):
-    g = tmp_path / "groups.tsv"
-    out, _ = _run(tmp_path, "with", "--groups", str(g))
-    plain, _ = _run(tmp_path, "without")
-    files = sorted(os.path.relpath(p, out) for p in glob.glob(str(out / "SP*" / "*.fastq.gz")))
-    assert files == sorted(os.path.relpath(p, plain)
-                           for p in glob.glob(str(plain / "SP*" / "*.fastq.gz")))
-    for f in files:   # the outputs the loop writes today are unchanged
-        assert (out / f).read_bytes() == (plain / f).read_bytes(), f
+def groups_equal_dmx_similarity(tmp_path, out, g, ds):
+    """FILE g of a --groups run into `out` names the kept wells of dataset `ds` in file-name
+    order, every read of a well in the well file's order, and per well the groups that
+    dmx-similarity --groups makes of the written well file."""
     rows = [ln.split("\t") for ln in g.read_text().splitlines()]
     wells = sorted({r[0] for r in rows})
     sp5, sp27 = _panels()
-    assert wells == sorted(f"{sp27[j].name}_{sp5[i].name}_s1.fastq.gz" for i, j in WELLS)
+    assert wells == sorted(f"{sp27[j].name}_{sp5[i].name}_{ds}.fastq.gz" for i, j in WELLS)
     assert [r[0] for r in rows] == sorted(r[0] for r in rows)   # wells in file-name order
     for w in wells:
         path = str(out / "SP27" / w)
@@ -109,6 +104,18 @@ def test_groups_equal_dmx_similarity_on_the_well_files(tmp_path):
                for ln in gf.read_text().splitlines() if ln.strip()}
         assert got == exp and len(exp) >= 2 and sum(len(x) for x in exp) >= 80
         assert any(lab == "-" for _, _, lab in mine)   # the short records are in no group
+
+
+def test_groups_equal_dmx_similarity_on_the_well_files(tmp_path):
+    g = tmp_path / "groups.tsv"
+    out, _ = _run(tmp_path, "with", "--groups", str(g))
+    plain, _ = _run(tmp_path, "without")
+    files = sorted(os.path.relpath(p, out) for p in glob.glob(str(out / "SP*" / "*.fastq.gz")))
+    assert files == sorted(os.path.relpath(p, plain)
+                           for p in glob.glob(str(plain / "SP*" / "*.fastq.gz")))
+    for f in files:   # the outputs the loop writes today are unchanged
+        assert (out / f).read_bytes() == (plain / f).read_bytes(), f
+    groups_equal_dmx_similarity(tmp_path, out, g, "s1")
 
 
 def test_a_second_batch_is_refused_before_the_file_exists(tmp_path):

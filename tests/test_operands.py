@@ -199,9 +199,175 @@ def test_rowassign_on_operands(ctx):
     assert ((exp[1] != NONE) & ~rev & (tab[3][sel] == 1)).any()
 
 
+# ---- the same calls on the trapped geometry -----------------------------------------------------
+# Edge lengths (1, 63 .. 129, 4200), every start % 32, strand-1 operands of len % 64 in {0, 1, 63},
+# N bases and batch edges: where the host folds a strand into pair flags (pairhits), into the
+# strands launch (groupalign) or into which copy of a row is read (rowdist, rowassign).
+
+def _both_ways(pairs):
+    return (np.concatenate([pairs[:, 0], pairs[:, 1]]).astype(np.uint32),
+            np.concatenate([pairs[:, 1], pairs[:, 0]]).astype(np.uint32))
+
+
+def geo_hit_case():
+    """The geometry's pairs both ways round with _hit_caps' caps."""
+    reads, tab, pairs = oc.geometry()
+    q, t = _both_ways(pairs)
+    ln = (tab[2] - tab[1]).astype(int)
+    ch, cf = _hit_caps(ln, t)
+    return q, t, ch, cf
+
+
+def test_pairhits_on_the_geometry(ctx):
+    reads, tab, pairs = oc.geometry()
+    rep = _load(ctx, reads, tab)
+    n = len(tab[0])
+    ln, st = (tab[2] - tab[1]).astype(int), tab[3]
+    q, t, ch, cf = geo_hit_case()
+    hh = lib.pairhits_host(rep, q, t, ch, cf, n_threads=8)
+    best, nh = ctx.pairhits(q, t, ch, cf)
+    assert best.shape == (n,) and nh == int((hh.outcome != NONE).sum()) > len(pairs)
+    np.testing.assert_array_equal(best, hh.best)
+    got, exp = ctx.pairhits_fetch(), hh.fetch()
+    for g, e in zip(got, exp):
+        np.testing.assert_array_equal(g, e)
+    hit = exp[0]
+    for L in (1, 63, 64, 65, 4200):   # hits between operands of every edge length
+        assert ((ln[q[hit]] == L) & (ln[t[hit]] == L)).any(), L
+    assert {(int(a), int(b)) for a, b in zip(st[q[hit]], st[t[hit]])} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    # the reverse retry ran for pairs of equal and of mixed strands: no forward hit, df > cap_half
+    df = lib.pairdist_host(rep, q, t, lib.PD_NW, n_threads=8).astype(np.int64)
+    retried = (df > ch) & (df > cf) & (ch >= 0)
+    assert (retried & (st[q] != st[t])).any() and (retried & (st[q] == st[t])).any()
+    tie = np.where(hh.best == NONE, 0, hh.best + 2).astype(np.uint32)
+    np.testing.assert_array_equal(ctx.hitgroups(tie), lib.hitgroups_host(hh, tie))
+    # the trap is armed: on whole reads the flanks' copies change the outcomes
+    ctx.clear_operands()
+    ctx.pairhits(tab[0][q], tab[0][t], ch, cf)
+    whole = ctx.pairhits_fetch()
+    assert len(whole[0]) != len(hit) or (whole[1] != exp[1]).mean() > 0.25
+    ctx.set_operands(*tab)
+
+
+def geo_groups():
+    """One group per geometry pair (seed: the first operand's sequence), then groups of three
+    operands whose lengths straddle 64 and 128, and per member a requested strand such that every
+    (member's strand, requested strand) occurs."""
+    reads, tab, pairs = oc.geometry()
+    strings = oc.extract(reads, tab)
+    ln, st = (tab[2] - tab[1]).astype(int), tab[3]
+    groups = [[int(a), int(b)] for a, b in pairs]
+    for lens3 in ((63, 64, 65), (127, 128, 129), (65, 63, 64), (129, 127, 128)):
+        for s in (0, 1):
+            groups.append([int(np.flatnonzero((ln == L) & (st == (s ^ (i & 1))))[i])
+                           for i, L in enumerate(lens3)])
+    seeds = [strings[g[0]] for g in groups]
+    strands = [[(k + i) % 2 for i in range(len(g))] for k, g in enumerate(groups)]
+    return groups, seeds, strands
+
+
+def test_groupalign_on_the_geometry(ctx):
+    reads, tab, pairs = oc.geometry()
+    rep = _load(ctx, reads, tab)
+    groups, seeds, strands = geo_groups()
+    st = tab[3]
+    combos = {(int(st[m]), s) for g, ss in zip(groups, strands) for m, s in zip(g, ss)}
+    assert combos == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    ln = (tab[2] - tab[1]).astype(int)
+    assert {1, 4200} <= {int(ln[m]) for g in groups for m in g}
+    exp = lib.groupalign_host(rep, seeds, groups, paths=True, strands=strands, n_threads=8)
+    got = ctx.groupalign(seeds, groups, paths=True, strands=strands)
+    for k in ("col_off", "mask", "count", "first", "dist", "op_off", "ops"):
+        np.testing.assert_array_equal(got[k], exp[k], err_msg=k)
+    # dmx_groupalign itself: the table's strands alone decide which launch serves a member
+    exp = lib.groupalign_host(rep, seeds, groups, n_threads=8)
+    got = ctx.groupalign(seeds, groups)
+    for k in ("col_off", "mask", "count", "first", "dist"):
+        np.testing.assert_array_equal(got[k], exp[k], err_msg=k)
+    # near copies on their own strands: most members lie close to their seed
+    sizes = np.array([len(g) for g in groups])
+    seedlen = np.repeat([len(s) for s in seeds], sizes)
+    assert (exp["dist"] <= 0.25 * seedlen + 2).mean() > 0.5
+    ctx.clear_operands()
+    whole = ctx.groupalign(seeds, [[int(tab[0][m]) for m in g] for g in groups])
+    assert (whole["dist"] != exp["dist"]).mean() > 0.25
+    ctx.set_operands(*tab)
+
+
+def geo_rows(rng, flip=False):
+    """Per geometry operand a consensus-like row of its sequence (IUPAC and gap columns from 63 nt
+    up, as _rows writes them).  flip: every second row is written reverse-complemented."""
+    reads, tab, _ = oc.geometry()
+    rows = []
+    for k, s in enumerate(oc.extract(reads, tab)):
+        s = list(s)
+        if len(s) >= 63:
+            for i in range(5, len(s), 23):
+                s[i] = "RYMKSW"[int(rng.integers(6))]
+            for i in range(11, len(s), 41):
+                s.insert(i, "-")
+        m = lib.mask_row("".join(s))
+        rows.append(lib.mask_rc(m) if flip and k % 2 else m)
+    return rows
+
+
+def test_rowdist_on_the_geometry(ctx):
+    reads, tab, pairs = oc.geometry()
+    rep = _load(ctx, reads, tab)
+    n = len(tab[0])
+    fwd = geo_rows(np.random.default_rng([SEED, 9]))
+    rows = [x for m in fwd for x in (m, lib.mask_rc(m))]   # row 2 k and its reverse complement
+    a, b = _both_ways(pairs)
+    q = np.concatenate([a, a, a]).astype(np.uint32)
+    r = np.concatenate([2 * b, 2 * b + 1, 2 * a]).astype(np.uint32)
+    assert set(q.tolist()) == set(range(n))               # every operand is a query
+    for caps in (None, np.full(len(q), 7, np.uint32)):
+        exp = lib.rowdist_host(rep, rows, q, r, caps, n_threads=8)
+        np.testing.assert_array_equal(ctx.rowdist(rows, q, r, caps), exp)
+    exp = lib.rowdist_host(rep, rows, q, r, None, n_threads=8)
+    own = exp[2 * len(a):]
+    ln = (tab[2] - tab[1]).astype(int)
+    # an operand against its own row: the gap columns and the IUPAC columns that lost its base
+    assert (own <= ln[a] // 41 + ln[a] // 23 + 2).all() and (own[ln[a] >= 63] > 0).all()
+    # the trap is armed: a table that is ignored reads whole reads, flanks and all
+    ctx.clear_operands()
+    whole = ctx.rowdist(rows, tab[0][q], r)
+    assert (whole != exp).mean() > 0.25
+    ctx.set_operands(*tab)
+
+
+def test_rowassign_on_the_geometry(ctx):
+    reads, tab, pairs = oc.geometry()
+    rep = _load(ctx, reads, tab)
+    n = len(tab[0])
+    strings = oc.extract(reads, tab)
+    every = geo_rows(np.random.default_rng([SEED, 10]), flip=True)
+    rows = [every[int(a)] for a in pairs[:, 0]]            # forward rows only: the call turns them
+    ln = [len(s) for s in strings] + [len(x) for x in rows]
+    cap_hit, cap_half, bin_off, bins = rac.tables(ln)
+    sel = np.arange(n, dtype=np.uint32)[::-1].copy()
+    exp = lib.rowassign_host(rep, rows, sel, cap_hit, cap_half, bin_off, bins, n_threads=8)
+    got = ctx.rowassign(rows, sel, cap_hit, cap_half, bin_off, bins)
+    for g, e in zip(got, exp):
+        np.testing.assert_array_equal(g, e)
+    st = tab[3][sel]
+    has = exp[0] != NONE
+    rev = has & ((exp[1] & lib.LG_REV) != 0)
+    assert rev.any() and (st[rev] == 1).any() and (st[rev] == 0).any()
+    assert (has & ~rev & (st == 1)).any() and (has & ~rev & (st == 0)).any()
+    sl = np.array([len(s) for s in strings])[sel]
+    for L in (1, 63, 64, 65, 4200):
+        assert (has & (sl == L)).any(), L
+    ctx.clear_operands()
+    whole = ctx.rowassign(rows, tab[0][sel], *rac.tables(
+        [len(x) for x in reads] + [len(x) for x in rows]))
+    assert (whole[0] != exp[0]).mean() > 0.25
+    ctx.set_operands(*tab)
+
+
 # ---- dmx_result_operands ------------------------------------------------------------------------
 
-BLOCK = 256   # the builder's tile (csrc/dmx_operands.hip kOpBlock)
+BLOCK = 256  # the builder's tile (csrc/dmx_operands.hip kOpBlock)
 
 
 @functools.lru_cache(maxsize=None)
