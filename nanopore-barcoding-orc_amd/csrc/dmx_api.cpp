@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -60,24 +61,46 @@ uint8_t iupac_mask(char ch) {
     }
 }
 
-template <typename T>
-int dev_alloc(Ctx* c, T** p, size_t count) {
-    if (*p) {
-        hipFree(*p);
-        *p = nullptr;
-    }
-    if (count == 0) count = 1;
-    CK(hipMalloc((void**)p, count * sizeof(T)));
-    return DMX_OK;
-}
-
-
 // (A0+1)(A1+1) per-bin counts + 2 RC counts (include/dmx.h dmx_counts)
 size_t counts_size(const Ctx* c) {
     const size_t a1 = c->mode == DMX_MODE_SINGLE ? 0 : (size_t)c->panel[1].n_all;
     return ((size_t)c->panel[0].n_all + 1) * (a1 + 1) + 2;
 }
 
+// dmx_stats' flag bits (include/dmx.h): lists that overflowed are grown and the pipeline run again
+// (exec_checked); the other two are internal errors.
+enum StatFlag {
+    kFlagClusters = 1, kFlagTraceback = 2, kFlagWindows = 4, kFlagCands = 8, kFlagFilter = 16,
+    kFlagsOverflow = kFlagClusters | kFlagWindows | kFlagCands,
+    kFlagsInternal = kFlagTraceback | kFlagFilter
+};
+
+// The window list and what is sized with it: the verified windows, 4 screen tasks per window
+// record, the filter tasks.
+int reserve_windows(Ctx* c, size_t n) {
+    CK(c->d_win.reserve(n));
+    CK(c->d_win2.reserve(n));
+    CK(c->d_tasks.reserve(4 * n));
+    CK(c->d_ftask.reserve(n));
+    return DMX_OK;
+}
+
+int reserve_cands(Ctx* c, size_t n) {
+    for (int r = 0; r < 2; ++r)
+        for (int l = 0; l < 2; ++l) CK(c->d_cand[r][l].reserve(n));
+    return DMX_OK;
+}
+
+int reserve_clusters(Ctx* c, size_t n) {
+    for (int r = 0; r < 2; ++r) {
+        CK(c->d_cl[r].reserve(n));
+        CK(c->d_outc[r].reserve(n));
+    }
+    return DMX_OK;
+}
+
+// Room for the current batch, mode and panels.  Every capacity is read from its buffers, so a
+// buffer whose allocation failed in an earlier call is allocated again here.
 int ensure_pipeline(Ctx* c) {
     // a view run has one item, winner slot and result per view, and views may outnumber the reads
     const size_t n = c->views_on ? std::max(c->n_reads, c->n_views) : c->n_reads;
@@ -86,152 +109,80 @@ int ensure_pipeline(Ctx* c) {
     const size_t items = linked ? slots0 : n;
     // non-linked rounds may need one winner slot per (item, orientation): see orient_slot
     const size_t need = std::max(slots0, items) * (linked ? 1 : 2);
-    if (!c->d_res || c->res_cap < n) {   // the resident input set's result array
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_res, n))) return rc;
-        c->res_cap = n;
+    CK(c->in.res.reserve(n));   // the resident input set's result array
+    for (int r = 0; r < 2; ++r) {
+        CK(c->d_winner[r].reserve(need));
+        CK(c->d_lb[r].reserve(need));
     }
-    if (c->slot_cap < need || c->cap_reads < n) {
-        const size_t s = need;
-        int rc;
-        for (int r = 0; r < 2; ++r) {
-            if ((rc = dev_alloc(c, &c->d_winner[r], s))) return rc;
-            if ((rc = dev_alloc(c, &c->d_lb[r], s))) return rc;
-        }
-        if ((rc = dev_alloc(c, &c->d_linked, n))) return rc;
-        c->slot_cap = s;
-        c->cap_reads = n;
-    }
+    CK(c->d_linked.reserve(n));
     // per-slot origins: only for the rounds this mode runs in ring mode (a band round's winner
     // key carries its origin), sized like the winner slots
     for (int r = 0; r < 2; ++r) {
-        if ((r == 1 && c->mode == DMX_MODE_SINGLE) || band_round(c, r) ||
-            c->origin_cap[r] >= c->slot_cap)
-            continue;
-        c->origin_cap[r] = 0;
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_origin[r], c->slot_cap))) return rc;
-        c->origin_cap[r] = c->slot_cap;
+        if ((r == 1 && c->mode == DMX_MODE_SINGLE) || band_round(c, r)) continue;
+        CK(c->d_origin[r].reserve(slot_cap(c)));
     }
-    // The item list has its own capacity: a linked batch needs reads x pairs items, which can
-    // exceed what an earlier two-round batch allocated (reads) while its winner slots (2 x
-    // reads) still suffice.  Sizing it only with the slots let finalize0_linked write past
-    // d_items (an illegal memory access in a parity sweep that ran a two-round case, then a
-    // linked one of fewer reads, on one context).
-    if (c->item_alloc < items) {
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_items, items))) return rc;
-        c->item_alloc = items;
-    }
+    // The item list is sized by its own need: a linked batch has reads x pairs items, which can
+    // exceed what an earlier two-round batch needed (reads) while its winner slots (2 x reads)
+    // still suffice.
+    CK(c->d_items.reserve(items));
     c->item_cap = items;
-    if (c->views_on && c->mode != DMX_MODE_SINGLE && c->item_src_alloc < items) {
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_item_src, items))) return rc;
-        c->item_src_alloc = items;
-    }
-    const size_t want_cl = 4 * std::max(slots0, n) + 65536;
-    if (c->cl_cap < want_cl) {
-        int rc;
-        for (int r = 0; r < 2; ++r) {
-            if ((rc = dev_alloc(c, &c->d_cl[r], want_cl))) return rc;
-            if ((rc = dev_alloc(c, &c->d_outc[r], want_cl))) return rc;
-        }
-        c->cl_cap = want_cl;
-    }
-    const size_t want_cand = 4 * std::max(slots0, n) + 65536;
-    if (c->cand_cap < want_cand) {
-        int rc;
-        for (int r = 0; r < 2; ++r)
-            for (int l = 0; l < 2; ++l) {
-                if ((rc = dev_alloc(c, &c->d_cand[r][l], want_cand))) return rc;
-            }
-        c->cand_cap = want_cand;
-    }
-    const size_t want_win = 4 * 2 * std::max(slots0, n) + 65536;
-    if (c->win_cap < want_win) {
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_win, want_win))) return rc;
-        if ((rc = dev_alloc(c, &c->d_win2, want_win))) return rc;
-        if ((rc = dev_alloc(c, &c->d_tasks, 4 * want_win))) return rc;
-        if ((rc = dev_alloc(c, &c->d_ftask, want_win))) return rc;
-        c->win_cap = want_win;
-        c->task_cap = 4 * want_win;
-        c->ftask_cap = want_win;
-    }
+    if (c->views_on && c->mode != DMX_MODE_SINGLE) CK(c->d_item_src.reserve(items));
+    int rc;
+    if ((rc = reserve_clusters(c, 4 * std::max(slots0, n) + 65536))) return rc;
+    if ((rc = reserve_cands(c, 4 * std::max(slots0, n) + 65536))) return rc;
+    if ((rc = reserve_windows(c, 4 * 2 * std::max(slots0, n) + 65536))) return rc;
     const size_t nc = counts_size(c);
-    if (c->n_counts != nc) {
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_counts, nc))) return rc;
-        c->n_counts = nc;
-    }
+    c->n_counts = 0;   // until there is room: dmx_counts and the all-reduce copy n_counts words
+    CK(c->d_counts.reserve(nc));
+    c->n_counts = nc;
     return DMX_OK;
 }
 
-// The pipeline counters (dmx_internal.h) with the sharded lists' totals (records kept, over
-// every shard) folded into their old slots: cnt[4 + r] windows, cnt[10 + r] verified windows,
-// cnt[12 + r] screen tasks, cnt[6 + 2r + l] candidates.  *ovf: flag bits of overflowed lists
-// (4 windows / tasks, 8 candidates).
+// The pipeline counters (dmx_device.h CounterSlot) with the sharded lists' totals (records kept,
+// over every shard) folded into their slots.  *ovf: flag bits of overflowed lists.
 hipError_t read_counters(Ctx* c, uint32_t* cnt, int* ovf) {
-    hipError_t e = hipMemcpy(cnt, c->d_counters, 32 * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    hipError_t e =
+        hipMemcpy(cnt, c->d_counters.p, kCntCount * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return e;
     std::vector<uint32_t> sh((size_t)kShLists * kShards * kShardStride);
-    e = hipMemcpy(sh.data(), c->d_shard, sh.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    e = hipMemcpy(sh.data(), c->d_shard.p, sh.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return e;
+    // each list of ShardList: where its run of lists starts, the slot that takes the first of
+    // them, its capacity and the flag an overflow raises
+    const struct {
+        int first, slot;
+        size_t cap;
+        int flag;
+    } lists[] = {{kShWin, kCntWindows, win_cap(c), kFlagWindows},
+                 {kShWin2, kCntVerified, win_cap(c), kFlagWindows},
+                 {kShTasks, kCntTasks, task_cap(c), kFlagWindows},
+                 {kShCand, kCntCands, cand_cap(c), kFlagCands},
+                 {kShFtask, kCntFtasks, win_cap(c), kFlagWindows}};
+    constexpr int n_lists = (int)(sizeof lists / sizeof *lists);
+    static_assert(kShWin == 0 && kShWin < kShWin2 && kShWin2 < kShTasks && kShTasks < kShCand &&
+                      kShCand < kShFtask && kShFtask < kShLists,
+                  "lists[] follows ShardList in ascending order");
     int o = 0;
     for (int x = 0; x < kShLists; ++x) {
-        const bool cand = x >= kShCand && x < kShFtask;
-        const uint32_t scap = (uint32_t)((cand ? c->cand_cap : x >= kShFtask ? c->ftask_cap
-                                          : x >= kShTasks ? c->task_cap : c->win_cap) /
-                                         kShards);
+        int k = 0;
+        while (k + 1 < n_lists && x >= lists[k + 1].first) ++k;
+        const uint32_t scap = (uint32_t)(lists[k].cap / kShards);
         uint64_t t = 0;
         for (int s = 0; s < kShards; ++s) {
             const uint32_t v = sh[(size_t)(x * kShards + s) * kShardStride];
             t += std::min(v, scap);
-            if (v > scap) o |= cand ? 8 : 4;
+            if (v > scap) o |= lists[k].flag;
         }
-        const int slot = x < kShWin2 ? 4 + x : x < kShTasks ? 10 + (x - kShWin2)
-                       : x < kShCand ? 12 + (x - kShTasks) : x < kShFtask ? 6 + (x - kShCand)
-                       : 14 + (x - kShFtask);
-        cnt[slot] = (uint32_t)t;
+        cnt[lists[k].slot + (x - lists[k].first)] = (uint32_t)t;
     }
     if (ovf) *ovf = o;
     return hipSuccess;
 }
 
-int grow_cands(Ctx* c) {
-    const size_t want = c->cand_cap * 2;
-    int rc;
-    for (int r = 0; r < 2; ++r)
-        for (int l = 0; l < 2; ++l) {
-            if ((rc = dev_alloc(c, &c->d_cand[r][l], want))) return rc;
-        }
-    c->cand_cap = want;
-    return DMX_OK;
-}
-
-int grow_windows(Ctx* c) {
-    const size_t want = c->win_cap * 2;
-    int rc;
-    if ((rc = dev_alloc(c, &c->d_win, want))) return rc;
-    if ((rc = dev_alloc(c, &c->d_win2, want))) return rc;
-    if ((rc = dev_alloc(c, &c->d_tasks, 4 * want))) return rc;
-    if ((rc = dev_alloc(c, &c->d_ftask, want))) return rc;
-    c->win_cap = want;
-    c->task_cap = 4 * want;
-    c->ftask_cap = want;
-    return DMX_OK;
-}
-
-int grow_clusters(Ctx* c) {
-    const size_t want = c->cl_cap * 2;
-    int rc;
-    for (int r = 0; r < 2; ++r) {
-        if ((rc = dev_alloc(c, &c->d_cl[r], want))) return rc;
-        if ((rc = dev_alloc(c, &c->d_outc[r], want))) return rc;
-    }
-    c->cl_cap = want;
-    return DMX_OK;
-}
+// An overflowed list doubles (exec_checked).
+int grow_cands(Ctx* c) { return reserve_cands(c, cand_cap(c) * 2); }
+int grow_windows(Ctx* c) { return reserve_windows(c, win_cap(c) * 2); }
+int grow_clusters(Ctx* c) { return reserve_clusters(c, cl_cap(c) * 2); }
 
 }  // namespace
 
@@ -287,12 +238,10 @@ PanelReach panel_reach(const HostPanel& hp, const DevPanel& dp) {
 int reset_counts(Ctx* c) {
     CK(hipSetDevice(c->device));
     const size_t nc = counts_size(c);
-    if (c->n_counts != nc || !c->d_counts) {
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_counts, nc))) return rc;
-        c->n_counts = nc;
-    }
-    CK(hipMemsetAsync(c->d_counts, 0, nc * sizeof(unsigned long long), c->stream));
+    c->n_counts = 0;   // until there is room (ensure_pipeline)
+    CK(c->d_counts.reserve(nc));
+    c->n_counts = nc;
+    CK(hipMemsetAsync(c->d_counts.p, 0, nc * sizeof(unsigned long long), c->stream));
     CK(hipStreamSynchronize(c->stream));
     c->counts_reduced = false;
     return DMX_OK;
@@ -301,14 +250,11 @@ int reset_counts(Ctx* c) {
 int views_reserve(Ctx* c, size_t n) {
     CK(hipSetDevice(c->device));
     ++c->view_gen;   // the list is about to change: an earlier exec's items are no longer d_views
-    if (!c->d_view_n) CK(hipMalloc((void**)&c->d_view_n, sizeof(uint32_t)));
-    if (c->view_alloc < n || !c->d_views) {
+    CK(c->d_view_n.reserve(1));
+    if (c->d_views.cap < std::max<size_t>(n, 1)) {
         // the last exec may still read the old list
         CK(hipStreamSynchronize(c->stream));
-        int rc;
-        c->view_alloc = 0;
-        if ((rc = dev_alloc(c, &c->d_views, n))) return rc;
-        c->view_alloc = std::max<size_t>(n, 1);
+        CK(c->d_views.reserve(n));
     }
     return DMX_OK;
 }
@@ -349,50 +295,45 @@ int dmx_open(int device, dmx_ctx** out) {
     c->screen_v1 = env_on("DMX_SCREEN_V1");   // A/B: the unpacked index screen
     if (hipSetDevice(device) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
+        dmx_close(c);
         return DMX_E_HIP;
     }
-    for (auto& e : c->ev) hipEventCreate(&e);
+    hipError_t e = hipSuccess;
+    bool nomem = false;   // which of the two failed: an event, or an allocation
+    for (auto& ev : c->ev)
+        if (e == hipSuccess) e = hipEventCreate(&ev);
+    const auto room = [&](auto& buf, size_t n) {
+        if (e == hipSuccess && (e = buf.reserve(n)) != hipSuccess) nomem = true;
+    };
     for (int r = 0; r < 2; ++r) {
-        hipMalloc((void**)&c->d_panel[r], sizeof(DevPanel));
-        hipMalloc((void**)&c->d_pieces[r], sizeof(DevPieces));
+        room(c->d_panel[r], 1);
+        room(c->d_pieces[r], 1);
     }
-    hipMalloc((void**)&c->d_counters, 32 * sizeof(uint32_t));
-    hipMalloc((void**)&c->d_shard, kShLists * kShards * kShardStride * sizeof(uint32_t));
+    room(c->d_counters, kCntCount);
+    room(c->d_shard, (size_t)kShLists * kShards * kShardStride);
+    if (e != hipSuccess) {
+        dmx_close(c);   // what was made so far goes with the context
+        return nomem ? DMX_E_NOMEM : DMX_E_HIP;
+    }
     *out = c;
     return DMX_OK;
 }
 
+// What has an order: the device's work ends, the feature states and the communicator go, then
+// the events and streams.  Every device buffer is freed with the context that owns it.
 void dmx_close(dmx_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
+    if (c->stream) hipStreamSynchronize(c->stream);
     chop_release(c);
     pd_release(c);
     lg_release(c);
     comm_release(c);
-    void* bufs[] = {c->d_seq_alloc, c->d_nmask_alloc,     c->d_offs,     c->d_lens,      c->d_res,
-                    c->d_winner[0], c->d_winner[1], c->d_origin[0], c->d_origin[1], c->d_lb[0], c->d_lb[1], c->d_cl[0],
-                    c->d_cl[1],     c->d_outc[0],   c->d_outc[1],  c->d_items, c->d_win, c->d_win2, c->d_linked, c->d_tasks, c->d_counters, c->d_shard,
-                    c->d_counts,    c->d_panel[0],  c->d_panel[1], c->d_pieces[0], c->d_pieces[1],
-                    c->d_ftask, c->d_pieces_flat, c->d_cells[0], c->d_cells[1], c->d_cells[2],
-                    c->d_cells[3], c->d_ends[0], c->d_ends[1], c->d_panel_all[0],
-                    c->d_panel_all[1], c->d_views, c->d_view_n, c->d_item_src};
-    for (void* b : bufs)
-        if (b) hipFree(b);
-    for (int r = 0; r < 2; ++r)
-        for (int l = 0; l < 2; ++l) {
-            if (c->d_cand[r][l]) hipFree(c->d_cand[r][l]);
-        }
-    void* alt[] = {c->alt.seq_alloc, c->alt.nmask_alloc, c->alt.offs, c->alt.lens, c->alt.res,
-                   c->alt.exc, c->d_exc};
-    for (void* b : alt)
-        if (b) hipFree(b);
     for (auto& e : c->ev)
         if (e) hipEventDestroy(e);
     if (c->cstream) hipStreamDestroy(c->cstream);
     if (c->dstream) hipStreamDestroy(c->dstream);
-    hipStreamDestroy(c->stream);
+    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -879,9 +820,9 @@ static int set_panel_impl(dmx_ctx* c, int round, const char* const* seqs, const 
     }
     c->band_wide[round] = kkmax > 5;   // list 1 (costs 4..kk): 11 diagonals cover kk <= 5
     CK(hipSetDevice(c->device));
-    CK(hipMemcpy(c->d_panel[round], &dp, sizeof(dp), hipMemcpyHostToDevice));
+    CK(hipMemcpy(c->d_panel[round].p, &dp, sizeof(dp), hipMemcpyHostToDevice));
     if (hp.piece_step)
-        CK(hipMemcpy(c->d_pieces[round], &hp.pieces, sizeof(DevPieces), hipMemcpyHostToDevice));
+        CK(hipMemcpy(c->d_pieces[round].p, &hp.pieces, sizeof(DevPieces), hipMemcpyHostToDevice));
     return DMX_OK;
 }
 
@@ -994,15 +935,14 @@ static int set_panel_ends(dmx_ctx* c, int round, const char* const* seqs, const 
     c->band_ok[round] = band_ok;
     c->band_wide[round] = kkmax > 5;
     CK(hipSetDevice(c->device));
-    CK(hipMemcpy(c->d_panel[round], dp.get(), sizeof(DevPanel), hipMemcpyHostToDevice));
+    CK(hipMemcpy(c->d_panel[round].p, dp.get(), sizeof(DevPanel), hipMemcpyHostToDevice));
     if (hp.piece_step)
-        CK(hipMemcpy(c->d_pieces[round], &hp.pieces, sizeof(DevPieces), hipMemcpyHostToDevice));
+        CK(hipMemcpy(c->d_pieces[round].p, &hp.pieces, sizeof(DevPieces), hipMemcpyHostToDevice));
     if (de->n) {
-        if (!c->d_ends[round]) CK(hipMalloc((void**)&c->d_ends[round], sizeof(DevEnds)));
-        if (!c->d_panel_all[round])
-            CK(hipMalloc((void**)&c->d_panel_all[round], sizeof(DevPanel)));
-        CK(hipMemcpy(c->d_ends[round], de.get(), sizeof(DevEnds), hipMemcpyHostToDevice));
-        CK(hipMemcpy(c->d_panel_all[round], all.get(), sizeof(DevPanel), hipMemcpyHostToDevice));
+        CK(c->d_ends[round].reserve(1));
+        CK(c->d_panel_all[round].reserve(1));
+        CK(hipMemcpy(c->d_ends[round].p, de.get(), sizeof(DevEnds), hipMemcpyHostToDevice));
+        CK(hipMemcpy(c->d_panel_all[round].p, all.get(), sizeof(DevPanel), hipMemcpyHostToDevice));
     }
     return DMX_OK;
 }
@@ -1049,6 +989,21 @@ int dmx_pack(const uint8_t* ascii, const uint64_t* offsets, const uint32_t* lens
 
 namespace {
 
+// Room in `set` for a batch of `words` packed words between the guards.  New buffers are zeroed
+// whole (the guards stay zero from then on) and start empty.
+int reserve_words(Ctx* c, InputSet& set, size_t words) {
+    const size_t total = words + 2 * kGuardWords;
+    if (min_cap(set.seq, set.nmask) >= total) return DMX_OK;
+    set.n_words = 0;
+    const hipError_t e1 = set.seq.reserve(total), e2 = set.nmask.reserve(total);
+    derive_inputs(c);
+    CK(e1);
+    CK(e2);
+    CK(hipMemsetAsync(set.seq.p, 0, total * 4, c->stream));
+    CK(hipMemsetAsync(set.nmask.p, 0, total * 4, c->stream));
+    return DMX_OK;
+}
+
 // Mask words [mw0, mw0 + nmw) of the caller's batch into the resident set's d_nmask on stream s:
 // a copy of the dense bitmap, or zero-fill + a scatter of the exceptions in that range (sorted
 // by index, so the range is one binary search).  The exceptions are staged in the set's d_exc.
@@ -1062,14 +1017,10 @@ int upload_mask(Ctx* c, const MaskSrc& m, size_t mw0, size_t nmw, hipStream_t s)
     const uint32_t* hi = std::lower_bound(lo, m.idx + m.n, (uint32_t)(mw0 + nmw));
     const size_t n = (size_t)(hi - lo), first = (size_t)(lo - m.idx);
     if (!n) return DMX_OK;
-    if (c->exc_cap < n || !c->d_exc) {
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_exc, 2 * n))) return rc;
-        c->exc_cap = n;
-    }
-    CK(hipMemcpyAsync(c->d_exc, m.idx + first, n * 4, hipMemcpyHostToDevice, s));
-    CK(hipMemcpyAsync(c->d_exc + n, m.val + first, n * 4, hipMemcpyHostToDevice, s));
-    return launch_mask_scatter(c->d_nmask, c->d_exc, (uint32_t)n, (uint32_t)mw0, s);
+    CK(c->in.exc.reserve(2 * n));
+    CK(hipMemcpyAsync(c->in.exc.p, m.idx + first, n * 4, hipMemcpyHostToDevice, s));
+    CK(hipMemcpyAsync(c->in.exc.p + n, m.val + first, n * 4, hipMemcpyHostToDevice, s));
+    return launch_mask_scatter(c->d_nmask, c->in.exc.p, (uint32_t)n, (uint32_t)mw0, s);
 }
 
 int load_impl(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& mask, const uint64_t* offsets,
@@ -1087,35 +1038,23 @@ int load_impl(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& mask, const uint
     }
     CK(hipSetDevice(c->device));
     int rc;
-    if (c->cap_words < n_words || !c->d_seq_alloc) {
-        const size_t total = n_words + 2 * kGuardWords;
-        if ((rc = dev_alloc(c, &c->d_seq_alloc, total))) return rc;
-        if ((rc = dev_alloc(c, &c->d_nmask_alloc, total))) return rc;
-        CK(hipMemsetAsync(c->d_seq_alloc, 0, total * 4, c->stream));
-        CK(hipMemsetAsync(c->d_nmask_alloc, 0, total * 4, c->stream));
-        c->d_seq = c->d_seq_alloc + kGuardWords;
-        c->d_nmask = c->d_nmask_alloc + kGuardWords;
-        c->cap_words = n_words;
-    }
+    if ((rc = reserve_words(c, c->in, n_words))) return rc;
     // the mask has 1 bit per nt: only its first half (of n_words words) carries data
     const size_t nmw = std::min(n_words, (n_words + 1) / 2 + 2);
-    if (c->d_seq_alloc && c->n_words > n_words)   // stale tail of a longer batch: guard zero
-        CK(hipMemsetAsync(c->d_seq + n_words, 0, (c->n_words - n_words) * 4, c->stream));
-    if (c->d_nmask_alloc && c->n_words > nmw)
-        CK(hipMemsetAsync(c->d_nmask + nmw, 0, (std::min(c->n_words, c->cap_words) - nmw) * 4,
+    if (c->in.n_words > n_words)   // stale tail of a longer batch: guard zero
+        CK(hipMemsetAsync(c->d_seq + n_words, 0, (c->in.n_words - n_words) * 4, c->stream));
+    if (c->in.n_words > nmw)
+        CK(hipMemsetAsync(c->d_nmask + nmw, 0, (std::min(c->in.n_words, c->in.cap_words()) - nmw) * 4,
                           c->stream));
-    if (!c->d_offs || c->in_cap_reads < n_reads) {
-        if ((rc = dev_alloc(c, &c->d_offs, n_reads))) return rc;
-        if ((rc = dev_alloc(c, &c->d_lens, n_reads))) return rc;
-        c->in_cap_reads = n_reads;
-    }
+    CK(c->in.offs.reserve(n_reads));
+    CK(c->in.lens.reserve(n_reads));
     c->n_reads = n_reads;
-    c->n_words = n_words;
+    c->in.n_words = n_words;
     CK(hipMemcpyAsync(c->d_seq, seq2b, n_words * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = upload_mask(c, mask, 0, nmw, c->stream))) return rc;
     if (n_reads) {
-        CK(hipMemcpyAsync(c->d_offs, offsets, n_reads * 8, hipMemcpyHostToDevice, c->stream));
-        CK(hipMemcpyAsync(c->d_lens, lens, n_reads * 4, hipMemcpyHostToDevice, c->stream));
+        CK(hipMemcpyAsync(c->in.offs.p, offsets, n_reads * 8, hipMemcpyHostToDevice, c->stream));
+        CK(hipMemcpyAsync(c->in.lens.p, lens, n_reads * 4, hipMemcpyHostToDevice, c->stream));
     }
     CK(hipStreamSynchronize(c->stream));
     c->executed = false;
@@ -1265,7 +1204,7 @@ static int run_round(dmx_ctx* c, int round, hipStream_t st) {
     if (c->panel[round].n > 0) {
         if ((rc = launch_round(c, round, st))) return rc;
     } else {   // restricted adapters only: no screen, no scan; the stage times read as 0
-        for (int e = 0; e < 3; ++e) CK(hipEventRecord(c->ev[3 * round + e], st));
+        for (int k : {kEvRound, kEvScan, kEvResolve}) CK(hipEventRecord(c->ev[ev_of(k, round)], st));
     }
     return c->ends_n[round] ? launch_ends(c, round, st) : DMX_OK;
 }
@@ -1288,10 +1227,10 @@ int dmx_exec(dmx_ctx* c) {
     int rc = ensure_pipeline(c);
     if (rc) return rc;
     hipStream_t st = c->stream;
-    CK(hipEventRecord(c->ev[8], st));
-    CK(hipMemsetAsync(c->d_counters, 0, 32 * sizeof(uint32_t), st));
-    CK(hipMemsetAsync(c->d_shard, 0, kShLists * kShards * kShardStride * sizeof(uint32_t), st));
-    CK(hipMemsetAsync(c->d_counts, 0, c->n_counts * sizeof(unsigned long long), st));
+    CK(hipEventRecord(c->ev[kEvExec], st));
+    CK(hipMemsetAsync(c->d_counters.p, 0, kCntCount * sizeof(uint32_t), st));
+    CK(hipMemsetAsync(c->d_shard.p, 0, kShLists * kShards * kShardStride * sizeof(uint32_t), st));
+    CK(hipMemsetAsync(c->d_counts.p, 0, c->n_counts * sizeof(unsigned long long), st));
     c->counts_reduced = false;
     // A panel whose accepted matches can score <= 0 keeps one winner per orientation:
     // ReverseComplementer compares the two orientations' best scores with "no match" = 0, so
@@ -1301,12 +1240,12 @@ int dmx_exec(dmx_ctx* c) {
                             c->panel[r].nonpos;
     const size_t slots0 = c->mode == DMX_MODE_LINKED ? c->n_reads * (size_t)c->panel[0].n
                                                      : round0_items(c) * (c->orient_slot[0] ? 2 : 1);
-    CK(hipMemsetAsync(c->d_winner[0], 0xFF, slots0 * sizeof(unsigned long long), st));
+    CK(hipMemsetAsync(c->d_winner[0].p, 0xFF, slots0 * sizeof(unsigned long long), st));
     if ((rc = prepare_flat(c, st))) return rc;
     if ((rc = run_round(c, 0, st))) return rc;
     if ((rc = launch_finalize(c, 0, st))) return rc;
     if (c->mode != DMX_MODE_SINGLE) {
-        CK(hipMemsetAsync(c->d_winner[1], 0xFF, c->item_cap * (c->orient_slot[1] ? 2 : 1) *
+        CK(hipMemsetAsync(c->d_winner[1].p, 0xFF, c->item_cap * (c->orient_slot[1] ? 2 : 1) *
                                                      sizeof(unsigned long long), st));
         if ((rc = run_round(c, 1, st))) return rc;
         if ((rc = launch_finalize(c, 1, st))) return rc;
@@ -1337,7 +1276,7 @@ int dmx_fetch(dmx_ctx* c, dmx_result* out) {
     }
     CK(hipSetDevice(c->device));
     if (c->exec_items)   // one result per item of round 0: reads, or the views of a view run
-        CK(hipMemcpyAsync(out, c->d_res, c->exec_items * sizeof(dmx_result),
+        CK(hipMemcpyAsync(out, c->in.res.p, c->exec_items * sizeof(dmx_result),
                           hipMemcpyDeviceToHost, c->stream));
     CK(hipStreamSynchronize(c->stream));
     return DMX_OK;
@@ -1346,7 +1285,7 @@ int dmx_fetch(dmx_ctx* c, dmx_result* out) {
 int dmx_set_views(dmx_ctx* c, const uint32_t* read, const int32_t* start, const int32_t* stop,
                   const uint8_t* strand, size_t n_views) {
     if (!c || (n_views && (!read || !start || !stop || !strand))) return DMX_E_INVALID;
-    if (!c->d_seq || !c->d_lens || c->chunked || c->h_lens.size() != c->n_reads) {
+    if (!c->d_seq || !c->in.lens.p || c->chunked || c->h_lens.size() != c->n_reads) {
         c->err = "dmx_set_views: no resident batch (dmx_load first)";
         return DMX_E_STATE;
     }
@@ -1382,9 +1321,9 @@ int dmx_set_views(dmx_ctx* c, const uint32_t* read, const int32_t* start, const 
     }
     const uint32_t nv = (uint32_t)n_views;
     if (n_views)
-        CK(hipMemcpyAsync(c->d_views, v.data(), n_views * sizeof(ItemView), hipMemcpyHostToDevice,
+        CK(hipMemcpyAsync(c->d_views.p, v.data(), n_views * sizeof(ItemView), hipMemcpyHostToDevice,
                           c->stream));
-    CK(hipMemcpyAsync(c->d_view_n, &nv, sizeof nv, hipMemcpyHostToDevice, c->stream));
+    CK(hipMemcpyAsync(c->d_view_n.p, &nv, sizeof nv, hipMemcpyHostToDevice, c->stream));
     CK(hipStreamSynchronize(c->stream));
     c->n_views = n_views;
     c->views_on = true;
@@ -1407,7 +1346,7 @@ int dmx_views_fetch(dmx_ctx* c, uint32_t* read, int32_t* start, int32_t* stop,
         CK(hipSetDevice(c->device));
         std::vector<ItemView> v(n);
         const std::vector<uint32_t>& lens = c->h_lens;
-        CK(hipMemcpyAsync(v.data(), c->d_views, n * sizeof(ItemView), hipMemcpyDeviceToHost,
+        CK(hipMemcpyAsync(v.data(), c->d_views.p, n * sizeof(ItemView), hipMemcpyDeviceToHost,
                           c->stream));
         CK(hipStreamSynchronize(c->stream));
         for (size_t k = 0; k < n; ++k) {
@@ -1433,7 +1372,7 @@ int dmx_counts(dmx_ctx* c, uint64_t* out, size_t n_out) {
         return DMX_E_INVALID;
     }
     CK(hipSetDevice(c->device));
-    CK(hipMemcpyAsync(out, c->d_counts, c->n_counts * 8, hipMemcpyDeviceToHost, c->stream));
+    CK(hipMemcpyAsync(out, c->d_counts.p, c->n_counts * 8, hipMemcpyDeviceToHost, c->stream));
     CK(hipStreamSynchronize(c->stream));
     return (int)c->n_counts;
 }
@@ -1448,59 +1387,58 @@ int dmx_stats(dmx_ctx* c, float* stage_ms, int n_stage, uint64_t* counts, int n_
     CK(hipSetDevice(c->device));
     CK(hipStreamSynchronize(c->stream));
     const int rounds = c->mode == DMX_MODE_SINGLE ? 1 : 2;
-    float t[19] = {};
+    float t[kStCount] = {};
+    const auto span = [&](int slot, int from, int to) {
+        hipEventElapsedTime(&t[slot], c->ev[from], c->ev[to]);
+    };
     for (int r = 0; r < rounds; ++r) {
-        hipEventElapsedTime(&t[3 * r + 0], c->ev[3 * r + 0], c->ev[3 * r + 1]);
-        hipEventElapsedTime(&t[3 * r + 1], c->ev[3 * r + 1], c->ev[3 * r + 2]);
-        hipEventElapsedTime(&t[3 * r + 2], c->ev[3 * r + 2], c->ev[6 + r]);
-        const bool f = c->panel[r].filter && !(c->mode == DMX_MODE_LINKED);
-        if (f) {
-            hipEventElapsedTime(&t[7 + 2 * r], c->ev[3 * r + 0], c->ev[9 + 2 * r]);
-            hipEventElapsedTime(&t[8 + 2 * r], c->ev[9 + 2 * r], c->ev[10 + 2 * r]);
-            hipEventElapsedTime(&t[11 + 2 * r], c->ev[10 + 2 * r], c->ev[13 + r]);
-            hipEventElapsedTime(&t[12 + 2 * r], c->ev[13 + r], c->ev[3 * r + 1]);
+        span(st_round(r, kStScan), ev_of(kEvRound, r), ev_of(kEvScan, r));
+        span(st_round(r, kStResolve), ev_of(kEvScan, r), ev_of(kEvResolve, r));
+        span(st_round(r, kStFinal), ev_of(kEvResolve, r), ev_of(kEvFinal, r));
+        if (c->panel[r].filter && c->mode != DMX_MODE_LINKED) {
+            span(st_filter(r), ev_of(kEvRound, r), ev_of(kEvFilter, r));
+            span(st_verify(r), ev_of(kEvFilter, r), ev_of(kEvVerify, r));
+            span(st_screen(r), ev_of(kEvVerify, r), ev_of(kEvScreen, r));
+            span(st_wscan(r), ev_of(kEvScreen, r), ev_of(kEvScan, r));
             if (c->panel[r].piece_step)   // the piece screen's share of the filter stage
-                hipEventElapsedTime(&t[15 + r], c->ev[3 * r + 0], c->ev[15 + r]);
+                span(st_pieces(r), ev_of(kEvRound, r), ev_of(kEvPieces, r));
         }
+        if (c->ends_n[r]) span(st_ends(r), ev_of(kEvEndsIn, r), ev_of(kEvEndsOut, r));
     }
-    hipEventElapsedTime(&t[6], c->ev[8], c->ev[6 + rounds - 1]);
-    for (int r = 0; r < rounds; ++r)
-        if (c->ends_n[r]) hipEventElapsedTime(&t[17 + r], c->ev[17 + 2 * r], c->ev[18 + 2 * r]);
-    for (int i = 0; i < n_stage && i < 19; ++i) stage_ms[i] = t[i];
-    uint32_t cnt[32];
+    span(kStTotal, kEvExec, ev_of(kEvFinal, rounds - 1));
+    for (int i = 0; i < n_stage && i < kStCount; ++i) stage_ms[i] = t[i];
+    uint32_t cnt[kCntCount];
     int list_ovf = 0;
     CK(read_counters(c, cnt, &list_ovf));
     if (getenv("DMX_DEBUG_STATS"))
         fprintf(stderr,
                 "dmx stats: filter tasks %u %u windows raw %u %u verified %u %u screened tasks "
                 "%u %u (by 3' cells only %u %u) cand %u %u %u %u\n",
-                cnt[14], cnt[15], cnt[4], cnt[5], cnt[10], cnt[11], cnt[12], cnt[13], cnt[19],
-                cnt[23], cnt[6], cnt[7], cnt[8], cnt[9]);
+                cnt[kCntFtasks], cnt[kCntFtasks + 1], cnt[kCntWindows], cnt[kCntWindows + 1],
+                cnt[kCntVerified], cnt[kCntVerified + 1], cnt[kCntTasks], cnt[kCntTasks + 1],
+                cnt[cnt_diag(0, kDiagEndOnly)], cnt[cnt_diag(1, kDiagEndOnly)], cnt[kCntCands],
+                cnt[kCntCands + 1], cnt[kCntCands + 2], cnt[kCntCands + 3]);
     if (counts) {
-        const bool b0 = c->band_ok[0] && !c->force_ring, b1 = c->band_ok[1] && !c->force_ring;
-        const uint64_t v[18] = {cnt[0],
-                                cnt[1],
-                                c->panel[0].verify ? cnt[10] : cnt[4],
-                                c->panel[1].verify ? cnt[11] : cnt[5],
-                                b0 ? (uint64_t)cnt[6] + cnt[7] : cnt[16],
-                                b1 ? (uint64_t)cnt[8] + cnt[9] : cnt[20],
-                                cnt[17],
-                                cnt[21],
-                                cnt[4],
-                                cnt[5],
-                                cnt[12],
-                                cnt[13],
-                                cnt[14],
-                                cnt[15],
-                                cnt[28],
-                                cnt[29],
-                                cnt[30],
-                                cnt[31]};
+        // per round: the pairs of include/dmx.h's list, in its order
+        uint64_t v[18];
+        for (int r = 0; r < 2; ++r) {
+            v[0 + r] = cnt[kCntClusters + r];
+            v[2 + r] = cnt[(c->panel[r].verify ? kCntVerified : kCntWindows) + r];
+            v[4 + r] = band_round(c, r)
+                           ? (uint64_t)cnt[kCntCands + 2 * r] + cnt[kCntCands + 2 * r + 1]
+                           : cnt[cnt_diag(r, kDiagResolved)];
+            v[6 + r] = cnt[cnt_diag(r, kDiagTraces)];
+            v[8 + r] = cnt[kCntWindows + r];
+            v[10 + r] = cnt[kCntTasks + r];
+            v[12 + r] = cnt[kCntFtasks + r];
+            v[14 + r] = cnt[kCntEndsDp + r];
+            v[16 + r] = cnt[kCntEndsSeen + r];
+        }
         for (int i = 0; i < n_counts && i < 18; ++i) counts[i] = v[i];
     }
     if (flags) {
-        int f = (int)cnt[3];
-        if (cnt[0] > c->cl_cap || cnt[1] > c->cl_cap) f |= 1;
+        int f = (int)cnt[kCntFlags];
+        if (cnt[kCntClusters] > cl_cap(c) || cnt[kCntClusters + 1] > cl_cap(c)) f |= kFlagClusters;
         f |= list_ovf;
         *flags = f;
     }
@@ -1515,10 +1453,10 @@ int dmx_debug_fetch(dmx_ctx* c, int what, int round, void* out, size_t cap_bytes
     }
     CK(hipSetDevice(c->device));
     CK(hipStreamSynchronize(c->stream));
-    uint32_t cnt[32];
+    uint32_t cnt[kCntCount];
     CK(read_counters(c, cnt, nullptr));
     if (what == DMX_DBG_FLAGS) {
-        if (cap_bytes >= 4) std::memcpy(out, &cnt[3], 4);
+        if (cap_bytes >= 4) std::memcpy(out, &cnt[kCntFlags], 4);
         return 4;
     }
     // every list is sharded: gather its shards (windows and tasks of round 1 share buffers with
@@ -1527,15 +1465,15 @@ int dmx_debug_fetch(dmx_ctx* c, int what, int round, void* out, size_t cap_bytes
     const char* base;
     size_t cap, rec;
     switch (what) {
-        case DMX_DBG_WINDOWS: slot = kShWin + round; base = (const char*)c->d_win; cap = c->win_cap; rec = sizeof(Window); break;
-        case DMX_DBG_VERIFIED: slot = kShWin2 + round; base = (const char*)c->d_win2; cap = c->win_cap; rec = sizeof(Window); break;
-        case DMX_DBG_TASKS: slot = kShTasks + round; base = (const char*)c->d_tasks; cap = c->task_cap; rec = sizeof(Window); break;
-        case DMX_DBG_CANDS0: slot = kShCand + 2 * round; base = (const char*)c->d_cand[round][0]; cap = c->cand_cap; rec = sizeof(Cand); break;
-        case DMX_DBG_CANDS1: slot = kShCand + 2 * round + 1; base = (const char*)c->d_cand[round][1]; cap = c->cand_cap; rec = sizeof(Cand); break;
+        case DMX_DBG_WINDOWS: slot = kShWin + round; base = (const char*)c->d_win.p; cap = win_cap(c); rec = sizeof(Window); break;
+        case DMX_DBG_VERIFIED: slot = kShWin2 + round; base = (const char*)c->d_win2.p; cap = win_cap(c); rec = sizeof(Window); break;
+        case DMX_DBG_TASKS: slot = kShTasks + round; base = (const char*)c->d_tasks.p; cap = task_cap(c); rec = sizeof(Window); break;
+        case DMX_DBG_CANDS0: slot = kShCand + 2 * round; base = (const char*)c->d_cand[round][0].p; cap = cand_cap(c); rec = sizeof(Cand); break;
+        case DMX_DBG_CANDS1: slot = kShCand + 2 * round + 1; base = (const char*)c->d_cand[round][1].p; cap = cand_cap(c); rec = sizeof(Cand); break;
         default: return DMX_E_INVALID;
     }
     uint32_t sh[kShards * kShardStride];
-    CK(hipMemcpy(sh, c->d_shard + slot * kShards * kShardStride, sizeof(sh),
+    CK(hipMemcpy(sh, c->d_shard.p + slot * kShards * kShardStride, sizeof(sh),
                  hipMemcpyDeviceToHost));
     const size_t scap = cap / kShards;
     size_t done = 0;
@@ -1550,6 +1488,34 @@ int dmx_debug_fetch(dmx_ctx* c, int what, int round, void* out, size_t cap_bytes
 
 namespace {
 
+// dmx_exec until every list held its records: an overflowed list is grown and the pipeline run
+// again, never truncated (dmx_run, dmx_exec_checked).  `enqueued`, if any, runs once, after the
+// first dmx_exec of the call has been enqueued and before the host waits for it.  Synchronises.
+int exec_checked(dmx_ctx* c, const std::function<int()>& enqueued = nullptr) {
+    int rc;
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        if ((rc = dmx_exec(c))) return rc;
+        if (attempt == 0 && enqueued && (rc = enqueued())) return rc;
+        uint64_t cl[8];
+        int flags = 0;
+        float ms[7];
+        if ((rc = dmx_stats(c, ms, 7, cl, 8, &flags))) return rc;
+        if (flags & kFlagsInternal) {
+            c->err = (flags & kFlagTraceback)
+                         ? "internal: traceback left the exact window (please report)"
+                         : "internal: filter task invariant violated (please report)";
+            return DMX_E_STATE;
+        }
+        if (!(flags & kFlagsOverflow)) return DMX_OK;
+        if (attempt == 7) break;
+        if ((flags & kFlagClusters) && (rc = grow_clusters(c))) return rc;
+        if ((flags & kFlagWindows) && (rc = grow_windows(c))) return rc;
+        if ((flags & kFlagCands) && (rc = grow_cands(c))) return rc;
+    }
+    c->err = "candidate cluster buffer overflow";
+    return DMX_E_NOMEM;
+}
+
 // One chunk of a chunked dmx_run: reads [lo, hi) of the caller's dmx_pack batch, rebased.
 struct Chunk {
     size_t lo, hi, w0, words;
@@ -1557,25 +1523,12 @@ struct Chunk {
     size_t exc_lo, exc_n;   // its range of the sparse mask's exceptions
 };
 
-// The buffers of the resident batch (Ctx fields) <-> the second set.
+// The resident set <-> the second set.
 void swap_inputs(Ctx* c) {
-    std::swap(c->d_seq_alloc, c->alt.seq_alloc);
-    std::swap(c->d_nmask_alloc, c->alt.nmask_alloc);
-    std::swap(c->d_offs, c->alt.offs);
-    std::swap(c->d_lens, c->alt.lens);
-    std::swap(c->d_res, c->alt.res);
-    std::swap(c->cap_words, c->alt.cap_words);
-    std::swap(c->in_cap_reads, c->alt.cap_reads);
-    std::swap(c->res_cap, c->alt.res_cap);
-    std::swap(c->d_exc, c->alt.exc);
-    std::swap(c->exc_cap, c->alt.exc_cap);
-    std::swap(c->n_words, c->alt.n_words);
-    c->d_seq = c->d_seq_alloc + kGuardWords;
-    c->d_nmask = c->d_nmask_alloc + kGuardWords;
+    c->in.swap(c->alt);
+    derive_inputs(c);
 }
 
-// Upload one chunk into the current set on the copy stream (host-blocking for pageable
-// memory, while the compute stream keeps running), zeroing a longer previous chunk's tail.
 // Upload one chunk into the current set on the copy stream (asynchronous: the caller syncs
 // cstream before the set is used), zeroing a longer previous chunk's tail.  Offsets go up as the
 // caller gave them and are rebased on the device.
@@ -1585,18 +1538,18 @@ int upload_chunk(Ctx* c, const Chunk& k, const uint32_t* seq2b, const MaskSrc& m
     // the nmask words of a range (1 bit per nt: half as many); the rest of the buffer stays
     // zero (the guard)
     const auto mask_words = [](size_t w) { return std::min(w, (w + 1) / 2 + 2); };
-    const size_t nmw = mask_words(k.words), old_nmw = mask_words(c->n_words);
-    if (c->n_words > k.words)
-        CK(hipMemsetAsync(c->d_seq + k.words, 0, (c->n_words - k.words) * 4, s));
+    const size_t nmw = mask_words(k.words), old_nmw = mask_words(c->in.n_words);
+    if (c->in.n_words > k.words)
+        CK(hipMemsetAsync(c->d_seq + k.words, 0, (c->in.n_words - k.words) * 4, s));
     if (old_nmw > nmw) CK(hipMemsetAsync(c->d_nmask + nmw, 0, (old_nmw - nmw) * 4, s));
     CK(hipMemcpyAsync(c->d_seq, seq2b + k.w0, k.words * 4, hipMemcpyHostToDevice, s));
     int rc;
     if ((rc = upload_mask(c, mask, k.w0 / 2, nmw, s))) return rc;
     const size_t n = k.hi - k.lo;
-    CK(hipMemcpyAsync(c->d_offs, offsets + k.lo, n * 8, hipMemcpyHostToDevice, s));
-    if ((rc = launch_rebase_offsets(c->d_offs, (uint32_t)n, k.g0, s))) return rc;
-    CK(hipMemcpyAsync(c->d_lens, lens + k.lo, n * 4, hipMemcpyHostToDevice, s));
-    c->n_words = k.words;
+    CK(hipMemcpyAsync(c->in.offs.p, offsets + k.lo, n * 8, hipMemcpyHostToDevice, s));
+    if ((rc = launch_rebase_offsets(c->in.offs.p, (uint32_t)n, k.g0, s))) return rc;
+    CK(hipMemcpyAsync(c->in.lens.p, lens + k.lo, n * 4, hipMemcpyHostToDevice, s));
+    c->in.n_words = k.words;
     return DMX_OK;
 }
 
@@ -1618,22 +1571,15 @@ void parallel_ranges(size_t n, F fn) {
     for (auto& x : th) x.join();
 }
 
-int alloc_set(Ctx* c, size_t words, size_t reads) {
+// Room in `set` for chunks of up to `words` words and `reads` reads, and their results.
+int alloc_set(Ctx* c, InputSet& set, size_t words, size_t reads) {
+    if (set.cap_words() >= words && set.cap_reads() >= reads && set.res.cap >= reads)
+        return DMX_OK;
     int rc;
-    const size_t total = words + 2 * kGuardWords;
-    if ((rc = dev_alloc(c, &c->d_seq_alloc, total))) return rc;
-    if ((rc = dev_alloc(c, &c->d_nmask_alloc, total))) return rc;
-    CK(hipMemsetAsync(c->d_seq_alloc, 0, total * 4, c->stream));
-    CK(hipMemsetAsync(c->d_nmask_alloc, 0, total * 4, c->stream));
-    if ((rc = dev_alloc(c, &c->d_offs, reads))) return rc;
-    if ((rc = dev_alloc(c, &c->d_lens, reads))) return rc;
-    if ((rc = dev_alloc(c, &c->d_res, reads))) return rc;
-    c->d_seq = c->d_seq_alloc + kGuardWords;
-    c->d_nmask = c->d_nmask_alloc + kGuardWords;
-    c->cap_words = words;
-    c->in_cap_reads = reads;
-    c->res_cap = reads;
-    c->n_words = 0;
+    if ((rc = reserve_words(c, set, words))) return rc;
+    CK(set.offs.reserve(reads));
+    CK(set.lens.reserve(reads));
+    CK(set.res.reserve(reads));
     CK(hipStreamSynchronize(c->stream));
     return DMX_OK;
 }
@@ -1697,25 +1643,10 @@ int run_chunked(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& nmask,
     if (!c->cstream) CK(hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
     if (!c->dstream) CK(hipStreamCreateWithFlags(&c->dstream, hipStreamNonBlocking));
     int rc;
-    // both sets sized for the largest chunk; each set's capacities travel with its buffers
-    // (swap_inputs), apart from the pipeline's cap_reads
-    if (c->cap_words < maxw || c->in_cap_reads < maxn || c->res_cap < maxn || !c->d_offs ||
-        !c->d_res) {
-        if ((rc = alloc_set(c, maxw, maxn))) return rc;
-    }
-    if (c->alt.cap_words < maxw || c->alt.cap_reads < maxn || c->alt.res_cap < maxn ||
-        !c->alt.offs || !c->alt.res) {
-        swap_inputs(c);
-        rc = alloc_set(c, maxw, maxn);
-        swap_inputs(c);
-        if (rc) return rc;
-    }
-    for (int set = 0; set < 2 && maxe; ++set) {   // exception staging, sized before the loop
-        if (c->exc_cap < maxe || !c->d_exc) {
-            if ((rc = dev_alloc(c, &c->d_exc, 2 * maxe))) return rc;
-            c->exc_cap = maxe;
-        }
-        swap_inputs(c);
+    // both sets sized for the largest chunk (and its exception staging)
+    for (InputSet* set : {&c->in, &c->alt}) {
+        if ((rc = alloc_set(c, *set, maxw, maxn))) return rc;
+        if (maxe) CK(set->exc.reserve(2 * maxe));
     }
     c->n_reads = maxn;
     c->views_on = false;
@@ -1731,44 +1662,29 @@ int run_chunked(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& nmask,
     for (size_t i = 0; i < ch.size(); ++i) {
         const size_t n = ch[i].hi - ch[i].lo;
         c->n_reads = n;
-        int attempt = 0;
-        for (;; ++attempt) {
-            if ((rc = dmx_exec(c))) return rc;
-            // meanwhile: the next chunk into the other set, the previous chunk's results out
-            // (uploads on cstream and the download on dstream run in both directions at once;
-            // the other set's inputs and its result array are disjoint buffers)
-            if (attempt == 0) {
-                swap_inputs(c);
-                if (i + 1 < ch.size() &&
-                    (rc = upload_chunk(c, ch[i + 1], seq2b, nmask, offsets, lens)))
-                    return rc;
-                if (i > 0) {
-                    const size_t pn = ch[i - 1].hi - ch[i - 1].lo;
-                    CK(hipMemcpyAsync(out + ch[i - 1].lo, c->d_res, pn * sizeof(dmx_result),
-                                      hipMemcpyDeviceToHost, c->dstream));
+        // meanwhile: the next chunk into the other set, the previous chunk's results out
+        // (uploads on cstream and the download on dstream run in both directions at once;
+        // the other set's inputs and its result array are disjoint buffers)
+        const auto overlap = [&]() -> int {
+            int rc = DMX_OK;
+            swap_inputs(c);
+            if (i + 1 < ch.size()) rc = upload_chunk(c, ch[i + 1], seq2b, nmask, offsets, lens);
+            if (rc == DMX_OK && i > 0) {
+                const size_t pn = ch[i - 1].hi - ch[i - 1].lo;
+                const hipError_t e =
+                    hipMemcpyAsync(out + ch[i - 1].lo, c->in.res.p, pn * sizeof(dmx_result),
+                                   hipMemcpyDeviceToHost, c->dstream);
+                if (e != hipSuccess) {
+                    c->err = std::string("dmx_run: result download: ") + hipGetErrorString(e);
+                    rc = DMX_E_HIP;
                 }
-                swap_inputs(c);
             }
-            uint64_t cl[8];
-            int flags = 0;
-            float ms[7];
-            if ((rc = dmx_stats(c, ms, 7, cl, 8, &flags))) return rc;
-            if (flags & 18) {
-                c->err = (flags & 2) ? "internal: traceback left the exact window (please report)"
-                                     : "internal: filter task invariant violated (please report)";
-                return DMX_E_STATE;
-            }
-            if (!(flags & 13)) break;
-            if (attempt >= 7) {
-                c->err = "candidate cluster buffer overflow";
-                return DMX_E_NOMEM;
-            }
-            if ((flags & 1) && (rc = grow_clusters(c))) return rc;
-            if ((flags & 4) && (rc = grow_windows(c))) return rc;
-            if ((flags & 8) && (rc = grow_cands(c))) return rc;
-        }
+            swap_inputs(c);
+            return rc;
+        };
+        if ((rc = exec_checked(c, overlap))) return rc;
         part.assign(c->n_counts, 0);
-        CK(hipMemcpy(part.data(), c->d_counts, c->n_counts * 8, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(part.data(), c->d_counts.p, c->n_counts * 8, hipMemcpyDeviceToHost));
         if (total.size() != part.size()) total.assign(part.size(), 0);
         for (size_t x = 0; x < part.size(); ++x) total[x] += part[x];
         CK(hipStreamSynchronize(c->cstream));   // the next chunk is in, the previous one out
@@ -1779,10 +1695,10 @@ int run_chunked(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& nmask,
     swap_inputs(c);
     {
         const Chunk& k = ch.back();
-        CK(hipMemcpy(out + k.lo, c->d_res, (k.hi - k.lo) * sizeof(dmx_result),
+        CK(hipMemcpy(out + k.lo, c->in.res.p, (k.hi - k.lo) * sizeof(dmx_result),
                      hipMemcpyDeviceToHost));
     }
-    CK(hipMemcpy(c->d_counts, total.data(), total.size() * 8, hipMemcpyHostToDevice));
+    CK(hipMemcpy(c->d_counts.p, total.data(), total.size() * 8, hipMemcpyHostToDevice));
     c->counts_reduced = false;
     c->chunked = true;
     return DMX_OK;
@@ -1791,31 +1707,6 @@ int run_chunked(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& nmask,
 }  // namespace
 
 namespace {
-
-// dmx_exec until every list held its records: an overflowed list is grown and the pipeline run
-// again, never truncated (dmx_run's one-shot path, dmx_exec_checked).  Synchronises.
-int exec_checked(dmx_ctx* c) {
-    int rc;
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        if ((rc = dmx_exec(c))) return rc;
-        uint64_t cl[8];
-        int flags = 0;
-        float ms[7];
-        if ((rc = dmx_stats(c, ms, 7, cl, 8, &flags))) return rc;
-        if (flags & 18) {
-            c->err = (flags & 2) ? "internal: traceback left the exact window (please report)"
-                                 : "internal: filter task invariant violated (please report)";
-            return DMX_E_STATE;
-        }
-        if (!(flags & 13)) return DMX_OK;
-        // candidate overflow: retry with more room, never truncate
-        if ((flags & 1) && (rc = grow_clusters(c))) return rc;
-        if ((flags & 4) && (rc = grow_windows(c))) return rc;
-        if ((flags & 8) && (rc = grow_cands(c))) return rc;
-    }
-    c->err = "candidate cluster buffer overflow";
-    return DMX_E_NOMEM;
-}
 
 int run_impl(dmx_ctx* c, const uint32_t* seq2b, const MaskSrc& mask, const uint64_t* offsets,
              const uint32_t* lens, size_t n_words, size_t n_reads, dmx_result* out) {

@@ -715,25 +715,18 @@ __global__ __launch_bounds__(1024) void chop_views_scan_kernel(const uint32_t* c
 struct ChopState {
     ChopPanel host{};
     bool set = false;
-    ChopPanel* d_panel = nullptr;
-    dmx_chop_hit* d_hstage = nullptr;
-    dmx_chop_hit* d_hits = nullptr;
-    dmx_chop_seg* d_sstage = nullptr;
-    dmx_chop_seg* d_segs = nullptr;
-    size_t hit_cap = 0, seg_cap = 0;
-    uint32_t* d_nhit = nullptr;
-    uint32_t* d_nseg = nullptr;
-    size_t read_cap = 0;
-    uint32_t* d_blk = nullptr;
-    uint32_t* d_blkoff = nullptr;
-    size_t blk_cap = 0;
-    unsigned long long* d_ctr = nullptr;
-    uint32_t* d_ovf = nullptr;            // overflowing blocks (block, count), blk_cap entries
-    uint64_t* d_ovf_base = nullptr;       // chop_big_kernel: hit-list bases, scratch, counters
-    dmx_chop_hit* d_big = nullptr;
-    size_t big_cap = 0;
-    uint32_t* d_big_cnt = nullptr;
-    size_t big_blocks_cap = 0;
+    DevBuf<ChopPanel> d_panel;
+    DevBuf<dmx_chop_hit> d_hstage, d_hits;   // grown together (hit_cap)
+    DevBuf<dmx_chop_seg> d_sstage, d_segs;   // grown together (seg_cap)
+    DevBuf<uint32_t> d_nhit, d_nseg;         // one entry per read
+    DevBuf<uint32_t> d_blk, d_blkoff;        // 4 and 2 entries per block
+    DevBuf<unsigned long long> d_ctr;
+    DevBuf<uint32_t> d_ovf;                  // overflowing blocks (block, count), 2 per block
+    DevBuf<uint64_t> d_ovf_base;             // chop_big_kernel: hit-list bases, scratch, counters
+    DevBuf<dmx_chop_hit> d_big;              // two halves of d_big.cap / 2 hits
+    DevBuf<uint32_t> d_big_cnt;
+    size_t hit_cap() const { return min_cap(d_hstage, d_hits); }
+    size_t seg_cap() const { return min_cap(d_sstage, d_segs); }
     uint64_t n_hits = 0, n_segs = 0;
     size_t n_reads = 0;
     bool done = false;
@@ -748,11 +741,6 @@ struct ChopState {
 void chop_release(Ctx* c) {
     ChopState* s = c->chop;
     if (!s) return;
-    void* bufs[] = {s->d_panel, s->d_hstage, s->d_hits,    s->d_sstage, s->d_segs,
-                    s->d_nhit,  s->d_nseg,   s->d_blk,     s->d_blkoff, s->d_ctr,
-                    s->d_ovf,   s->d_ovf_base, s->d_big,   s->d_big_cnt};
-    for (void* b : bufs)
-        if (b) hipFree(b);
     for (auto& e : s->ev)
         if (e) hipEventDestroy(e);
     delete s;
@@ -777,15 +765,6 @@ namespace {
             return DMX_E_HIP;                                                              \
         }                                                                                  \
     } while (0)
-
-template <typename T>
-hipError_t dev_realloc(T** p, size_t count) {
-    if (*p) {
-        hipFree(*p);
-        *p = nullptr;
-    }
-    return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-}
 
 int iupac_bits(char ch) {
     switch (ch) {
@@ -895,8 +874,8 @@ extern "C" int dmx_chop_set(dmx_ctx* c, const char* const* primers, const int* p
     }
     CHOP_CK(hipSetDevice(c->device));
     ChopState* s = chop_state(c);
-    if (!s->d_panel) CHOP_CK(hipMalloc((void**)&s->d_panel, sizeof(ChopPanel)));
-    CHOP_CK(hipMemcpyAsync(s->d_panel, &P, sizeof(ChopPanel), hipMemcpyHostToDevice, c->stream));
+    CHOP_CK(s->d_panel.reserve(1));
+    CHOP_CK(hipMemcpyAsync(s->d_panel.p, &P, sizeof(ChopPanel), hipMemcpyHostToDevice, c->stream));
     CHOP_CK(hipStreamSynchronize(c->stream));
     bool hi = true, lo = true;
     for (int l = 0; l < P.n_labels; ++l) {
@@ -925,53 +904,43 @@ extern "C" int dmx_chop_exec(dmx_ctx* c, uint64_t* n_hits, uint64_t* n_segs) {
     CHOP_CK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     s->done = false;
-    if (!s->d_ctr) CHOP_CK(hipMalloc((void**)&s->d_ctr, 4 * sizeof(unsigned long long)));
-    if (s->read_cap < n || !s->d_nhit) {
-        CHOP_CK(dev_realloc(&s->d_nhit, n));
-        CHOP_CK(dev_realloc(&s->d_nseg, n));
-        s->read_cap = n;
+    CHOP_CK(s->d_ctr.reserve(4));
+    CHOP_CK(s->d_nhit.reserve(n));
+    CHOP_CK(s->d_nseg.reserve(n));
+    if (s->hit_cap() < 2 * n + 4096) {   // with room to spare: twice the least
+        CHOP_CK(s->d_hstage.reserve(4 * n + 4096));
+        CHOP_CK(s->d_hits.reserve(4 * n + 4096));
     }
-    if (s->hit_cap < 2 * n + 4096 || !s->d_hstage) {
-        const size_t cap = 4 * n + 4096;
-        CHOP_CK(dev_realloc(&s->d_hstage, cap));
-        CHOP_CK(dev_realloc(&s->d_hits, cap));
-        s->hit_cap = cap;
-    }
-    if (s->seg_cap < n + 4096 || !s->d_sstage) {
-        const size_t cap = 2 * n + 4096;
-        CHOP_CK(dev_realloc(&s->d_sstage, cap));
-        CHOP_CK(dev_realloc(&s->d_segs, cap));
-        s->seg_cap = cap;
+    if (s->seg_cap() < n + 4096) {
+        CHOP_CK(s->d_sstage.reserve(2 * n + 4096));
+        CHOP_CK(s->d_segs.reserve(2 * n + 4096));
     }
     unsigned long long ctr[4] = {0, 0, 0, 0};
     const uint32_t nb = (uint32_t)((n + kChopReads - 1) / kChopReads);
-    if (s->blk_cap < nb || !s->d_blk) {
-        CHOP_CK(dev_realloc(&s->d_blk, 4 * (size_t)nb));
-        CHOP_CK(dev_realloc(&s->d_blkoff, 2 * (size_t)nb));
-        CHOP_CK(dev_realloc(&s->d_ovf, 2 * (size_t)nb));
-        s->blk_cap = nb;
-    }
+    CHOP_CK(s->d_blk.reserve(4 * (size_t)nb));
+    CHOP_CK(s->d_blkoff.reserve(2 * (size_t)nb));
+    CHOP_CK(s->d_ovf.reserve(2 * (size_t)nb));
     size_t n_big = 0;
     CHOP_CK(bounds_reset(c, st));
     for (;;) {
-        CHOP_CK(hipMemsetAsync(s->d_ctr, 0, 4 * sizeof(unsigned long long), st));
+        CHOP_CK(hipMemsetAsync(s->d_ctr.p, 0, 4 * sizeof(unsigned long long), st));
         ChopArgs A;
         A.pk.seq = c->d_seq;
         A.pk.nmask = c->d_nmask;
         A.pk.bd = make_bounds(c, kKerChop);
-        A.offs = c->d_offs;
-        A.lens = c->d_lens;
+        A.offs = c->in.offs.p;
+        A.lens = c->in.lens.p;
         A.n_reads = (uint32_t)n;
-        A.panel = s->d_panel;
-        A.hits = s->d_hstage;
-        A.segs = s->d_sstage;
-        A.hit_cap = s->hit_cap;
-        A.seg_cap = s->seg_cap;
-        A.nhit = s->d_nhit;
-        A.nseg = s->d_nseg;
-        A.blk = s->d_blk;
-        A.ctr = s->d_ctr;
-        A.ovf = s->d_ovf;
+        A.panel = s->d_panel.p;
+        A.hits = s->d_hstage.p;
+        A.segs = s->d_sstage.p;
+        A.hit_cap = s->hit_cap();
+        A.seg_cap = s->seg_cap();
+        A.nhit = s->d_nhit.p;
+        A.nseg = s->d_nseg.p;
+        A.blk = s->d_blk.p;
+        A.ctr = s->d_ctr.p;
+        A.ovf = s->d_ovf.p;
         A.ovf_cap = nb;
         CHOP_CK(hipEventRecord(s->ev[0], st));
         if (nb) {
@@ -981,35 +950,29 @@ extern "C" int dmx_chop_exec(dmx_ctx* c, uint64_t* n_hits, uint64_t* n_segs) {
         }
         CHOP_CK(hipGetLastError());
         CHOP_CK(hipEventRecord(s->ev[1], st));
-        CHOP_CK(hipMemcpyAsync(ctr, s->d_ctr, 4 * sizeof(unsigned long long),
+        CHOP_CK(hipMemcpyAsync(ctr, s->d_ctr.p, 4 * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, st));
         CHOP_CK(hipStreamSynchronize(st));
         n_big = 0;
         if (ctr[2] & 1ull) {   // blocks whose hits overflowed the LDS list: redo them alone
             const size_t no = (size_t)std::min<unsigned long long>(ctr[3], nb);
             std::vector<uint32_t> ovf(2 * no);
-            CHOP_CK(hipMemcpy(ovf.data(), s->d_ovf, ovf.size() * 4, hipMemcpyDeviceToHost));
+            CHOP_CK(hipMemcpy(ovf.data(), s->d_ovf.p, ovf.size() * 4, hipMemcpyDeviceToHost));
             std::vector<uint64_t> base(no + 1, 0);
             for (size_t i = 0; i < no; ++i) base[i + 1] = base[i] + ovf[2 * i + 1];
-            if (s->big_cap < base[no] || !s->d_big) {
-                CHOP_CK(dev_realloc(&s->d_big, 2 * base[no]));
-                s->big_cap = base[no];
-            }
-            if (s->big_blocks_cap < no + 1 || !s->d_ovf_base) {
-                CHOP_CK(dev_realloc(&s->d_ovf_base, no + 1));
-                CHOP_CK(dev_realloc(&s->d_big_cnt, no + 1));
-                s->big_blocks_cap = no + 1;
-            }
-            CHOP_CK(hipMemcpyAsync(s->d_ovf_base, base.data(), (no + 1) * 8,
+            CHOP_CK(s->d_big.reserve(2 * base[no]));
+            CHOP_CK(s->d_ovf_base.reserve(no + 1));
+            CHOP_CK(s->d_big_cnt.reserve(no + 1));
+            CHOP_CK(hipMemcpyAsync(s->d_ovf_base.p, base.data(), (no + 1) * 8,
                                    hipMemcpyHostToDevice, st));
-            CHOP_CK(hipMemsetAsync(s->d_big_cnt, 0, (no + 1) * 4, st));
+            CHOP_CK(hipMemsetAsync(s->d_big_cnt.p, 0, (no + 1) * 4, st));
             set_kid(A.pk.bd, kKerChopBig);
             hipLaunchKernelGGL(chop_big_kernel, dim3((uint32_t)no), dim3(kChopBlock), 0, st, A,
-                               (const uint64_t*)s->d_ovf_base, s->d_big, s->d_big + s->big_cap,
-                               s->d_big_cnt);
+                               (const uint64_t*)s->d_ovf_base.p, s->d_big.p, s->d_big.p + s->d_big.cap / 2,
+                               s->d_big_cnt.p);
             CHOP_CK(hipGetLastError());
             CHOP_CK(hipEventRecord(s->ev[1], st));
-            CHOP_CK(hipMemcpyAsync(ctr, s->d_ctr, 4 * sizeof(unsigned long long),
+            CHOP_CK(hipMemcpyAsync(ctr, s->d_ctr.p, 4 * sizeof(unsigned long long),
                                    hipMemcpyDeviceToHost, st));
             CHOP_CK(hipStreamSynchronize(st));
             n_big = no;
@@ -1018,18 +981,16 @@ extern "C" int dmx_chop_exec(dmx_ctx* c, uint64_t* n_hits, uint64_t* n_segs) {
             c->err = "dmx_chop_exec: more than 2^32 hits in one batch";
             return DMX_E_UNSUPPORTED;
         }
-        if (ctr[0] > s->hit_cap || ctr[1] > s->seg_cap) {
-            if (ctr[0] > s->hit_cap) {
+        if (ctr[0] > s->hit_cap() || ctr[1] > s->seg_cap()) {
+            if (ctr[0] > s->hit_cap()) {
                 const size_t cap = ctr[0] + ctr[0] / 4 + 4096;
-                CHOP_CK(dev_realloc(&s->d_hstage, cap));
-                CHOP_CK(dev_realloc(&s->d_hits, cap));
-                s->hit_cap = cap;
+                CHOP_CK(s->d_hstage.reserve(cap));
+                CHOP_CK(s->d_hits.reserve(cap));
             }
-            if (ctr[1] > s->seg_cap) {
+            if (ctr[1] > s->seg_cap()) {
                 const size_t cap = ctr[1] + ctr[1] / 4 + 4096;
-                CHOP_CK(dev_realloc(&s->d_sstage, cap));
-                CHOP_CK(dev_realloc(&s->d_segs, cap));
-                s->seg_cap = cap;
+                CHOP_CK(s->d_sstage.reserve(cap));
+                CHOP_CK(s->d_segs.reserve(cap));
             }
             continue;
         }
@@ -1039,9 +1000,9 @@ extern "C" int dmx_chop_exec(dmx_ctx* c, uint64_t* n_hits, uint64_t* n_segs) {
     CHOP_CK(hipEventRecord(s->ev[2], st));
     if (nb) {
         hipLaunchKernelGGL(chop_blkscan_kernel, dim3(1), dim3(1024), 0, st,
-                           (const uint32_t*)s->d_blk, nb, s->d_blkoff);
-        ChopOrderArgs O{s->d_blk, s->d_blkoff, nb, s->d_hstage, s->d_hits, s->d_sstage,
-                        s->d_segs};
+                           (const uint32_t*)s->d_blk.p, nb, s->d_blkoff.p);
+        ChopOrderArgs O{s->d_blk.p, s->d_blkoff.p, nb, s->d_hstage.p, s->d_hits.p, s->d_sstage.p,
+                        s->d_segs.p};
         hipLaunchKernelGGL(chop_order_kernel, dim3(std::min<uint32_t>(nb, 8192u)), dim3(256), 0,
                            st, O);
         CHOP_CK(hipGetLastError());
@@ -1072,16 +1033,16 @@ extern "C" int dmx_chop_fetch(dmx_ctx* c, uint32_t* n_seg, uint32_t* n_hit, dmx_
     hipStream_t st = c->stream;
     const size_t n = s->n_reads;
     if (n_seg && n)
-        CHOP_CK(hipMemcpyAsync(n_seg, s->d_nseg, n * 4, hipMemcpyDeviceToHost, st));
+        CHOP_CK(hipMemcpyAsync(n_seg, s->d_nseg.p, n * 4, hipMemcpyDeviceToHost, st));
     if (n_hit && n)
-        CHOP_CK(hipMemcpyAsync(n_hit, s->d_nhit, n * 4, hipMemcpyDeviceToHost, st));
+        CHOP_CK(hipMemcpyAsync(n_hit, s->d_nhit.p, n * 4, hipMemcpyDeviceToHost, st));
     const size_t ns = std::min<uint64_t>(s->n_segs, seg_cap);
     const size_t nh = std::min<uint64_t>(s->n_hits, hit_cap);
     if (segs && ns)
-        CHOP_CK(hipMemcpyAsync(segs, s->d_segs, ns * sizeof(dmx_chop_seg), hipMemcpyDeviceToHost,
+        CHOP_CK(hipMemcpyAsync(segs, s->d_segs.p, ns * sizeof(dmx_chop_seg), hipMemcpyDeviceToHost,
                                st));
     if (hits && nh)
-        CHOP_CK(hipMemcpyAsync(hits, s->d_hits, nh * sizeof(dmx_chop_hit), hipMemcpyDeviceToHost,
+        CHOP_CK(hipMemcpyAsync(hits, s->d_hits.p, nh * sizeof(dmx_chop_hit), hipMemcpyDeviceToHost,
                                st));
     CHOP_CK(hipStreamSynchronize(st));
     return DMX_OK;
@@ -1123,32 +1084,32 @@ extern "C" int dmx_chop_views(dmx_ctx* c, const uint8_t* qc_ok, int32_t min_len,
     uint32_t total = 0, bad = 0;
     CHOP_CK(s->verr.reserve(1));
     CHOP_CK(hipMemsetAsync(s->verr.p, 0, sizeof(uint32_t), st));
-    CHOP_CK(hipMemsetAsync(c->d_view_n, 0, sizeof(uint32_t), st));
+    CHOP_CK(hipMemsetAsync(c->d_view_n.p, 0, sizeof(uint32_t), st));
     if (nb) {
         ChopViewsArgs A;
-        A.nseg = s->d_nseg;
-        A.segs = s->d_segs;
-        A.blkoff = s->d_blkoff;
+        A.nseg = s->d_nseg.p;
+        A.segs = s->d_segs.p;
+        A.blkoff = s->d_blkoff.p;
         A.qc = qc_ok ? s->qc.p : nullptr;
-        A.lens = c->d_lens;
+        A.lens = c->in.lens.p;
         A.n_reads = (uint32_t)n;
         A.min_len = min_len;
-        A.n_segs = std::min<uint64_t>(s->n_segs, s->seg_cap);
+        A.n_segs = std::min<uint64_t>(s->n_segs, s->seg_cap());
         A.cnt = s->vcnt.p;
         A.off = s->voff.p;
-        A.views = c->d_views;
+        A.views = c->d_views.p;
         A.err = s->verr.p;
         A.bd = make_bounds(c, kKerChopViews);
 #ifdef DMX_DEBUG_BOUNDS
-        A.bd.items = s->seg_cap;
+        A.bd.items = s->seg_cap();
 #endif
         CHOP_CK(bounds_reset(c, st));
         hipLaunchKernelGGL(chop_views_kernel<true>, dim3(nb), dim3(64), 0, st, A);
         hipLaunchKernelGGL(chop_views_scan_kernel, dim3(1), dim3(1024), 0, st,
-                           (const uint32_t*)s->vcnt.p, nb, s->voff.p, c->d_view_n);
+                           (const uint32_t*)s->vcnt.p, nb, s->voff.p, c->d_view_n.p);
         hipLaunchKernelGGL(chop_views_kernel<false>, dim3(nb), dim3(64), 0, st, A);
         CHOP_CK(hipGetLastError());
-        CHOP_CK(hipMemcpyAsync(&total, c->d_view_n, sizeof total, hipMemcpyDeviceToHost, st));
+        CHOP_CK(hipMemcpyAsync(&total, c->d_view_n.p, sizeof total, hipMemcpyDeviceToHost, st));
         CHOP_CK(hipMemcpyAsync(&bad, s->verr.p, sizeof bad, hipMemcpyDeviceToHost, st));
     }
     CHOP_CK(hipStreamSynchronize(st));

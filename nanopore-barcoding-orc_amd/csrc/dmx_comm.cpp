@@ -210,13 +210,13 @@ int dmx_allreduce_counts(dmx_ctx* c, uint64_t* out, size_t n_out) {
     // idempotent per exec: a second call returns the summed counts without summing them again
     // (every rank follows the same call sequence, so either all ranks reduce or none does)
     if (!c->counts_reduced) {
-        const ncclResult_t r = rccl()->AllReduce(c->d_counts, c->d_counts, c->n_counts,
+        const ncclResult_t r = rccl()->AllReduce(c->d_counts.p, c->d_counts.p, c->n_counts,
                                                  ncclUint64, ncclSum, c->comm, c->stream);
         if (r != ncclSuccess) return nccl_fail(c, "ncclAllReduce", r);
         c->counts_reduced = true;
     }
     if (out &&
-        hipMemcpyAsync(out, c->d_counts, c->n_counts * 8, hipMemcpyDeviceToHost, c->stream) !=
+        hipMemcpyAsync(out, c->d_counts.p, c->n_counts * 8, hipMemcpyDeviceToHost, c->stream) !=
             hipSuccess) {
         c->err = "dmx_allreduce_counts: D2H copy failed";
         return DMX_E_HIP;
@@ -251,7 +251,7 @@ int allreduce_counts_group(dmx_ctx* const* ctxs, int n_ctx, uint64_t* out, size_
     for (int k = 0; k < n_ctx && r == ncclSuccess; ++k) {
         Ctx* c = ctxs[k];
         hipSetDevice(c->device);
-        r = R->AllReduce(c->d_counts, c->d_counts, nc, ncclUint64, ncclSum, c->comm, c->stream);
+        r = R->AllReduce(c->d_counts.p, c->d_counts.p, nc, ncclUint64, ncclSum, c->comm, c->stream);
     }
     const ncclResult_t r2 = R->GroupEnd();
     if (r != ncclSuccess) return nccl_fail(ctxs[0], "ncclAllReduce", r);
@@ -264,7 +264,7 @@ int allreduce_counts_group(dmx_ctx* const* ctxs, int n_ctx, uint64_t* out, size_
         }
     }
     hipSetDevice(ctxs[0]->device);
-    if (hipMemcpy(out, ctxs[0]->d_counts, nc * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+    if (hipMemcpy(out, ctxs[0]->d_counts.p, nc * 8, hipMemcpyDeviceToHost) != hipSuccess) {
         ctxs[0]->err = "count all-reduce: D2H copy failed";
         return DMX_E_HIP;
     }

@@ -424,23 +424,72 @@ struct DevEnds {
 // records the first offender (kernel id, buffer id, index) in d_counters[24..27], so the call
 // fails naming the kernel instead of faulting.
 // ---------------------------------------------------------------------------------------------
-enum BoundsBuf : uint32_t {
-    kBufSeq = 1, kBufMask = 2, kBufSlot = 3, kBufItem = 4, kBufRes = 5, kBufCount = 6,
-    kBufRead = 7, kBufLinked = 8, kBufCand = 9, kBufChop = 10, kBufPd = 11,
-    kBufPaTrace = 12, kBufPaOps = 13, kBufGaCols = 14, kBufRdCols = 15, kBufRrCols = 16,
-    kBufHistBins = 17, kBufRaCols = 18, kBufRaTable = 19, kBufRaBest = 20,
-    kBufEndsSeq = 21, kBufEndsMask = 22, kBufEndsSlot = 23, kBufEndsItem = 24, kBufEndsRead = 25
+// One list defines each id and the name bounds_check reports it by (host side).
+#define DMX_BOUNDS_BUFS(X)                                                                      \
+    X(Seq, "seq") X(Mask, "nmask") X(Slot, "winner slots") X(Item, "items") X(Res, "results")   \
+    X(Count, "counts") X(Read, "reads") X(Linked, "linked keys") X(Cand, "candidates")          \
+    X(Chop, "chop") X(Pd, "pairdist scratch") X(PaTrace, "pairalign trace")                     \
+    X(PaOps, "pairalign ops") X(GaCols, "groupalign columns") X(RdCols, "rowdist columns")      \
+    X(RrCols, "rowpair columns") X(HistBins, "identity table") X(RaCols, "rowassign columns")   \
+    X(RaTable, "rowassign tables") X(RaBest, "rowassign places") X(EndsSeq, "end-window seq")   \
+    X(EndsMask, "end-window nmask") X(EndsSlot, "end-window winner slots")                      \
+    X(EndsItem, "end-window items") X(EndsRead, "end-window reads")
+#define DMX_BOUNDS_KERNELS(X)                                                                   \
+    X(Filter, "filter_kernel") X(Verify, "verify_kernel") X(Screen, "iscreen_kernel")           \
+    X(Screen4, "iscreen4_kernel") X(Wscan, "wscan_kernel") X(Scan, "scan_kernel")               \
+    X(Band0, "band_cand_kernel<0,3>") X(Band1, "band_cand_kernel<4,5|7>")                       \
+    X(Resolve, "resolve_kernel") X(Select, "select_kernel") X(Fin0, "finalize0_kernel")         \
+    X(Fin1, "finalize1_kernel") X(Fin0L, "finalize0_linked_kernel")                             \
+    X(Fin1L, "finalize1_linked_kernel") X(Fin2L, "finalize2_linked_kernel")                     \
+    X(Chop, "chop_kernel") X(ChopBig, "chop_big_kernel") X(ChopStart, "chop_start")             \
+    X(SelfTest, "bounds_selftest_kernel") X(Pieces, "pscreen_kernel")                           \
+    X(Pairdist, "pairdist_kernel") X(Pairalign, "pairalign_kernel")                             \
+    X(PairalignTb, "pairalign_traceback_kernel") X(Groupalign, "groupalign_kernel")             \
+    X(GroupalignTb, "groupalign_traceback_kernel") X(GroupalignMerge, "groupalign_merge_kernel") \
+    X(Rowdist, "rowdist_kernel") X(Rowpair, "rowpair_kernel") X(RowpairRc, "rowpair_rc_kernel") \
+    X(Hithist, "lg_hist_kernel") X(Rowassign, "rowassign_kernel")                               \
+    X(RowassignDecide, "rowassign_decide_kernel") X(RowassignFinish, "rowassign_finish_kernel") \
+    X(Ends, "ends_kernel") X(EndsOrigin, "ends_origin_kernel")                                  \
+    X(EndsRemap, "ends_remap_kernel") X(ChopViews, "chop_views_kernel")                         \
+    X(Operands, "operands kernels")
+enum BoundsBuf : uint32_t {   // kBufSeq = 1, ... (0: none)
+    kBufNone_ = 0,
+#define DMX_BUF_ID_(id, name) kBuf##id,
+    DMX_BOUNDS_BUFS(DMX_BUF_ID_)
+#undef DMX_BUF_ID_
+    kBufEnd_
 };
-enum BoundsKernel : int32_t {
-    kKerFilter = 1, kKerVerify, kKerScreen, kKerScreen4, kKerWscan, kKerScan, kKerBand0,
-    kKerBand1, kKerResolve, kKerSelect, kKerFin0, kKerFin1, kKerFin0L, kKerFin1L,
-    kKerFin2L, kKerChop, kKerChopBig, kKerChopStart, kKerSelfTest, kKerPieces, kKerPairdist,
-    kKerPairalign, kKerPairalignTb, kKerGroupalign, kKerGroupalignTb, kKerGroupalignMerge,
-    kKerRowdist, kKerRowpair, kKerRowpairRc, kKerHithist, kKerRowassign,
-    kKerRowassignDecide, kKerRowassignFinish, kKerEnds, kKerEndsOrigin, kKerEndsRemap,
-    kKerChopViews, kKerOperands
+enum BoundsKernel : int32_t {   // kKerFilter = 1, ... (0: not set)
+    kKerNone_ = 0,
+#define DMX_KER_ID_(id, name) kKer##id,
+    DMX_BOUNDS_KERNELS(DMX_KER_ID_)
+#undef DMX_KER_ID_
+    kKerEnd_
 };
+static_assert(kBufSeq == 1 && kBufEndsRead == 25 && kKerFilter == 1 && kKerOperands == 38,
+              "bounds ids are recorded on the device as numbers");
 constexpr int kBoundsRec = 24;     // d_counters[24..27]: kernel id + 1, buffer, index lo / hi
+// Slots of the pipeline counters (Ctx::d_counters, u32 each) as the host addresses them.  The
+// kernels reach theirs through the pointers of their argument structs (cl_count, n_items_dev,
+// flags, diag, n_dp, n_seen) and bchk above; the lists of ShardList are counted per shard and
+// folded into the window / candidate / task slots when the host reads them (read_counters).
+enum CounterSlot {
+    kCntClusters = 0,    // + round: candidate clusters
+    kCntItems = 2,       // round-1 items (finalize0)
+    kCntFlags = 3,       // dmx_stats' flag bits
+    kCntWindows = 4,     // + round: filter windows
+    kCntCands = 6,       // + 2 round + list: candidate cells
+    kCntVerified = 10,   // + round: windows kept by the prefix verification
+    kCntTasks = 12,      // + round: tasks passed by the index screen
+    kCntFtasks = 14,     // + round: filter tasks of the piece screen
+    kCntDiag = 16,       // + 4 round + DiagSlot
+    kCntBounds = kBoundsRec,   // 4 slots: the DMX_DEBUG_BOUNDS record
+    kCntEndsDp = 28,     // + round: end-window triples that ran the exact DP
+    kCntEndsSeen = 30,   // + round: ... that were looked at
+    kCntCount = 32
+};
+enum DiagSlot { kDiagResolved = 0, kDiagTraces = 1, kDiagEndOnly = 3 };   // (2: unused)
+constexpr int cnt_diag(int round, int k) { return kCntDiag + 4 * round + k; }
 
 struct Bounds {
 #ifdef DMX_DEBUG_BOUNDS

@@ -383,33 +383,33 @@ int launch_ends(Ctx* c, int round, hipStream_t st) {
     A.pk.seq = c->d_seq;
     A.pk.nmask = c->d_nmask;
     A.pk.bd = make_bounds(c, kKerEnds);
-    A.offs = c->d_offs;
-    A.lens = c->d_lens;
+    A.offs = c->in.offs.p;
+    A.lens = c->in.lens.p;
     if (round == 0 && c->views_on) {   // a view run: round 0's items like round 1's
-        A.items = c->d_views;
-        A.n_items_dev = c->d_view_n;
+        A.items = c->d_views.p;
+        A.n_items_dev = c->d_view_n.p;
         A.n_items = (uint32_t)c->n_views;
 #ifdef DMX_DEBUG_BOUNDS
-        A.pk.bd.items = c->view_alloc;
+        A.pk.bd.items = c->d_views.cap;
 #endif
     } else if (round == 0) {
         A.items = nullptr;
         A.n_items_dev = nullptr;
         A.n_items = (uint32_t)c->n_reads;
     } else {
-        A.items = c->d_items;
-        A.n_items_dev = c->d_counters + 2;
+        A.items = c->d_items.p;
+        A.n_items_dev = c->d_counters.p + kCntItems;
         A.n_items = (uint32_t)c->item_cap;
     }
-    A.E = c->d_ends[round];
-    A.winner = c->d_winner[round];
-    A.origin = c->d_origin[round];
+    A.E = c->d_ends[round].p;
+    A.winner = c->d_winner[round].p;
+    A.origin = c->d_origin[round].p;
     A.oslot = c->orient_slot[round] ? 1 : 0;
     A.okey = band_round(c, round) ? 1 : 0;
-    A.flags = c->d_counters + 3;
-    A.n_dp = c->d_counters + 28 + round;
-    A.n_seen = c->d_counters + 30 + round;
-    hipEventRecord(c->ev[17 + 2 * round], st);
+    A.flags = c->d_counters.p + kCntFlags;
+    A.n_dp = c->d_counters.p + kCntEndsDp + round;
+    A.n_seen = c->d_counters.p + kCntEndsSeen + round;
+    hipEventRecord(c->ev[ev_of(kEvEndsIn, round)], st);
     if (A.n_items) {
         if (c->ends_remap[round] && c->panel[round].n > 0) {
             set_kid(A.pk.bd, kKerEndsRemap);
@@ -427,7 +427,7 @@ int launch_ends(Ctx* c, int round, hipStream_t st) {
             hipLaunchKernelGGL(ends_kernel<1>, dim3(grid), dim3(kEndsBlock), 0, st, A);
         }
     }
-    hipEventRecord(c->ev[18 + 2 * round], st);
+    hipEventRecord(c->ev[ev_of(kEvEndsOut, round)], st);
     return hipGetLastError() == hipSuccess ? DMX_OK : DMX_E_HIP;
 }
 

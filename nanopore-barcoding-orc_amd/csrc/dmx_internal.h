@@ -43,7 +43,70 @@ struct DevBuf {
         if (e == hipSuccess) cap = n;
         return e;
     }
+    void swap(DevBuf& o) {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
 };
+
+// The capacity that buffers grown together share: the smallest of theirs, so a member whose
+// allocation failed (capacity 0) makes the whole group read as too small.
+template <typename T>
+size_t min_cap(const DevBuf<T>& b) {
+    return b.cap;
+}
+template <typename T, typename... R>
+size_t min_cap(const DevBuf<T>& b, const R&... rest) {
+    return std::min(b.cap, min_cap(rest...));
+}
+
+// One set of input buffers and the results computed from them.  A context has two: the resident
+// batch and the set the chunks of a large dmx_run alternate with.
+struct InputSet {
+    DevBuf<uint32_t> seq, nmask;   // packed buffers with kGuardWords zeroed words on both sides
+    DevBuf<uint64_t> offs;         // (the filter loads whole aligned 64-nt blocks)
+    DevBuf<uint32_t> lens;
+    DevBuf<dmx_result> res;
+    DevBuf<uint32_t> exc;          // sparse no-match mask staging: [idx][val] (dmx_run_sparse)
+    size_t n_words = 0;
+    // words of a batch that fit between the guards; reads that fit offs / lens
+    size_t cap_words() const {
+        const size_t t = min_cap(seq, nmask);
+        return t > 2 * (size_t)kGuardWords ? t - 2 * (size_t)kGuardWords : 0;
+    }
+    size_t cap_reads() const { return min_cap(offs, lens); }
+    void swap(InputSet& o) {
+        seq.swap(o.seq), nmask.swap(o.nmask), offs.swap(o.offs), lens.swap(o.lens);
+        res.swap(o.res), exc.swap(o.exc);
+        std::swap(n_words, o.n_words);
+    }
+};
+
+// Indices of Ctx::ev: per round (ev_of) the start of the round, the end of its scan stage, of
+// the resolve stage and of finalize; inside the scan stage the ends of the filter pass, the
+// verification, the index screen and the piece screen (its filter tasks follow); before / after
+// the end-window stage.  One more event marks the start of dmx_exec.
+enum EvKind {
+    kEvRound, kEvScan, kEvResolve, kEvFinal, kEvFilter, kEvVerify, kEvScreen, kEvPieces,
+    kEvEndsIn, kEvEndsOut, kEvKinds
+};
+constexpr int ev_of(int kind, int round) { return 2 * kind + round; }
+constexpr int kEvExec = 2 * kEvKinds;
+constexpr int kEvCount = kEvExec + 1;
+
+// Slots of dmx_stats' stage times (include/dmx.h): per round the scan, resolve and finalize
+// stages; the whole exec; per round the filter pass, the verification, the index screen, the
+// window scan after it, the piece screen's share of the filter pass and the end-window stage.
+enum StageKind { kStScan, kStResolve, kStFinal };
+constexpr int st_round(int round, int kind) { return 3 * round + kind; }
+constexpr int kStTotal = 6;
+constexpr int st_filter(int round) { return 7 + 2 * round; }
+constexpr int st_verify(int round) { return 8 + 2 * round; }
+constexpr int st_screen(int round) { return 11 + 2 * round; }
+constexpr int st_wscan(int round) { return 12 + 2 * round; }
+constexpr int st_pieces(int round) { return 15 + round; }
+constexpr int st_ends(int round) { return 17 + round; }
+constexpr int kStCount = st_ends(1) + 1;
 
 // Reach of a panel's gathers around a view, in nt (panel_reach below).
 struct PanelReach {
@@ -86,81 +149,53 @@ struct Ctx {
     int mode = DMX_MODE_SINGLE;
     PanelSwitches sw;         // read by dmx_open
     HostPanel panel[2];
-    DevPanel* d_panel[2] = {nullptr, nullptr};
-    DevPieces* d_pieces[2] = {nullptr, nullptr};
+    DevBuf<DevPanel> d_panel[2];     // one record each, made by dmx_open
+    DevBuf<DevPieces> d_pieces[2];
     // end-window stage: per round the number of restricted adapters (0: the
     // stage does not run and nothing below is read), whether the internal pipeline's keys need
     // their adapter index mapped back, the stage's tables and the whole panel for finalize
     int ends_n[2] = {0, 0};
     bool ends_remap[2] = {false, false};
-    DevEnds* d_ends[2] = {nullptr, nullptr};
-    DevPanel* d_panel_all[2] = {nullptr, nullptr};
+    DevBuf<DevEnds> d_ends[2];
+    DevBuf<DevPanel> d_panel_all[2];
 
-    // resident batch
-    size_t n_reads = 0, n_words = 0;
-    size_t cap_reads = 0;     // pipeline buffers (winner slots, items, linked keys)
-    size_t cap_words = 0;     // d_seq / d_nmask of the resident input set
-    size_t in_cap_reads = 0;  // d_offs / d_lens of the resident input set
-    size_t res_cap = 0;       // d_res of the resident input set
-    uint32_t* d_seq = nullptr;          // = d_seq_alloc + kGuardWords
+    // resident batch.  dmx_run of a large batch alternates its chunks between `in` and `alt`
+    // (inputs + results), so the next chunk's upload and the previous chunk's download overlap
+    // the current chunk's kernels (dmx_api.cpp run_chunked).
+    size_t n_reads = 0;
+    InputSet in, alt;
+    // the resident set's packed buffers past their leading guard words: the only pointers into
+    // a buffer that are kept, re-derived by derive_inputs after every allocation or swap of `in`
+    uint32_t* d_seq = nullptr;
     uint32_t* d_nmask = nullptr;
-    uint32_t* d_seq_alloc = nullptr;    // packed buffers with zeroed guard words on both sides
-    uint32_t* d_nmask_alloc = nullptr;  // (the filter loads whole aligned 64-nt blocks)
-    uint64_t* d_offs = nullptr;
-    uint32_t* d_lens = nullptr;
-    uint32_t* d_exc = nullptr;          // sparse no-match mask staging: [idx][val] (dmx_run_sparse)
-    size_t exc_cap = 0;
-
-    // dmx_run of a large batch: chunks alternate between the buffers above and this second
-    // set (inputs + results), so the next chunk's upload and the previous chunk's download
-    // overlap the current chunk's kernels (dmx_api.cpp run_chunked)
-    struct InSet {
-        uint32_t* seq_alloc = nullptr;
-        uint32_t* nmask_alloc = nullptr;
-        uint64_t* offs = nullptr;
-        uint32_t* lens = nullptr;
-        dmx_result* res = nullptr;
-        uint32_t* exc = nullptr;
-        // capacities travel with their buffers (swap_inputs): words, offs/lens, res, exceptions
-        size_t cap_words = 0, cap_reads = 0, res_cap = 0, n_words = 0, exc_cap = 0;
-    } alt;
     hipStream_t cstream = nullptr;      // uploads of chunked runs
     hipStream_t dstream = nullptr;      // result downloads of chunked runs (the other direction)
     bool chunked = false;               // the last dmx_run was chunked: dmx_fetch is refused
 
     // pipeline state
-    dmx_result* d_res = nullptr;
-    unsigned long long* d_winner[2] = {nullptr, nullptr};
-    int32_t* d_origin[2] = {nullptr, nullptr};   // ring rounds only (band rounds: in the key)
-    size_t origin_cap[2] = {0, 0};
-    int32_t* d_lb[2] = {nullptr, nullptr};
+    DevBuf<unsigned long long> d_winner[2];
+    DevBuf<int32_t> d_origin[2];   // ring rounds only (band rounds: in the key)
+    DevBuf<int32_t> d_lb[2];
     bool ring_small[2] = {true, true};
     bool band_ok[2] = {true, true};
     bool band_wide[2] = {true, true};      // some adapter has kk 6..7: list 1 needs 15 diagonals
     bool orient_slot[2] = {false, false};   // per round: one winner slot per (item, orientation)
     bool force_ring = false;          // DMX_RESOLVE=ring (A/B testing)
-    size_t slot_cap = 0;
-    Cluster* d_cl[2] = {nullptr, nullptr};
-    Outcome* d_outc[2] = {nullptr, nullptr};
-    size_t cl_cap = 0;
-    Cand* d_cand[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    size_t cand_cap = 0;
-    Window* d_win = nullptr;
-    Window* d_win2 = nullptr;
-    size_t win_cap = 0;
-    ItemView* d_items = nullptr;
+    bool resolve_attr_set = false;    // resolve_kernel's dynamic-LDS limit raised on this device
+    DevBuf<Cluster> d_cl[2];
+    DevBuf<Outcome> d_outc[2];
+    DevBuf<Cand> d_cand[2][2];
+    DevBuf<Window> d_win, d_win2;
+    DevBuf<ItemView> d_items;            // sized by its own need (ensure_pipeline)
     size_t item_cap = 0;                 // round-2 items of the current mode and batch
-    size_t item_alloc = 0;               // entries allocated in d_items (>= item_cap)
     // view runs (dmx_set_views / dmx_chop_views): round 0's item list.  A buffer
     // of its own: finalize0 reads view k while it writes the round-1 list d_items.
     bool views_on = false;
     size_t n_views = 0;
-    ItemView* d_views = nullptr;
-    size_t view_alloc = 0;
+    DevBuf<ItemView> d_views;
     std::vector<uint32_t> h_lens;        // the resident batch's read lengths (dmx_load's copy)
-    uint32_t* d_view_n = nullptr;        // the list's length on the device (round 0's n_items_dev)
-    uint32_t* d_item_src = nullptr;      // round-1 item -> the view it came from (its result)
-    size_t item_src_alloc = 0;
+    DevBuf<uint32_t> d_view_n;           // the list's length on the device (round 0's n_items_dev)
+    DevBuf<uint32_t> d_item_src;         // round-1 item -> the view it came from (its result)
     // operand table (dmx_set_operands / dmx_result_operands): with a table set the
     // amplicon-sorting calls index operands, not reads.  d_op_off / d_op_len stand in for d_offs /
     // d_lens in their launches (the sub-range as it lies in memory); d_op holds the table itself
@@ -181,33 +216,27 @@ struct Ctx {
     DevBuf<uint32_t> d_op_hist;
     DevBuf<uint64_t> d_op_first;
     DevBuf<uint8_t> d_op_keep;
-    uint32_t* d_shard = nullptr;      // [kShLists][kShards] per-shard list counters (dmx_device.h)
-    uint32_t* d_counters = nullptr;   // [0..1] clusters, [2] items, [3] flags, [4..5] windows, [6+2r..] candidates, [10+r] verified windows, [16+4r..] diag, [24..27] DMX_DEBUG_BOUNDS record
-    unsigned long long* d_counts = nullptr;
-    unsigned long long* d_linked = nullptr;
-    Window* d_tasks = nullptr;           // index screen survivors (window piece of one adapter)
-    size_t task_cap = 0;
-    FTask* d_ftask = nullptr;            // piece screen -> filter tasks
-    size_t ftask_cap = 0;
+    DevBuf<uint32_t> d_shard;         // [kShLists][kShards] per-shard list counters (dmx_device.h)
+    DevBuf<uint32_t> d_counters;      // kCntCount slots (dmx_device.h CounterSlot)
+    DevBuf<unsigned long long> d_counts;   // n_counts of them are in use
+    DevBuf<unsigned long long> d_linked;   // one key per read (linked mode)
+    DevBuf<Window> d_tasks;           // index screen survivors (window piece of one adapter)
+    DevBuf<FTask> d_ftask;            // piece screen -> filter tasks
     // flat piece scan (prepare_flat): one scan of the batch against the flat rounds' combined
     // table marks cells[2 r + strand] for every flat round r
-    DevPieces* d_pieces_flat = nullptr;
+    DevBuf<DevPieces> d_pieces_flat;
     int flat_rounds = 0;                 // bit r: round r's screen is the flat scan (this exec)
     int flat_want = 0;                   // the rounds the combined table was built for
     int flat_step = 0;                   // its sampling stride (0: no table)
     size_t flat_lds = 0;                 // its LDS image
     uint64_t panel_gen = 1;              // bumped by set_panel / set_mode
     uint64_t flat_gen = 0;               // panel_gen the combined table was built for
-    uint32_t* d_cells[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t cells_cap[4] = {0, 0, 0, 0};
+    DevBuf<uint32_t> d_cells[4];
     size_t cells_words = 0;
     bool no_screen = false;              // DMX_NO_SCREEN=1: every window runs every adapter
     bool screen_v1 = false;              // DMX_SCREEN_V1=1: one lane per (window, adapter) screen
     size_t n_counts = 0;
-    hipEvent_t ev[21] = {};   // [3r..3r+2] round r stages, [6+r] finalize, [8] start,
-                              // [9+2r] after filter, [10+2r] after verify, [13+r] after screen,
-                              // [15+r] after the piece screen (its filter tasks follow),
-                              // [17+2r] / [18+2r] before / after the end-window stage
+    hipEvent_t ev[kEvCount] = {};   // EvKind per round (ev_of), kEvExec
     bool executed = false;
     size_t exec_items = 0;       // results of the last dmx_exec (round 0's items)
     bool exec_views = false;     // ... which were the views of d_views as of exec_view_gen
@@ -229,6 +258,28 @@ struct Ctx {
     uint64_t comm_group = 0;     // nonzero: made by dmx_comm_init_all (one process, grouped calls)
     bool counts_reduced = false; // d_counts already summed over the ranks (cleared by dmx_exec)
 };
+
+// Capacities of the pipeline's buffer groups, as their buffers have them: the winner slots (with
+// the slot lower bounds), the cluster, candidate and window lists.  The screen's task list holds
+// 4 records per window record, the filter task list one.
+inline size_t slot_cap(const Ctx* c) {
+    return min_cap(c->d_winner[0], c->d_winner[1], c->d_lb[0], c->d_lb[1]);
+}
+inline size_t cl_cap(const Ctx* c) {
+    return min_cap(c->d_cl[0], c->d_cl[1], c->d_outc[0], c->d_outc[1]);
+}
+inline size_t cand_cap(const Ctx* c) {
+    return min_cap(c->d_cand[0][0], c->d_cand[0][1], c->d_cand[1][0], c->d_cand[1][1]);
+}
+inline size_t win_cap(const Ctx* c) {
+    return std::min(min_cap(c->d_win, c->d_win2, c->d_ftask), c->d_tasks.cap / 4);
+}
+inline size_t task_cap(const Ctx* c) { return 4 * win_cap(c); }
+// d_seq / d_nmask from the resident set's allocations.
+inline void derive_inputs(Ctx* c) {
+    c->d_seq = c->in.seq.p ? c->in.seq.p + kGuardWords : nullptr;
+    c->d_nmask = c->in.nmask.p ? c->in.nmask.p + kGuardWords : nullptr;
+}
 
 void chop_release(Ctx* c);
 void pd_release(Ctx* c);
@@ -284,7 +335,7 @@ int launch_finalize(Ctx* c, int round, hipStream_t st);
 int launch_ends(Ctx* c, int round, hipStream_t st);
 // The panel finalize decodes with: the whole panel where the round has restricted adapters.
 inline const DevPanel* final_panel(const Ctx* c, int round) {
-    return c->ends_n[round] ? c->d_panel_all[round] : c->d_panel[round];
+    return c->ends_n[round] ? c->d_panel_all[round].p : c->d_panel[round].p;
 }
 // offs[i] -= g0 for a chunk's offsets uploaded as the caller gave them (stream st)
 int launch_rebase_offsets(uint64_t* offs, uint32_t n, uint64_t g0, hipStream_t st);

@@ -4453,16 +4453,16 @@ Bounds make_bounds(const Ctx* c, int kid) {
     Bounds b;
 #ifdef DMX_DEBUG_BOUNDS
     b.lo = -(int64_t)kGuardWords;
-    b.hi = (int64_t)c->cap_words + kGuardWords;   // both buffers: cap_words + 2 guards words
-    b.slots = c->slot_cap;
-    b.items = c->item_alloc;
+    b.hi = (int64_t)c->in.cap_words() + kGuardWords;   // both buffers: the words + 2 guards
+    b.slots = slot_cap(c);
+    b.items = c->d_items.cap;
     b.reads = c->n_reads;
     b.counts = c->n_counts;
-    b.linked = c->cap_reads;
-    b.res = c->res_cap;
-    b.views = c->view_alloc;
-    b.srcs = c->item_src_alloc;
-    b.rec = c->d_counters;
+    b.linked = c->d_linked.cap;
+    b.res = c->in.res.cap;
+    b.views = c->d_views.cap;
+    b.srcs = c->d_item_src.cap;
+    b.rec = c->d_counters.p;
     b.kid = kid;
 #else
     (void)c, (void)kid;
@@ -4472,7 +4472,7 @@ Bounds make_bounds(const Ctx* c, int kid) {
 
 hipError_t bounds_reset(Ctx* c, hipStream_t st) {
 #ifdef DMX_DEBUG_BOUNDS
-    return hipMemsetAsync(c->d_counters + kBoundsRec, 0, 4 * sizeof(uint32_t), st);
+    return hipMemsetAsync(c->d_counters.p + kCntBounds, 0, 4 * sizeof(uint32_t), st);
 #else
     (void)c, (void)st;
     return hipSuccess;
@@ -4481,30 +4481,16 @@ hipError_t bounds_reset(Ctx* c, hipStream_t st) {
 
 int bounds_check(Ctx* c, const char* where) {
 #ifdef DMX_DEBUG_BOUNDS
-    static const char* const kKer[] = {
-        "?", "filter_kernel", "verify_kernel", "iscreen_kernel", "iscreen4_kernel",
-        "wscan_kernel", "scan_kernel", "band_cand_kernel<0,3>", "band_cand_kernel<4,5|7>",
-        "resolve_kernel", "select_kernel", "finalize0_kernel", "finalize1_kernel", "finalize0_linked_kernel", "finalize1_linked_kernel",
-        "finalize2_linked_kernel", "chop_kernel", "chop_big_kernel", "chop_start",
-        "bounds_selftest_kernel", "pscreen_kernel", "pairdist_kernel", "pairalign_kernel",
-        "pairalign_traceback_kernel", "groupalign_kernel", "groupalign_traceback_kernel",
-        "groupalign_merge_kernel", "rowdist_kernel", "rowpair_kernel", "rowpair_rc_kernel",
-        "lg_hist_kernel", "rowassign_kernel", "rowassign_decide_kernel",
-        "rowassign_finish_kernel", "ends_kernel", "ends_origin_kernel", "ends_remap_kernel",
-        "chop_views_kernel", "operands kernels"};
-    static const char* const kBuf[] = {"?", "seq", "nmask", "winner slots", "items", "results",
-                                       "counts", "reads", "linked keys", "candidates", "chop",
-                                       "pairdist scratch", "pairalign trace", "pairalign ops",
-                                       "groupalign columns", "rowdist columns",
-                                       "rowpair columns", "identity table",
-                                       "rowassign columns", "rowassign tables",
-                                       "rowassign places", "end-window seq",
-                                       "end-window nmask", "end-window winner slots",
-                                       "end-window items", "end-window reads"};
+#define DMX_NAME_(id, name) name,
+    static const char* const kKer[] = {"?", DMX_BOUNDS_KERNELS(DMX_NAME_)};
+    static const char* const kBuf[] = {"?", DMX_BOUNDS_BUFS(DMX_NAME_)};
+#undef DMX_NAME_
+    static_assert(sizeof kKer / sizeof *kKer == kKerEnd_ && sizeof kBuf / sizeof *kBuf == kBufEnd_,
+                  "one name per id");
     uint32_t rec[4];
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess)
-        e = hipMemcpy(rec, c->d_counters + kBoundsRec, sizeof(rec), hipMemcpyDeviceToHost);
+        e = hipMemcpy(rec, c->d_counters.p + kCntBounds, sizeof(rec), hipMemcpyDeviceToHost);
     if (e != hipSuccess) {
         c->err = std::string(where) + ": " + hipGetErrorString(e);
         return DMX_E_HIP;
@@ -4539,24 +4525,23 @@ __global__ void bounds_selftest_kernel(Packed pk, uint64_t slot_probe, uint32_t*
 
 int bounds_selftest(Ctx* c, uint32_t* host_out) {
 #ifdef DMX_DEBUG_BOUNDS
-    if (!c->d_seq || !c->d_winner[0]) {
+    if (!c->d_seq || !c->d_winner[0].p) {
         c->err = "dmx_debug_bounds_selftest: load and run a batch first";
         return DMX_E_STATE;
     }
-    uint32_t* d_out = nullptr;
-    if (hipMalloc((void**)&d_out, 3 * sizeof(uint32_t)) != hipSuccess) return DMX_E_HIP;
+    DevBuf<uint32_t> d_out;
+    if (d_out.reserve(3) != hipSuccess) return DMX_E_HIP;
     Packed pk;
     pk.seq = c->d_seq;
     pk.nmask = c->d_nmask;
     pk.bd = make_bounds(c, kKerSelfTest);
-    hipMemsetAsync(c->d_counters + 3, 0, sizeof(uint32_t), c->stream);
+    hipMemsetAsync(c->d_counters.p + kCntFlags, 0, sizeof(uint32_t), c->stream);
     bounds_reset(c, c->stream);
     hipLaunchKernelGGL(bounds_selftest_kernel, dim3(1), dim3(64), 0, c->stream, pk,
-                       (uint64_t)c->slot_cap, d_out);
+                       (uint64_t)slot_cap(c), d_out.p);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess)
-        e = hipMemcpy(host_out, d_out, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    hipFree(d_out);
+        e = hipMemcpy(host_out, d_out.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return DMX_E_HIP;
     return bounds_check(c, "dmx_debug_bounds_selftest");
 #else
@@ -4580,8 +4565,8 @@ int prepare_flat(Ctx* c, hipStream_t st) {
             c->panel[r].piece_step && c->panel[r].n_orient == 2)
             want |= 1 << r;
     if (!want) return DMX_OK;
-    const size_t nsb = (c->n_words + kSuperNt / 16 - 1) / (kSuperNt / 16);
-    if (nsb >= (1ull << 31) || c->n_words >= (1ull << 31)) return DMX_OK;
+    const size_t nsb = (c->in.n_words + kSuperNt / 16 - 1) / (kSuperNt / 16);
+    if (nsb >= (1ull << 31) || c->in.n_words >= (1ull << 31)) return DMX_OK;
     if (c->flat_gen != c->panel_gen || c->flat_want != want) {
         c->flat_gen = c->panel_gen;
         c->flat_want = want;
@@ -4618,26 +4603,20 @@ int prepare_flat(Ctx* c, hipStream_t st) {
         T->n_pieces = npc;
         T->n_keys = nk;
         T->n_entries = (int)ents.size();
-        if (!c->d_pieces_flat &&
-            hipMalloc((void**)&c->d_pieces_flat, sizeof(DevPieces)) != hipSuccess)
-            return DMX_E_NOMEM;
+        if (c->d_pieces_flat.reserve(1) != hipSuccess) return DMX_E_NOMEM;
         // the previous exec's scan may still read the old table
         if (hipStreamSynchronize(st) != hipSuccess ||
-            hipMemcpy(c->d_pieces_flat, T.get(), sizeof(DevPieces), hipMemcpyHostToDevice) !=
+            hipMemcpy(c->d_pieces_flat.p, T.get(), sizeof(DevPieces), hipMemcpyHostToDevice) !=
                 hipSuccess)
             return DMX_E_HIP;
         c->flat_lds = (size_t)kPieceLdsFixed + 8 * ((size_t)(nk + 1) / 2) + 8 * ents.size();
         c->flat_step = step;
     }
     if (!c->flat_step) return DMX_OK;   // the tables do not fit together: the per-part screen
-    const size_t cw = (c->n_words + 31) / 32 + 2 * kCellGuardWords;
+    const size_t cw = (c->in.n_words + 31) / 32 + 2 * kCellGuardWords;
     for (int i = 0; i < 4; ++i) {
-        if (!(want >> (i >> 1) & 1) || (c->d_cells[i] && c->cells_cap[i] >= cw)) continue;
-        if (c->d_cells[i]) hipFree(c->d_cells[i]);
-        c->d_cells[i] = nullptr;
-        c->cells_cap[i] = 0;
-        if (hipMalloc((void**)&c->d_cells[i], cw * 4) != hipSuccess) return DMX_E_NOMEM;
-        c->cells_cap[i] = cw;
+        if (!(want >> (i >> 1) & 1)) continue;
+        if (c->d_cells[i].reserve(cw) != hipSuccess) return DMX_E_NOMEM;
     }
     c->cells_words = cw;
     c->flat_rounds = want;
@@ -4649,20 +4628,20 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
     R.pk.seq = c->d_seq;
     R.pk.nmask = c->d_nmask;
     R.pk.bd = make_bounds(c, 0);
-    R.offs = c->d_offs;
-    R.lens = c->d_lens;
-    R.panel = c->d_panel[round];
+    R.offs = c->in.offs.p;
+    R.lens = c->in.lens.p;
+    R.panel = c->d_panel[round].p;
     const HostPanel& hp = c->panel[round];
     const bool linked = c->mode == DMX_MODE_LINKED;
     R.per_task_slot = (linked && round == 0) ? 1 : 0;
     R.slot_div = c->orient_slot[round] ? hp.n : 0;
     if (round == 0 && c->views_on) {   // a view run: round 0 over the view list, as round 1
-        R.items = c->d_views;          // runs over finalize0's (never linked: dmx_exec)
-        R.n_items_dev = c->d_view_n;
+        R.items = c->d_views.p;          // runs over finalize0's (never linked: dmx_exec)
+        R.n_items_dev = c->d_view_n.p;
         R.n_items = (uint32_t)c->n_views;
         R.T = hp.n * hp.n_orient;
 #ifdef DMX_DEBUG_BOUNDS
-        R.pk.bd.items = c->view_alloc;
+        R.pk.bd.items = c->d_views.cap;
 #endif
     } else if (round == 0) {
         R.items = nullptr;
@@ -4670,62 +4649,62 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
         R.n_items = (uint32_t)c->n_reads;
         R.T = linked ? hp.n : hp.n * hp.n_orient;
     } else {
-        R.items = c->d_items;
-        R.n_items_dev = c->d_counters + 2;
+        R.items = c->d_items.p;
+        R.n_items_dev = c->d_counters.p + kCntItems;
         R.n_items = (uint32_t)c->item_cap;
         R.T = linked ? 1 : hp.n * hp.n_orient;
     }
-    R.cl = c->d_cl[round];
-    R.outc = c->d_outc[round];
-    R.cl_count = c->d_counters + round;
-    R.cl_cap = (uint32_t)c->cl_cap;
-    R.flags = c->d_counters + 3;
-    R.winner = c->d_winner[round];
-    R.origin = c->d_origin[round];
-    R.lb = c->d_lb[round];
+    R.cl = c->d_cl[round].p;
+    R.outc = c->d_outc[round].p;
+    R.cl_count = c->d_counters.p + kCntClusters + round;
+    R.cl_cap = (uint32_t)cl_cap(c);
+    R.flags = c->d_counters.p + kCntFlags;
+    R.winner = c->d_winner[round].p;
+    R.origin = c->d_origin[round].p;
+    R.lb = c->d_lb[round].p;
     if (R.T > kScanBlock) return DMX_E_UNSUPPORTED;
-    hipMemsetAsync(R.lb, 0, sizeof(int32_t) * (round == 0 ? c->slot_cap
+    hipMemsetAsync(R.lb, 0, sizeof(int32_t) * (round == 0 ? slot_cap(c)
                                                          : c->item_cap * (R.slot_div ? 2 : 1)),
                    st);
 
     const uint32_t rpb = kScanBlock / R.T;
     const uint32_t grid = (uint32_t)((R.n_items + rpb - 1) / rpb);
-    R.diag = c->d_counters + 16 + 4 * round;
-    R.win = c->d_win;
-    R.win_count = c->d_shard + (kShWin + round) * kShards * kShardStride;
-    R.win2 = c->d_win2;
-    R.win2_count = c->d_shard + (kShWin2 + round) * kShards * kShardStride;
-    R.win_cap = (uint32_t)c->win_cap;
-    R.win_scap = (uint32_t)(c->win_cap / kShards);
+    R.diag = c->d_counters.p + cnt_diag(round, 0);
+    R.win = c->d_win.p;
+    R.win_count = c->d_shard.p + (kShWin + round) * kShards * kShardStride;
+    R.win2 = c->d_win2.p;
+    R.win2_count = c->d_shard.p + (kShWin2 + round) * kShards * kShardStride;
+    R.win_cap = (uint32_t)win_cap(c);
+    R.win_scap = (uint32_t)(win_cap(c) / kShards);
     const bool band = band_round(c, round);
     R.band = band ? 1 : 0;
     for (int l = 0; l < 2; ++l) {
-        R.cand[l] = c->d_cand[round][l];
+        R.cand[l] = c->d_cand[round][l].p;
     }
-    R.cand_count = c->d_shard + (kShCand + 2 * round) * kShards * kShardStride;
-    R.cand_cap = (uint32_t)c->cand_cap;
-    R.cand_scap = (uint32_t)(c->cand_cap / kShards);
+    R.cand_count = c->d_shard.p + (kShCand + 2 * round) * kShards * kShardStride;
+    R.cand_cap = (uint32_t)cand_cap(c);
+    R.cand_scap = (uint32_t)(cand_cap(c) / kShards);
     R.screen = (hp.filter && hp.verify && hp.screen && !linked && !c->no_screen &&
-                (uint64_t)c->win_cap * (uint64_t)hp.n < (1ull << 32)) ? 1 : 0;
-    R.tasks = c->d_tasks;
-    R.task_count = c->d_shard + (kShTasks + round) * kShards * kShardStride;
-    R.task_cap = (uint32_t)c->task_cap;
-    R.task_scap = (uint32_t)(c->task_cap / kShards);
-    R.pieces = c->d_pieces[round];
-    R.ftask = c->d_ftask;
-    R.ftask_count = c->d_shard + (kShFtask + round) * kShards * kShardStride;
-    R.ftask_scap = (uint32_t)(c->ftask_cap / kShards);
-    R.n_words = (uint32_t)c->n_words;
-    R.nsb = (uint32_t)((c->n_words + kSuperNt / 16 - 1) / (kSuperNt / 16));
+                (uint64_t)win_cap(c) * (uint64_t)hp.n < (1ull << 32)) ? 1 : 0;
+    R.tasks = c->d_tasks.p;
+    R.task_count = c->d_shard.p + (kShTasks + round) * kShards * kShardStride;
+    R.task_cap = (uint32_t)task_cap(c);
+    R.task_scap = (uint32_t)(task_cap(c) / kShards);
+    R.pieces = c->d_pieces[round].p;
+    R.ftask = c->d_ftask.p;
+    R.ftask_count = c->d_shard.p + (kShFtask + round) * kShards * kShardStride;
+    R.ftask_scap = (uint32_t)(win_cap(c) / kShards);
+    R.n_words = (uint32_t)c->in.n_words;
+    R.nsb = (uint32_t)((c->in.n_words + kSuperNt / 16 - 1) / (kSuperNt / 16));
     R.round = round;
     for (int i = 0; i < 4; ++i)
-        R.cells[i] = (c->flat_rounds >> (i >> 1) & 1) ? c->d_cells[i] + kCellGuardWords : nullptr;
-    hipEventRecord(c->ev[round * 3 + 0], st);
+        R.cells[i] = (c->flat_rounds >> (i >> 1) & 1) ? c->d_cells[i].p + kCellGuardWords : nullptr;
+    hipEventRecord(c->ev[ev_of(kEvRound, round)], st);
     if (round == 0 && c->flat_rounds) {   // the flat scan: every flat round's marks at once
         for (int i = 0; i < 4; ++i)
-            if (R.cells[i]) hipMemsetAsync(c->d_cells[i], 0, 4 * c->cells_words, st);
+            if (R.cells[i]) hipMemsetAsync(c->d_cells[i].p, 0, 4 * c->cells_words, st);
         RoundArgs S = R;
-        S.pieces = c->d_pieces_flat;
+        S.pieces = c->d_pieces_flat.p;
         constexpr uint32_t wpb = kPScanBlock / 64;   // superblocks per block step
         const uint32_t sgrid = std::min<uint32_t>((R.nsb + wpb - 1) / wpb, kPScanGrid);
         const size_t lds = c->flat_lds;
@@ -4765,7 +4744,7 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
                 }
                 DMX_DBG_SYNC("pscreen_kernel");
             }
-            hipEventRecord(c->ev[15 + round], st);
+            hipEventRecord(c->ev[ev_of(kEvPieces, round)], st);
             set_kid(R.pk.bd, kKerFilter);
             hipLaunchKernelGGL(ftask_kernel, dim3(256 * 8), dim3(kScanBlock), 0, st, R);
             DMX_DBG_SYNC("ftask_kernel");
@@ -4778,12 +4757,12 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
                 hipLaunchKernelGGL(filter_kernel, dim3(fgrid), dim3(kScanBlock), 0, st, R);
             DMX_DBG_SYNC("filter_kernel");
         }
-        hipEventRecord(c->ev[9 + 2 * round], st);
+        hipEventRecord(c->ev[ev_of(kEvFilter, round)], st);
         set_kid(R.pk.bd, kKerVerify);
         if (hp.verify)
             hipLaunchKernelGGL(verify_kernel, dim3(256 * 8), dim3(kScanBlock), 0, st, R);
         DMX_DBG_SYNC("verify_kernel");
-        hipEventRecord(c->ev[10 + 2 * round], st);
+        hipEventRecord(c->ev[ev_of(kEvVerify, round)], st);
         if (R.screen) {   // packed quads for panels of <= 32 adapters (DMX_SCREEN_V1: A/B)
             if (hp.n <= 4 * kScreenQuads && !c->screen_v1) {
                 set_kid(R.pk.bd, kKerScreen4);
@@ -4794,7 +4773,7 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
             }
         }
         DMX_DBG_SYNC("iscreen");
-        hipEventRecord(c->ev[13 + round], st);
+        hipEventRecord(c->ev[ev_of(kEvScreen, round)], st);
         set_kid(R.pk.bd, kKerWscan);
         // (near-start tasks in a second launch, pruned against the slot lower bounds of the
         // first: measured no faster, profiles/r6_ab_wscan_near_phase_*.txt)
@@ -4802,15 +4781,15 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
         else hipLaunchKernelGGL(wscan_kernel<false>, dim3(256 * 16), dim3(kScanBlock), 0, st, R);
         DMX_DBG_SYNC("wscan_kernel");
     } else if (grid > 0) {
-        hipEventRecord(c->ev[9 + 2 * round], st);
-        hipEventRecord(c->ev[10 + 2 * round], st);
-        hipEventRecord(c->ev[13 + round], st);
+        hipEventRecord(c->ev[ev_of(kEvFilter, round)], st);
+        hipEventRecord(c->ev[ev_of(kEvVerify, round)], st);
+        hipEventRecord(c->ev[ev_of(kEvScreen, round)], st);
         set_kid(R.pk.bd, kKerScan);
         if (band) hipLaunchKernelGGL(scan_kernel<true>, dim3(grid), dim3(kScanBlock), 0, st, R);
         else hipLaunchKernelGGL(scan_kernel<false>, dim3(grid), dim3(kScanBlock), 0, st, R);
         DMX_DBG_SYNC("scan_kernel");
     }
-    hipEventRecord(c->ev[round * 3 + 1], st);
+    hipEventRecord(c->ev[ev_of(kEvScan, round)], st);
     if (band) {
         set_kid(R.pk.bd, kKerBand0);
         // (list 0 in two launches, costs 0..2 then 3, measured slower: round 2's band 2.15 ->
@@ -4834,17 +4813,16 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
         }
         DMX_DBG_SYNC("band_cand_kernel<4, 5|7>");
         // (no selection pass: the winning key carries its origin, make_key_o)
-        hipEventRecord(c->ev[round * 3 + 2], st);
+        hipEventRecord(c->ev[ev_of(kEvResolve, round)], st);
         return hipGetLastError() == hipSuccess ? DMX_OK : DMX_E_HIP;
     }
     const size_t tabs = (size_t)144 * hp.n;
-    static bool attr_set = false;
-    if (!attr_set) {   // dynamic LDS above 64 KiB must be allowed explicitly
+    if (!c->resolve_attr_set) {   // dynamic LDS above 64 KiB must be allowed explicitly
         hipFuncSetAttribute((const void*)resolve_kernel<kRingSmall>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         hipFuncSetAttribute((const void*)resolve_kernel<kRingLarge>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
+        c->resolve_attr_set = true;
     }
     set_kid(R.pk.bd, kKerResolve);
     if (c->ring_small[round])
@@ -4857,7 +4835,7 @@ int launch_round(Ctx* c, int round, hipStream_t st) {
     set_kid(R.pk.bd, kKerSelect);
     hipLaunchKernelGGL(select_kernel, dim3(1024), dim3(256), 0, st, R);
     DMX_DBG_SYNC("select_kernel");
-    hipEventRecord(c->ev[round * 3 + 2], st);
+    hipEventRecord(c->ev[ev_of(kEvResolve, round)], st);
     return hipGetLastError() == hipSuccess ? DMX_OK : DMX_E_HIP;
 }
 
@@ -4889,25 +4867,25 @@ int launch_mask_scatter(uint32_t* mask, const uint32_t* d_exc, uint32_t n, uint3
 
 int launch_finalize(Ctx* c, int round, hipStream_t st) {
     FinalArgs F;
-    F.lens = c->d_lens;
+    F.lens = c->in.lens.p;
     F.p0 = final_panel(c, 0);
     F.p1 = final_panel(c, 1);
-    F.winner = c->d_winner[round];
-    F.origin = c->d_origin[round];
+    F.winner = c->d_winner[round].p;
+    F.origin = c->d_origin[round].p;
     F.okey = band_round(c, round) ? 1 : 0;
-    F.res = c->d_res;
-    F.items = c->d_items;
-    F.n_items = c->d_counters + 2;
+    F.res = c->in.res.p;
+    F.items = c->d_items.p;
+    F.n_items = c->d_counters.p + kCntItems;
     F.n_reads = (uint32_t)c->n_reads;
     F.mode = c->mode;
     F.A0 = c->panel[0].n_all;
     F.A1 = c->mode == DMX_MODE_SINGLE ? 0 : c->panel[1].n_all;
     F.oslot = c->orient_slot[round] ? 1 : 0;
-    F.counts = c->d_counts;
-    F.winner0 = c->d_winner[0];
-    F.origin0 = c->d_origin[0];
+    F.counts = c->d_counts.p;
+    F.winner0 = c->d_winner[0].p;
+    F.origin0 = c->d_origin[0].p;
     F.okey0 = band_round(c, 0) ? 1 : 0;
-    F.linked_best = c->d_linked;
+    F.linked_best = c->d_linked.p;
     F.bd = make_bounds(c, kKerFin0);
     if (c->mode == DMX_MODE_LINKED) {
         const uint32_t gr = (uint32_t)((c->n_reads + 255) / 256);
@@ -4924,11 +4902,11 @@ int launch_finalize(Ctx* c, int round, hipStream_t st) {
                                    dim3(256), 0, st, F);
         }
         DMX_DBG_SYNC("finalize_linked");
-        hipEventRecord(c->ev[6 + round], st);
+        hipEventRecord(c->ev[ev_of(kEvFinal, round)], st);
         return hipGetLastError() == hipSuccess ? DMX_OK : DMX_E_HIP;
     }
-    F.views = c->d_views;
-    F.item_src = c->d_item_src;
+    F.views = c->d_views.p;
+    F.item_src = c->d_item_src.p;
     if (c->views_on) F.n_reads = (uint32_t)c->n_views;   // round 0's items: one result each
     if (round == 0) {
         const uint32_t grid = (uint32_t)std::min<size_t>((F.n_reads + 255) / 256, kFinalGrid);
@@ -4946,7 +4924,7 @@ int launch_finalize(Ctx* c, int round, hipStream_t st) {
             hipLaunchKernelGGL(finalize1_kernel<false>, dim3(grid), dim3(256), shm, st, F);
     }
     DMX_DBG_SYNC("finalize");
-    hipEventRecord(c->ev[6 + round], st);
+    hipEventRecord(c->ev[ev_of(kEvFinal, round)], st);
     return hipGetLastError() == hipSuccess ? DMX_OK : DMX_E_HIP;
 }
 

@@ -296,7 +296,7 @@ int dmx_set_operands(dmx_ctx* c, const uint32_t* read, const int32_t* start, con
         c->err = "dmx_set_operands: null table";
         return DMX_E_INVALID;
     }
-    if (!c->d_seq || !c->d_lens || c->chunked || c->h_lens.size() != c->n_reads) {
+    if (!c->d_seq || !c->in.lens.p || c->chunked || c->h_lens.size() != c->n_reads) {
         c->err = "dmx_set_operands: no resident batch (dmx_load first)";
         return DMX_E_STATE;
     }
@@ -315,7 +315,7 @@ int dmx_set_operands(dmx_ctx* c, const uint32_t* read, const int32_t* start, con
                              c->stream));
         hipLaunchKernelGGL(operands_locate_kernel, dim3((uint32_t)((n + kOpBlock - 1) / kOpBlock)),
                            dim3(kOpBlock), 0, c->stream, (const OperandRec*)c->d_op.p, (uint32_t)n,
-                           (const uint64_t*)c->d_offs, (uint32_t)c->n_reads, c->d_op_off.p,
+                           (const uint64_t*)c->in.offs.p, (uint32_t)c->n_reads, c->d_op_off.p,
                            c->d_op_len.p, c->d_op_strand.p);
         OP_CK(hipGetLastError());
     }
@@ -371,7 +371,7 @@ int dmx_result_operands(dmx_ctx* c, const uint8_t* keep, size_t n_keep, int32_t 
         c->err = "dmx_result_operands: linked mode has no operand table";
         return DMX_E_UNSUPPORTED;
     }
-    if (!c->executed || c->chunked || !c->d_res || c->h_lens.size() != c->n_reads ||
+    if (!c->executed || c->chunked || !c->in.res.p || c->h_lens.size() != c->n_reads ||
         (c->exec_views && c->exec_view_gen != c->view_gen)) {
         c->err = "dmx_result_operands: no dmx_exec on the current batch and view list";
         return DMX_E_STATE;
@@ -422,10 +422,10 @@ int dmx_result_operands(dmx_ctx* c, const uint8_t* keep, size_t n_keep, int32_t 
     }
     OpBuildArgs A;
     A.bd = make_bounds(c, kKerOperands);
-    A.res = c->d_res;
-    A.views = c->exec_views ? c->d_views : nullptr;
-    A.lens = c->d_lens;
-    A.offs = c->d_offs;
+    A.res = c->in.res.p;
+    A.views = c->exec_views ? c->d_views.p : nullptr;
+    A.lens = c->in.lens.p;
+    A.offs = c->in.offs.p;
     A.p0 = final_panel(c, 0);
     A.p1 = final_panel(c, 1);
     A.keep = keep ? d_keep.p : nullptr;

@@ -1067,7 +1067,7 @@ int pd_fetch_lens(Ctx* c, const char* who, size_t n_pairs, std::vector<uint32_t>
     lens.resize(c->d_seq ? c->n_reads : 0);
     if (!lens.empty() && n_pairs) {
         PD_CK(who, hipSetDevice(c->device));
-        PD_CK(who, hipMemcpy(lens.data(), c->d_lens, lens.size() * 4, hipMemcpyDeviceToHost));
+        PD_CK(who, hipMemcpy(lens.data(), c->in.lens.p, lens.size() * 4, hipMemcpyDeviceToHost));
     }
     return DMX_OK;
 }
@@ -1085,8 +1085,8 @@ int pd_fetch_strands(Ctx* c, const char* who, std::vector<uint8_t>& strands) {
 }
 
 // Where the forms find their reads: the batch's offsets and lengths, or the operand table's.
-inline const uint64_t* pd_offs(const Ctx* c) { return c->ops_on ? c->d_op_off.p : c->d_offs; }
-inline const uint32_t* pd_lens(const Ctx* c) { return c->ops_on ? c->d_op_len.p : c->d_lens; }
+inline const uint64_t* pd_offs(const Ctx* c) { return c->ops_on ? c->d_op_off.p : c->in.offs.p; }
+inline const uint32_t* pd_lens(const Ctx* c) { return c->ops_on ? c->d_op_len.p : c->in.lens.p; }
 // make_bounds for a kernel that indexes them (DMX_DEBUG_BOUNDS builds).
 inline Bounds pd_bounds(const Ctx* c, int kid) {
     Bounds b = make_bounds(c, kid);
