@@ -40,8 +40,11 @@
 // dmx_groupalign_strands), rowdist_kernel and rowpair_kernel are its instantiations, told apart at
 // compile time by their argument struct), one traceback (pa_traceback) and one host path: the chunk planner (pd_plan: chunk
 // limits, sort, wave packing, pair records), the staging of a launch (pd_stage: buffers, upload,
-// the arguments every kernel takes) and the buffers themselves (PdBufs).  A change to the block
-// step, the stripes or the planner is made once.
+// the arguments every kernel takes; pa_stage_trace: the trace form's), the end of a launch group
+// (pd_mark, pd_finish: error, events, wait, bounds check, times), the buffers themselves (PdBufs)
+// and, for the forms whose rows come with the call, the rows on the device (PdRows,
+// dmx_pd_rows.h; pd_rows_validate).  A change to the block step, the stripes, the planner, the
+// launch protocol or the row layout is made once.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +53,7 @@
 #include <type_traits>
 
 #include "dmx_internal.h"
+#include "dmx_pd_rows.h"
 
 namespace dmx {
 
@@ -194,7 +198,7 @@ struct PdBufs {
     DevBuf<PdWave> waves;
     DevBuf<uint32_t> out;
     DevBuf<uint8_t> scratch;
-    hipEvent_t ev[3] = {};       // before the forward pass, after it, after the traceback
+    hipEvent_t ev[4] = {};       // before the forward pass, after it, the traceback, the merge
     ~PdBufs() {
         for (auto& e : ev)
             if (e) hipEventDestroy(e);
@@ -203,49 +207,35 @@ struct PdBufs {
 struct PdState : PdBufs<PdPair> {
     float ms = 0.f;
 };
-struct PaState : PdBufs<PaPair> {
+struct PaTrace {                    // what the trace form's two kernels share (pa_stage_trace)
     DevBuf<ulonglong2> pm;
     DevBuf<uint16_t> sc;
     DevBuf<uint8_t> ops;
+};
+struct PaState : PdBufs<PaPair>, PaTrace {
     float ms[2] = {0.f, 0.f};    // forward pass, traceback
     int launches = 0;            // chunks of the last call
 };
-struct GaState : PdBufs<GaPair> {
-    DevBuf<ulonglong2> pm;
-    DevBuf<uint16_t> sc;
-    DevBuf<uint8_t> ops;
+struct GaState : PdBufs<GaPair>, PaTrace {
     DevBuf<uint8_t> mask;        // both halves of every group's row
     DevBuf<uint16_t> count, first;
-    hipEvent_t ev_merge = nullptr;   // after the merge (ev[0..2] as in the trace form)
     float ms[3] = {0.f, 0.f, 0.f};   // forward pass, traceback, merge
     int launches = 0, rounds = 0;
-    ~GaState() {
-        if (ev_merge) hipEventDestroy(ev_merge);
-    }
 };
 
-// A row of dmx_rowpairdist on the device: where it starts in the mask array and its length.
-struct RrRow {
-    uint64_t off;
-    uint32_t n, pad;
-};
 struct RdState : PdBufs<RdPair> {
-    DevBuf<uint8_t> mask;        // the rows of the last call (then their reverse complements, when
-                                 // a query is an operand on strand 1)
-    DevBuf<RrRow> rows;          // the uploaded rows (rowpair_rc_kernel)
+    PdRows rows;                 // the call's rows (their copies: a query on strand 1)
     float ms = 0.f;
 };
 
 struct RrState : PdBufs<RrPair> {   // DESIGN.md §8j; PdBufs::out holds the whole list's distances
-    DevBuf<uint8_t> mask;        // the rows of the last call, then their reverse complements
-    DevBuf<RrRow> rows;          // the uploaded rows (rowpair_rc_kernel)
+    PdRows rows;                 // the call's rows (their copies: a flagged pair)
     DevBuf<uint32_t> outc;       // dmx_rowhits: per pair d | DMX_LG_REV, or DMX_LG_NONE
     DevBuf<int32_t> cap;         // dmx_rowhits: the caller's caps
     float ms = 0.f;
 };
 struct RaState : PdBufs<RaPair> {   // DESIGN.md §8l; PdBufs::out holds one launch's distances
-    DevBuf<uint8_t> mask;        // the rows of the last call, then their reverse complements
-    DevBuf<RrRow> rows;          // the uploaded rows (rowpair_rc_kernel)
+    PdRows rows;                 // the call's rows (their copies: a retry, a read on strand 1)
     DevBuf<int32_t> cap_hit, cap_half;   // the caller's tables, by the longer length
     DevBuf<uint32_t> bin_off;
     DevBuf<uint16_t> bins;
@@ -257,19 +247,13 @@ struct RaState : PdBufs<RaPair> {   // DESIGN.md §8l; PdBufs::out holds one lau
     float ms = 0.f;
 };
 
+template <class State>
+static void pd_drop(State*& s) {
+    delete s;
+    s = nullptr;
+}
 void pd_release(Ctx* c) {
-    delete c->pd;
-    delete c->pa;
-    delete c->ga;
-    delete c->rd;
-    delete c->rr;
-    delete c->ra;
-    c->ra = nullptr;
-    c->pd = nullptr;
-    c->pa = nullptr;
-    c->ga = nullptr;
-    c->rd = nullptr;
-    c->rr = nullptr;
+    pd_drop(c->pd), pd_drop(c->pa), pd_drop(c->ga), pd_drop(c->rd), pd_drop(c->rr), pd_drop(c->ra);
 }
 
 // The five match masks (A, C, G, T, N) of query rows 64 wi .. 64 wi + 63, built in registers
@@ -909,6 +893,10 @@ size_t pd_env(const char* name, size_t dflt, size_t most) {
     const size_t v = e ? (size_t)std::strtoull(e, nullptr, 10) : 0;
     return std::min(v ? v : dflt, most);
 }
+// Pairs per launch: the place in the chunk has 24 bits of the sort key.
+size_t pd_chunk() { return pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24); }
+// Bytes of trace per launch.
+size_t pa_trace_budget() { return pd_env("DMX_PA_TRACE_MB", kPaTraceMbDefault, (size_t)1 << 20) << 20; }
 
 int pd_group_size(uint32_t m) {
     const uint32_t mw = std::min<uint32_t>((m + 63u) / 64u, 64u);
@@ -942,6 +930,29 @@ int pd_validate(const char* who, int mode, const uint32_t* lens, size_t n_reads,
                    std::to_string(DMX_PD_MAX_LEN) + " nt supported";
             return DMX_E_UNSUPPORTED;
         }
+    }
+    return DMX_OK;
+}
+
+// The rows a call gives (dmx_rowdist, dmx_rowpairdist / dmx_rowhits, dmx_rowassign): offsets and
+// mask bits checked; rowlen[g] becomes the length of row g, clamped at DMX_PD_MAX_LEN + 1 (a
+// length above the limit is refused by the caller, for the pairs that name the row).  `name`
+// opens the message.
+int pd_rows_validate(const std::string& name, size_t n_rows, const uint8_t* masks,
+                     const uint64_t* row_off, std::vector<uint32_t>& rowlen, std::string* err) {
+    rowlen.assign(n_rows, 0);
+    for (size_t g = 0; g < n_rows; ++g) {
+        if (row_off[g + 1] < row_off[g]) {
+            *err = name + "row " + std::to_string(g) + ": offsets must not decrease";
+            return DMX_E_INVALID;
+        }
+        for (uint64_t x = row_off[g]; x < row_off[g + 1]; ++x)
+            if (masks[x] & 0xE0u) {
+                *err = name + "row " + std::to_string(g) + ": column " +
+                       std::to_string(x - row_off[g]) + " has a mask bit above the five symbols";
+                return DMX_E_INVALID;
+            }
+        rowlen[g] = (uint32_t)std::min<uint64_t>(row_off[g + 1] - row_off[g], DMX_PD_MAX_LEN + 1u);
     }
     return DMX_OK;
 }
@@ -1214,7 +1225,104 @@ void pd_launch_forward(void (*kernel)(Args), const Args& A, hipStream_t st) {
     hipLaunchKernelGGL(kernel, dim3(nb), dim3(64 * kPdWavesPerBlock), 0, st, A);
 }
 
+// After a launch: its error, if it made one, and the event that ends it.
+int pd_mark(Ctx* c, const char* who, hipEvent_t ev) {
+    PD_CK(who, hipGetLastError());
+    PD_CK(who, hipEventRecord(ev, c->stream));
+    return DMX_OK;
+}
+
+// The end of a launch group, after its launches and downloads are on the stream: waits for them
+// (synced: the caller already has), checks the bounds record (DMX_DEBUG_BOUNDS builds) and adds
+// the time between ev[k] and ev[k + 1] to ms[k] for the n events of the group.
+int pd_finish(Ctx* c, const char* who, const hipEvent_t* ev, int n, float* ms, bool synced = false) {
+    hipStream_t st = c->stream;
+    if (!synced) PD_CK(who, hipStreamSynchronize(st));
+    if (const int brc = bounds_check(c, who)) return brc;
+    for (int k = 0; k + 1 < n; ++k) {
+        float t = 0.f;
+        hipEventElapsedTime(&t, ev[k], ev[k + 1]);
+        ms[k] += t;
+    }
+    return DMX_OK;
+}
+
+// The trace form's share of a staged launch (PaArgs, GaArgs): room for `trace` word-steps and
+// `ops` path bytes, and the fields both of its kernels read.
+template <class Args>
+int pa_stage_trace(Ctx* c, const char* who, PaTrace& b, size_t trace, size_t ops, uint32_t* out,
+                   Args& A) {
+    PD_CK(who, b.pm.reserve(trace));
+    PD_CK(who, b.sc.reserve(trace));
+    PD_CK(who, b.ops.reserve(ops));
+    A.pm = b.pm.p;
+    A.sc = b.sc.p;
+    A.trace_steps = std::min(b.pm.cap, b.sc.cap);
+    A.ops = b.ops.p;
+    A.ops_bytes = b.ops.cap;
+    A.out = out;
+    return DMX_OK;
+}
+template <class Args>
+void pa_launch_traceback(void (*kernel)(Args), Args& A, int kid, hipStream_t st) {
+    set_kid(A.pk.bd, kid);
+    hipLaunchKernelGGL(kernel, dim3((A.n_pairs + kPaTbLanes - 1u) / kPaTbLanes), dim3(kPaTbLanes), 0,
+                       st, A);
+}
+// A path of `len` ops between m rows and n columns: what the traceback can have written.
+inline bool pa_path_ok(uint32_t len, uint32_t m, uint32_t n) {
+    return len <= m + n && len >= std::max(m, n);
+}
+
+// The pairs a launch's retry bitmap names, appended to `retry` as places in the list the chunk
+// [lo, hi) was cut from.  Bit b is the pair at place b of the chunk, or (sorted) the pair the
+// plan ran as its b-th.
+template <class Pair>
+void pd_retry_list(const std::vector<uint32_t>& need, const PdPlan<Pair>& pl, size_t lo, size_t hi,
+                   bool sorted, std::vector<uint32_t>& retry) {
+    for (size_t w = 0; w < need.size(); ++w)
+        for (uint32_t bits = need[w]; bits; bits &= bits - 1u) {
+            const size_t b = 32 * w + (size_t)__builtin_ctz(bits);
+            if (b < hi - lo) retry.push_back((uint32_t)(lo + (sorted ? pl.place(b) : b)));
+        }
+}
+// v[at[k]] for every k: a column of the second pass's list.
+template <class T>
+std::vector<uint32_t> pd_pick(const T* v, const std::vector<uint32_t>& at) {
+    std::vector<uint32_t> out(at.size());
+    for (size_t k = 0; k < at.size(); ++k) out[k] = (uint32_t)v[at[k]];
+    return out;
+}
+
 }  // namespace
+
+int dmx::PdRows::upload(Ctx* c, const char* who) {
+    PD_CK(who, mask.reserve(2 * total));
+    PD_CK(who, hipMemcpyAsync(mask.p, image.data(), total, hipMemcpyHostToDevice, c->stream));
+    return DMX_OK;
+}
+
+int dmx::PdRows::write_rc(Ctx* c, const char* who, const hipEvent_t* ev, float* ms) {
+    if (written) return DMX_OK;
+    hipStream_t st = c->stream;
+    PD_CK(who, rows.reserve(used.size()));
+    PD_CK(who, hipMemcpyAsync(rows.p, used.data(), used.size() * sizeof(RrRow),
+                              hipMemcpyHostToDevice, st));
+    PD_CK(who, bounds_reset(c, st));
+    RrRcArgs R;
+    R.bd = make_bounds(c, kKerRowpairRc);
+    R.rows = rows.p;
+    R.n_rows = (uint32_t)used.size();
+    R.mask = mask.p;
+    R.half = total;
+    R.cols = 2 * total;
+    PD_CK(who, hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(rowpair_rc_kernel, dim3(R.n_rows), dim3(kRrRcBlock), 0, st, R);
+    if (const int rc = pd_mark(c, who, ev[1])) return rc;
+    if (const int rc = pd_finish(c, who, ev, 2, ms)) return rc;   // `used` is pageable
+    written = true;
+    return DMX_OK;
+}
 
 extern "C" int dmx_pairdist_group_sizes(int* out, int cap) {
     for (int k = 0; k < kPdNSizes && k < cap && out; ++k) out[k] = kPdSizes[k];
@@ -1264,6 +1372,7 @@ extern "C" int dmx_pairdist(dmx_ctx* c, int mode, const uint32_t* q, const uint3
                                    &c->err))
         return rc;
     if (!n_pairs) return DMX_OK;
+    PD_CK(who, hipSetDevice(c->device));
     // operands: the pair's flag with both strands folded in; the query is never turned
     std::vector<uint8_t> strands, eff;
     if (const int rc = pd_fetch_strands(c, who, strands)) return rc;
@@ -1276,8 +1385,7 @@ extern "C" int dmx_pairdist(dmx_ctx* c, int mode, const uint32_t* q, const uint3
     if (const int rc = pd_state(c, who, c->pd)) return rc;
     PdState* s = c->pd;
     hipStream_t st = c->stream;
-    // the place in the chunk has 24 bits of the sort key
-    const size_t chunk = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+    const size_t chunk = pd_chunk();
 
     PdPlan<PdPair> pl;
     std::vector<uint32_t> res;
@@ -1292,15 +1400,10 @@ extern "C" int dmx_pairdist(dmx_ctx* c, int mode, const uint32_t* q, const uint3
         A.out = s->out.p;
         PD_CK(who, hipEventRecord(s->ev[0], st));
         pd_launch_forward(pairdist_kernel, A, st);
-        PD_CK(who, hipGetLastError());
-        PD_CK(who, hipEventRecord(s->ev[1], st));
+        if (const int rc = pd_mark(c, who, s->ev[1])) return rc;
         res.resize(np);
         PD_CK(who, hipMemcpyAsync(res.data(), A.out, np * 4, hipMemcpyDeviceToHost, st));
-        PD_CK(who, hipStreamSynchronize(st));
-        if (const int brc = bounds_check(c, who)) return brc;
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-        total_ms += ms;
+        if (const int rc = pd_finish(c, who, s->ev, 2, &total_ms)) return rc;
         for (size_t k = 0; k < np; ++k) out[lo + pl.place(k)] = res[k];
         lo = hi;
     }
@@ -1359,7 +1462,7 @@ extern "C" int dmx_pairhits(dmx_ctx* c, const uint32_t* q, const uint32_t* t,
         if (const int rc = pd_state(c, who, c->pd)) return rc;
         PdState* s = c->pd;   // dmx_pairdist's buffers; its ms stays its own
         hipStream_t st = c->stream;
-        const size_t chunk = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+        const size_t chunk = pd_chunk();
         PdPlan<PdPair> pl;
         std::vector<uint32_t> orig, need, retry;
         // one launch of pairs[lo .. ) of a list; in[k]: the input pair of the list's pair k
@@ -1374,39 +1477,28 @@ extern "C" int dmx_pairhits(dmx_ctx* c, const uint32_t* q, const uint32_t* t,
             A.out = s->out.p;
             PD_CK(who, hipEventRecord(s->ev[0], st));
             pd_launch_forward(pairdist_kernel, A, st);
-            PD_CK(who, hipGetLastError());
-            PD_CK(who, hipEventRecord(s->ev[1], st));
+            if (const int rc = pd_mark(c, who, s->ev[1])) return rc;
             orig.resize(np);
             for (size_t k = 0; k < np; ++k)
                 orig[k] = in ? in[lo + pl.place(k)] : (uint32_t)(lo + pl.place(k));
             if (const int rc = lg_hits_decide(c, who, A.out, orig.data(), np, pass, lo, &need))
-                return rc;
-            if (const int brc = bounds_check(c, who)) return brc;
-            float ms = 0.f;
-            hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-            total_ms += ms;
+                return rc;   // has synchronised
             *end = hi;
-            return DMX_OK;
+            return pd_finish(c, who, s->ev, 2, &total_ms, /*synced=*/true);
         };
         for (size_t lo = 0, hi = 0; lo < n_pairs; lo = hi) {
             if (const int rc = launch(q, t, fwd.empty() ? nullptr : fwd.data(), fcap.data(), n_pairs,
                                       lo, nullptr, 0, &hi))
                 return rc;
-            for (size_t w = 0; w < need.size(); ++w)
-                for (uint32_t bits = need[w]; bits; bits &= bits - 1u) {
-                    const size_t b = 32 * w + (size_t)__builtin_ctz(bits);
-                    if (b < hi - lo) retry.push_back((uint32_t)(lo + b));
-                }
+            // the decision sets bit i - lo for input pair i: the place in the chunk
+            pd_retry_list(need, pl, lo, hi, /*sorted=*/false, retry);
         }
         const size_t n2 = retry.size();
-        std::vector<uint32_t> q2(n2), t2(n2), cap2(n2);
+        // the second pass's list; a cap is >= 0 where a retry is asked for
+        const std::vector<uint32_t> q2 = pd_pick(q, retry), t2 = pd_pick(t, retry),
+                                    cap2 = pd_pick(cap_hit, retry);
         std::vector<uint8_t> rc2(n2, DMX_PD_RC);
-        for (size_t k = 0; k < n2; ++k) {
-            if (!fwd.empty()) rc2[k] = (uint8_t)(DMX_PD_RC ^ fwd[retry[k]]);
-            q2[k] = q[retry[k]];
-            t2[k] = t[retry[k]];
-            cap2[k] = (uint32_t)cap_hit[retry[k]];   // >= 0 where a retry is asked for
-        }
+        for (size_t k = 0; k < n2 && !fwd.empty(); ++k) rc2[k] = (uint8_t)(DMX_PD_RC ^ fwd[retry[k]]);
         for (size_t lo = 0, hi = 0; lo < n2; lo = hi)
             if (const int rc = launch(q2.data(), t2.data(), rc2.data(), cap2.data(), n2, lo,
                                       retry.data(), 1, &hi))
@@ -1491,15 +1583,16 @@ extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, c
         return rc;
     op_off[0] = 0;
     if (!n_pairs) return DMX_OK;
+    PD_CK(who, hipSetDevice(c->device));
     if (const int rc = pd_state(c, who, c->pa)) return rc;
     PaState* s = c->pa;
     hipStream_t st = c->stream;
-    const size_t budget = pd_env("DMX_PA_TRACE_MB", kPaTraceMbDefault, (size_t)1 << 20) << 20;   // bytes
+    const size_t budget = pa_trace_budget();
 
     PdPlan<PaPair> pl;
     std::vector<uint32_t> res, place;
     std::vector<uint8_t> region;
-    float ms_fwd = 0.f, ms_tb = 0.f;
+    float ms2[2] = {0.f, 0.f};   // forward pass, traceback
     uint64_t at = 0;   // bytes of `ops` filled
     for (size_t lo = 0; lo < n_pairs;) {
         const size_t hi = pd_plan(pl, lens.data(), q, t, flags, nullptr, n_pairs, lo,
@@ -1507,35 +1600,17 @@ extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, c
         const size_t np = hi - lo;
         PaArgs A;
         if (const int rc = pd_stage(c, who, *s, pl, 2 * np, kKerPairalign, A)) return rc;
-        PD_CK(who, s->pm.reserve(pl.trace));
-        PD_CK(who, s->sc.reserve(pl.trace));
-        PD_CK(who, s->ops.reserve(pl.ops));
-        A.pm = s->pm.p;
-        A.sc = s->sc.p;
-        A.trace_steps = std::min(s->pm.cap, s->sc.cap);
-        A.ops = s->ops.p;
-        A.ops_bytes = s->ops.cap;
-        A.out = s->out.p;
+        if (const int rc = pa_stage_trace(c, who, *s, pl.trace, pl.ops, s->out.p, A)) return rc;
         PD_CK(who, hipEventRecord(s->ev[0], st));
         pd_launch_forward(pairalign_kernel, A, st);
-        PD_CK(who, hipGetLastError());
-        PD_CK(who, hipEventRecord(s->ev[1], st));
-        set_kid(A.pk.bd, kKerPairalignTb);
-        hipLaunchKernelGGL(pairalign_traceback_kernel, dim3((A.n_pairs + kPaTbLanes - 1u) / kPaTbLanes),
-                           dim3(kPaTbLanes), 0, st, A);
-        PD_CK(who, hipGetLastError());
-        PD_CK(who, hipEventRecord(s->ev[2], st));
+        if (const int rc = pd_mark(c, who, s->ev[1])) return rc;
+        pa_launch_traceback(pairalign_traceback_kernel, A, kKerPairalignTb, st);
+        if (const int rc = pd_mark(c, who, s->ev[2])) return rc;
         res.resize(2 * np);
         region.resize(pl.ops);
         PD_CK(who, hipMemcpyAsync(res.data(), A.out, 2 * np * 4, hipMemcpyDeviceToHost, st));
         PD_CK(who, hipMemcpyAsync(region.data(), A.ops, pl.ops, hipMemcpyDeviceToHost, st));
-        PD_CK(who, hipStreamSynchronize(st));
-        if (const int brc = bounds_check(c, who)) return brc;
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-        ms_fwd += ms;
-        hipEventElapsedTime(&ms, s->ev[1], s->ev[2]);
-        ms_tb += ms;
+        if (const int rc = pd_finish(c, who, s->ev, 3, ms2)) return rc;
         ++s->launches;
         // the chunk's paths in the caller's pair order: pair lo + x ran at sorted place[x]
         place.resize(np);
@@ -1544,7 +1619,7 @@ extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, c
             const size_t k = place[x];
             const uint32_t m = lens[q[lo + x]], n = lens[t[lo + x]];
             const uint32_t len = res[2 * k + 1];
-            if (len > m + n || len < std::max(m, n)) {
+            if (!pa_path_ok(len, m, n)) {
                 c->err = "dmx_pairalign: pair " + std::to_string(lo + x) + ": path of " +
                          std::to_string(len) + " ops for reads of " + std::to_string(m) + " and " +
                          std::to_string(n) + " nt";
@@ -1558,8 +1633,7 @@ extern "C" int dmx_pairalign(dmx_ctx* c, const uint32_t* q, const uint32_t* t, c
         lo = hi;
     }
     op_off[n_pairs] = at;
-    s->ms[0] = ms_fwd;
-    s->ms[1] = ms_tb;
+    s->ms[0] = ms2[0], s->ms[1] = ms2[1];
     return DMX_OK;
 }
 
@@ -1830,6 +1904,7 @@ static int ga_device(const char* who, dmx_ctx* c, size_t n_groups, const uint8_t
     col_off[0] = 0;
     if (ops) op_off[0] = 0;
     if (!n_groups) return DMX_OK;
+    PD_CK(who, hipSetDevice(c->device));
     // operands: a member's flag with its strand folded in (a launch with a turned member runs
     // the strands form, dmx_groupalign's included)
     std::vector<uint8_t> strands, mflags;
@@ -1845,10 +1920,8 @@ static int ga_device(const char* who, dmx_ctx* c, size_t n_groups, const uint8_t
     }
     if (const int rc = pd_state(c, who, c->ga)) return rc;
     GaState* s = c->ga;
-    if (!s->ev_merge) PD_CK(who, hipEventCreate(&s->ev_merge));
     hipStream_t st = c->stream;
-    PD_CK(who, hipSetDevice(c->device));
-    const size_t budget = pd_env("DMX_PA_TRACE_MB", kPaTraceMbDefault, (size_t)1 << 20) << 20;
+    const size_t budget = pa_trace_budget();
     const uint64_t m0 = member_off[0];
 
     // every group's row has a region of its bound, padded to 16 columns (the forward pass loads
@@ -1903,19 +1976,11 @@ static int ga_device(const char* who, dmx_ctx* c, size_t n_groups, const uint8_t
             }
             GaArgs A;
             if (const int rc = pd_stage(c, who, *s, pl, 2 * np, kKerGroupalign, A)) return rc;
-            PD_CK(who, s->pm.reserve(pl.trace));
-            PD_CK(who, s->sc.reserve(pl.trace));
-            PD_CK(who, s->ops.reserve(pl.ops));
-            A.pm = s->pm.p;
-            A.sc = s->sc.p;
-            A.trace_steps = std::min(s->pm.cap, s->sc.cap);
-            A.ops = s->ops.p;
-            A.ops_bytes = s->ops.cap;
+            if (const int rc = pa_stage_trace(c, who, *s, pl.trace, pl.ops, s->out.p, A)) return rc;
             A.mask = s->mask.p;
             A.count = s->count.p;
             A.first = s->first.p;
             A.cols = std::min(s->mask.cap, std::min(s->count.cap, s->first.cap) / 5);
-            A.out = s->out.p;
             // a pair the kernels skip must not leave a stale length behind
             PD_CK(who, hipMemsetAsync(A.out, 0, 2 * np * 4, st));
             PD_CK(who, hipEventRecord(s->ev[0], st));
@@ -1928,41 +1993,27 @@ static int ga_device(const char* who, dmx_ctx* c, size_t n_groups, const uint8_t
             } else {
                 pd_launch_forward(groupalign_kernel, A, st);
             }
-            PD_CK(who, hipGetLastError());
-            PD_CK(who, hipEventRecord(s->ev[1], st));
-            set_kid(A.pk.bd, kKerGroupalignTb);
-            hipLaunchKernelGGL(groupalign_traceback_kernel,
-                               dim3((A.n_pairs + kPaTbLanes - 1u) / kPaTbLanes), dim3(kPaTbLanes), 0,
-                               st, A);
-            PD_CK(who, hipGetLastError());
-            PD_CK(who, hipEventRecord(s->ev[2], st));
+            if (const int rc = pd_mark(c, who, s->ev[1])) return rc;
+            pa_launch_traceback(groupalign_traceback_kernel, A, kKerGroupalignTb, st);
+            if (const int rc = pd_mark(c, who, s->ev[2])) return rc;
             set_kid(A.pk.bd, kKerGroupalignMerge);
             hipLaunchKernelGGL(groupalign_merge_kernel,
                                dim3((A.n_pairs + kGaMergeWaves - 1u) / kGaMergeWaves),
                                dim3(64 * kGaMergeWaves), 0, st, A);
-            PD_CK(who, hipGetLastError());
-            PD_CK(who, hipEventRecord(s->ev_merge, st));
+            if (const int rc = pd_mark(c, who, s->ev[3])) return rc;
             res.resize(2 * np);
             PD_CK(who, hipMemcpyAsync(res.data(), A.out, 2 * np * 4, hipMemcpyDeviceToHost, st));
             if (ops) {
                 region.resize(pl.ops);
                 PD_CK(who, hipMemcpyAsync(region.data(), A.ops, pl.ops, hipMemcpyDeviceToHost, st));
             }
-            PD_CK(who, hipStreamSynchronize(st));
-            if (const int brc = bounds_check(c, who)) return brc;
-            float ms = 0.f;
-            hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-            ms3[0] += ms;
-            hipEventElapsedTime(&ms, s->ev[1], s->ev[2]);
-            ms3[1] += ms;
-            hipEventElapsedTime(&ms, s->ev[2], s->ev_merge);
-            ms3[2] += ms;
+            if (const int rc = pd_finish(c, who, s->ev, 4, ms3)) return rc;
             ++s->launches;
             for (size_t k = 0; k < np; ++k) {
                 const GaPair& P = pl.pairs[k];
                 const size_t g = P.t;
                 const uint32_t m = lens[P.q], n = P.n, len = res[2 * k + 1];
-                if (len > m + n || len < std::max(m, n)) {
+                if (!pa_path_ok(len, m, n)) {
                     c->err = std::string(who) + ": group " + std::to_string(g) + ", round " +
                              std::to_string(round) + ": path of " + std::to_string(len) +
                              " ops for a read of " + std::to_string(m) + " nt and a row of " +
@@ -2031,24 +2082,14 @@ extern "C" int dmx_groupalign_strands(dmx_ctx* c, size_t n_groups, const uint8_t
 
 namespace {
 
-// Every argument check of both entry points, naming the pair or the row; rn[i] becomes the length
-// of pair i's row.  0, or the code with *err set.
+// Every argument check of both entry points, naming the pair or the row; rowlen[g] becomes the
+// length of row g, rn[i] that of pair i's row.  0, or the code with *err set.
 int rd_validate(const char* who, const uint32_t* lens, size_t n_reads, size_t n_rows,
                 const uint8_t* masks, const uint64_t* row_off, const uint32_t* q, const uint32_t* r,
-                size_t n_pairs, std::vector<uint32_t>& rn, std::string* err) {
+                size_t n_pairs, std::vector<uint32_t>& rowlen, std::vector<uint32_t>& rn,
+                std::string* err) {
     const std::string name = std::string(who) + ": ";
-    for (size_t g = 0; g < n_rows; ++g) {
-        if (row_off[g + 1] < row_off[g]) {
-            *err = name + "row " + std::to_string(g) + ": offsets must not decrease";
-            return DMX_E_INVALID;
-        }
-        for (uint64_t x = row_off[g]; x < row_off[g + 1]; ++x)
-            if (masks[x] & 0xE0u) {
-                *err = name + "row " + std::to_string(g) + ": column " +
-                       std::to_string(x - row_off[g]) + " has a mask bit above the five symbols";
-                return DMX_E_INVALID;
-            }
-    }
+    if (const int rc = pd_rows_validate(name, n_rows, masks, row_off, rowlen, err)) return rc;
     rn.resize(n_pairs);
     for (size_t i = 0; i < n_pairs; ++i) {
         if (q[i] >= n_reads) {
@@ -2096,9 +2137,9 @@ extern "C" int dmx_rowdist_host(const uint32_t* seq2b, const uint32_t* nmask,
         return DMX_E_INVALID;
     }
     std::string err;
-    std::vector<uint32_t> rn;
-    if (const int rc = rd_validate(who, lens, n_reads, n_rows, masks, row_off, q, r, n_pairs, rn,
-                                   &err)) {
+    std::vector<uint32_t> rowlen, rn;
+    if (const int rc = rd_validate(who, lens, n_reads, n_rows, masks, row_off, q, r, n_pairs, rowlen,
+                                   rn, &err)) {
         set_process_error(err);
         return rc;
     }
@@ -2129,59 +2170,32 @@ extern "C" int dmx_rowdist(dmx_ctx* c, size_t n_rows, const uint8_t* masks, cons
         c->err = "dmx_rowdist: null rows, pair list or output";
         return DMX_E_INVALID;
     }
-    std::vector<uint32_t> lens, rn;
+    std::vector<uint32_t> lens, rowlen, rn;
     if (const int rc = pd_fetch_lens(c, who, n_pairs, lens)) return rc;
     if (const int rc = rd_validate(who, lens.data(), lens.size(), n_rows, masks, row_off, q, r,
-                                   n_pairs, rn, &c->err))
+                                   n_pairs, rowlen, rn, &c->err))
         return rc;
+    PD_CK(who, hipSetDevice(c->device));
     if (const int rc = pd_state(c, who, c->rd)) return rc;
     RdState* s = c->rd;
+    PdRows& rows = s->rows;
     hipStream_t st = c->stream;
-    PD_CK(who, hipSetDevice(c->device));
-    const size_t chunk = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+    const size_t chunk = pd_chunk();
 
-    // every row starts at a multiple of 16 columns and is padded to one with zeros (the forward
-    // pass loads 16 mask bytes at a time); rows no pair names are not uploaded
-    std::vector<uint64_t> goff(n_rows, ~(uint64_t)0);
-    uint64_t total = 0;
-    for (size_t i = 0; i < n_pairs; ++i)
-        if (goff[r[i]] == ~(uint64_t)0) {
-            goff[r[i]] = total;
-            total += ((uint64_t)rn[i] + 15u) & ~(uint64_t)15u;
-        }
-    std::vector<uint8_t> rows(total, 0);
-    std::vector<RrRow> used;
-    for (size_t g = 0; g < n_rows; ++g)
-        if (goff[g] != ~(uint64_t)0) {
-            std::memcpy(rows.data() + goff[g], masks + row_off[g], row_off[g + 1] - row_off[g]);
-            used.push_back(RrRow{goff[g], (uint32_t)(row_off[g + 1] - row_off[g]), 0u});
-        }
     // operands: a query on strand 1 against a row is the sub-range as it lies in memory against
-    // the row's reverse complement, written `total` columns behind the rows as dmx_rowassign's are
+    // the row's reverse complement
     std::vector<uint8_t> strands;
     if (const int rc = pd_fetch_strands(c, who, strands)) return rc;
     bool turned = false;
     for (size_t i = 0; i < n_pairs && !strands.empty() && !turned; ++i) turned = strands[q[i]] != 0;
-    PD_CK(who, s->mask.reserve(turned ? 2 * total : total));
-    PD_CK(who, hipMemcpyAsync(s->mask.p, rows.data(), total, hipMemcpyHostToDevice, st));
+    rows.place(masks, row_off, rowlen, r, nullptr, n_pairs);
+    if (const int rc = rows.upload(c, who)) return rc;
+    float rc_ms = 0.f;   // not part of dmx_rowdist_ms
     if (turned) {
-        PD_CK(who, s->rows.reserve(used.size()));
-        PD_CK(who, hipMemcpyAsync(s->rows.p, used.data(), used.size() * sizeof(RrRow),
-                                  hipMemcpyHostToDevice, st));
-        PD_CK(who, bounds_reset(c, st));
-        RrRcArgs R;
-        R.bd = make_bounds(c, kKerRowpairRc);
-        R.rows = s->rows.p;
-        R.n_rows = (uint32_t)used.size();
-        R.mask = s->mask.p;
-        R.half = total;
-        R.cols = 2 * total;
-        hipLaunchKernelGGL(rowpair_rc_kernel, dim3(R.n_rows), dim3(kRrRcBlock), 0, st, R);
-        PD_CK(who, hipGetLastError());
+        if (const int rc = rows.write_rc(c, who, s->ev, &rc_ms)) return rc;
+    } else {
+        PD_CK(who, hipStreamSynchronize(st));   // one wait for the upload either way
     }
-    PD_CK(who, hipStreamSynchronize(st));   // `rows` and `used` are pageable
-    if (turned)
-        if (const int brc = bounds_check(c, who)) return brc;
 
     PdPlan<RdPair> pl;
     std::vector<uint32_t> res;
@@ -2190,23 +2204,18 @@ extern "C" int dmx_rowdist(dmx_ctx* c, size_t n_rows, const uint8_t* masks, cons
         const size_t hi = pd_plan(pl, lens.data(), q, r, nullptr, caps, n_pairs, lo, chunk,
                                   kPdNoBudget, rn.data());
         const size_t np = hi - lo;
-        for (RdPair& P : pl.pairs) P.row = goff[P.t] + (turned && strands[P.q] ? total : 0u);
+        for (RdPair& P : pl.pairs) P.row = rows.off(P.t, turned && strands[P.q]);
         RdArgs A;
         if (const int rc = pd_stage(c, who, *s, pl, np, kKerRowdist, A)) return rc;
-        A.mask = s->mask.p;
-        A.cols = s->mask.cap;
+        A.mask = rows.mask.p;
+        A.cols = rows.cols();
         A.out = s->out.p;
         PD_CK(who, hipEventRecord(s->ev[0], st));
         pd_launch_forward(rowdist_kernel, A, st);
-        PD_CK(who, hipGetLastError());
-        PD_CK(who, hipEventRecord(s->ev[1], st));
+        if (const int rc = pd_mark(c, who, s->ev[1])) return rc;
         res.resize(np);
         PD_CK(who, hipMemcpyAsync(res.data(), A.out, np * 4, hipMemcpyDeviceToHost, st));
-        PD_CK(who, hipStreamSynchronize(st));
-        if (const int brc = bounds_check(c, who)) return brc;
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-        total_ms += ms;
+        if (const int rc = pd_finish(c, who, s->ev, 2, &total_ms)) return rc;
         for (size_t k = 0; k < np; ++k) out[lo + pl.place(k)] = res[k];
         lo = hi;
     }
@@ -2233,21 +2242,7 @@ int rr_validate(const char* who, int mode, size_t n_rows, const uint8_t* masks,
         *err = name + "at most " + std::to_string(DMX_LG_MAX_PAIRS) + " pairs supported";
         return DMX_E_UNSUPPORTED;
     }
-    rowlen.assign(n_rows, 0);
-    for (size_t g = 0; g < n_rows; ++g) {
-        if (row_off[g + 1] < row_off[g]) {
-            *err = name + "row " + std::to_string(g) + ": offsets must not decrease";
-            return DMX_E_INVALID;
-        }
-        for (uint64_t x = row_off[g]; x < row_off[g + 1]; ++x)
-            if (masks[x] & 0xE0u) {
-                *err = name + "row " + std::to_string(g) + ": column " +
-                       std::to_string(x - row_off[g]) + " has a mask bit above the five symbols";
-                return DMX_E_INVALID;
-            }
-        // a length above the limit is refused below, for the pairs that name the row
-        rowlen[g] = (uint32_t)std::min<uint64_t>(row_off[g + 1] - row_off[g], DMX_PD_MAX_LEN + 1u);
-    }
+    if (const int rc = pd_rows_validate(name, n_rows, masks, row_off, rowlen, err)) return rc;
     for (size_t i = 0; i < n_pairs; ++i) {
         if (q[i] >= n_rows || t[i] >= n_rows) {
             *err = name + "pair " + std::to_string(i) + " names a row outside the " +
@@ -2302,52 +2297,24 @@ int rr_run(Ctx* c, const char* who, int mode, size_t n_rows, const uint8_t* mask
     PD_CK(who, hipSetDevice(c->device));
     if (const int rc = pd_state(c, who, c->rr)) return rc;
     RrState* s = c->rr;
+    PdRows& rows = s->rows;
     hipStream_t st = c->stream;
-    const size_t chunk = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+    const size_t chunk = pd_chunk();
 
-    std::vector<uint64_t> goff(n_rows, ~(uint64_t)0);
-    std::vector<RrRow> used;
     std::vector<uint32_t> tn(n_pairs);
-    uint64_t total = 0;
     bool any_rc = false;
     for (size_t i = 0; i < n_pairs; ++i) {
-        for (const uint32_t g : {q[i], t[i]})
-            if (goff[g] == ~(uint64_t)0) {
-                goff[g] = total;
-                used.push_back(RrRow{total, rowlen[g], 0u});
-                total += ((uint64_t)rowlen[g] + 15u) & ~(uint64_t)15u;
-            }
         tn[i] = rowlen[t[i]];
         any_rc = any_rc || (flags && (flags[i] & DMX_PD_RC));
     }
-    std::vector<uint8_t> rows(total, 0);
-    for (size_t g = 0; g < n_rows; ++g)
-        if (goff[g] != ~(uint64_t)0) std::memcpy(rows.data() + goff[g], masks + row_off[g], rowlen[g]);
-    PD_CK(who, s->mask.reserve(2 * total));
+    rows.place(masks, row_off, rowlen, q, t, n_pairs);
     PD_CK(who, s->out.reserve(n_pairs));
-    PD_CK(who, hipMemcpyAsync(s->mask.p, rows.data(), total, hipMemcpyHostToDevice, st));
+    if (const int rc = rows.upload(c, who)) return rc;
     float ms_sum = 0.f;
     if (any_rc) {
-        PD_CK(who, s->rows.reserve(used.size()));
-        PD_CK(who, hipMemcpyAsync(s->rows.p, used.data(), used.size() * sizeof(RrRow),
-                                  hipMemcpyHostToDevice, st));
-        PD_CK(who, bounds_reset(c, st));
-        RrRcArgs R;
-        R.bd = make_bounds(c, kKerRowpairRc);
-        R.rows = s->rows.p;
-        R.n_rows = (uint32_t)used.size();
-        R.mask = s->mask.p;
-        R.half = total;
-        R.cols = 2 * total;
-        PD_CK(who, hipEventRecord(s->ev[0], st));
-        hipLaunchKernelGGL(rowpair_rc_kernel, dim3(R.n_rows), dim3(kRrRcBlock), 0, st, R);
-        PD_CK(who, hipGetLastError());
-        PD_CK(who, hipEventRecord(s->ev[1], st));
-    }
-    PD_CK(who, hipStreamSynchronize(st));   // `rows` and `used` are pageable
-    if (any_rc) {
-        if (const int brc = bounds_check(c, who)) return brc;
-        hipEventElapsedTime(&ms_sum, s->ev[0], s->ev[1]);
+        if (const int rc = rows.write_rc(c, who, s->ev, &ms_sum)) return rc;
+    } else {
+        PD_CK(who, hipStreamSynchronize(st));   // one wait for the upload either way
     }
 
     PdPlan<RrPair> pl;
@@ -2356,8 +2323,8 @@ int rr_run(Ctx* c, const char* who, int mode, size_t n_rows, const uint8_t* mask
                                   kPdNoBudget, tn.data());
         for (size_t k = 0; k < pl.pairs.size(); ++k) {
             RrPair& P = pl.pairs[k];
-            P.row = goff[P.t] + ((P.flags & DMX_PD_RC) ? total : 0u);
-            P.qrow = goff[P.q];
+            P.row = rows.off(P.t, (P.flags & DMX_PD_RC) != 0);
+            P.qrow = rows.off(P.q, false);
             P.m = rowlen[P.q];
             P.dst = (uint32_t)(lo + pl.place(k));
             P.pad = 0;
@@ -2365,20 +2332,16 @@ int rr_run(Ctx* c, const char* who, int mode, size_t n_rows, const uint8_t* mask
         RrArgs A;
         // out_words = the whole list: the buffer is not reallocated between the chunks
         if (const int rc = pd_stage(c, who, *s, pl, n_pairs, kKerRowpair, A)) return rc;
-        A.mask = s->mask.p;
-        A.cols = any_rc ? 2 * total : total;
+        A.mask = rows.mask.p;
+        A.cols = rows.cols();
         A.mode = mode;
         A.out_n = (uint32_t)n_pairs;
         A.out = s->out.p;
         PD_CK(who, hipEventRecord(s->ev[0], st));
         pd_launch_forward(rowpair_kernel, A, st);
-        PD_CK(who, hipGetLastError());
-        PD_CK(who, hipEventRecord(s->ev[1], st));
-        PD_CK(who, hipStreamSynchronize(st));   // the plan's pair records are pageable
-        if (const int brc = bounds_check(c, who)) return brc;
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-        ms_sum += ms;
+        if (const int rc = pd_mark(c, who, s->ev[1])) return rc;
+        // waits: the plan's pair records are pageable
+        if (const int rc = pd_finish(c, who, s->ev, 2, &ms_sum)) return rc;
         lo = hi;
     }
     *ms_total = ms_sum;
@@ -2542,10 +2505,10 @@ extern "C" int dmx_rowhits(dmx_ctx* c, int mode, size_t n_rows, const uint8_t* m
     hipLaunchKernelGGL(rowhits_decide_kernel,
                        dim3((uint32_t)((n_pairs + kRrRcBlock - 1) / kRrRcBlock)), dim3(kRrRcBlock),
                        0, st, D);
-    PD_CK(who, hipGetLastError());
-    PD_CK(who, hipEventRecord(s->ev[1], st));
-    PD_CK(who, hipStreamSynchronize(st));   // `cap` is pageable
-    hipEventElapsedTime(&ms_decide, s->ev[0], s->ev[1]);
+    if (const int rc = pd_mark(c, who, s->ev[1])) return rc;
+    // waits: `cap` is pageable.  The decision takes no bounds record, so the check reads the
+    // record as rr_run's last launch left it: clean, or rr_run had failed.
+    if (const int rc = pd_finish(c, who, s->ev, 2, &ms_decide)) return rc;
     const int rc = lg_compact_outcomes(c, who, s->outc.p, n_pairs, hits_cap, pair, d, rev, n_hits,
                                        &ms_compact);
     if (rc == DMX_OK || rc == DMX_E_INVALID) s->ms = ms + ms_decide + ms_compact;
@@ -2581,20 +2544,7 @@ int ra_prepare(const char* who, const uint32_t* lens, size_t n_reads, size_t n_r
         *err = name + "at most " + std::to_string(kRaRowMax) + " rows supported";
         return DMX_E_UNSUPPORTED;
     }
-    ps.rowlen.assign(n_rows, 0);
-    for (size_t g = 0; g < n_rows; ++g) {
-        if (row_off[g + 1] < row_off[g]) {
-            *err = name + "row " + std::to_string(g) + ": offsets must not decrease";
-            return DMX_E_INVALID;
-        }
-        for (uint64_t x = row_off[g]; x < row_off[g + 1]; ++x)
-            if (masks[x] & 0xE0u) {
-                *err = name + "row " + std::to_string(g) + ": column " +
-                       std::to_string(x - row_off[g]) + " has a mask bit above the five symbols";
-                return DMX_E_INVALID;
-            }
-        ps.rowlen[g] = (uint32_t)std::min<uint64_t>(row_off[g + 1] - row_off[g], DMX_PD_MAX_LEN + 1u);
-    }
+    if (const int rc = pd_rows_validate(name, n_rows, masks, row_off, ps.rowlen, err)) return rc;
     for (size_t k = 0; k < n_sel; ++k)
         if (reads[k] >= n_reads) {
             *err = name + "place " + std::to_string(k) + " names a read outside the batch";
@@ -2789,26 +2739,12 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
     PD_CK(who, hipSetDevice(c->device));
     if (const int rc = pd_state(c, who, c->ra)) return rc;
     RaState* s = c->ra;
+    PdRows& rows = s->rows;
     hipStream_t st = c->stream;
-    const size_t chunk_pairs = pd_env("DMX_PD_CHUNK", kPdChunkDefault, 1u << 24);
+    const size_t chunk_pairs = pd_chunk();
 
-    // the rows some pair names closed up, each padded to 16 columns; room for their reverse
-    // complements behind them, written only when a pair retries
-    std::vector<uint64_t> goff(n_rows, ~(uint64_t)0);
-    std::vector<RrRow> used;
-    uint64_t total = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t g = ps.row[i];
-        if (goff[g] == ~(uint64_t)0) {
-            goff[g] = total;
-            used.push_back(RrRow{total, ps.rowlen[g], 0u});
-            total += ((uint64_t)ps.rowlen[g] + 15u) & ~(uint64_t)15u;
-        }
-    }
-    std::vector<uint8_t> rows(total, 0);
-    for (size_t g = 0; g < n_rows; ++g)
-        if (goff[g] != ~(uint64_t)0) std::memcpy(rows.data() + goff[g], masks + row_off[g], ps.rowlen[g]);
-    PD_CK(who, s->mask.reserve(2 * total));
+    // the reverse complements are written only when a pair retries or a read is on strand 1
+    rows.place(masks, row_off, ps.rowlen, ps.row.data(), nullptr, n);
     PD_CK(who, s->cap_hit.reserve(n_len));
     PD_CK(who, s->cap_half.reserve(n_len));
     PD_CK(who, s->bin_off.reserve(n_len));
@@ -2818,7 +2754,7 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
     PD_CK(who, s->o_row.reserve(n_sel));
     PD_CK(who, s->o_d.reserve(n_sel));
     PD_CK(who, s->o_class.reserve(n_sel));
-    PD_CK(who, hipMemcpyAsync(s->mask.p, rows.data(), total, hipMemcpyHostToDevice, st));
+    if (const int rc = rows.upload(c, who)) return rc;
     PD_CK(who, hipMemcpyAsync(s->cap_hit.p, cap_hit, n_len * 4, hipMemcpyHostToDevice, st));
     PD_CK(who, hipMemcpyAsync(s->cap_half.p, cap_half, n_len * 4, hipMemcpyHostToDevice, st));
     PD_CK(who, hipMemcpyAsync(s->bin_off.p, bin_off, n_len * 4, hipMemcpyHostToDevice, st));
@@ -2832,39 +2768,14 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
     // same against the row), so the copies are written before the first pass
     std::vector<uint8_t> strands;
     if (const int rc = pd_fetch_strands(c, who, strands)) return rc;
-    bool turned = false, rc_written = false;
+    bool turned = false;
     for (size_t i = 0; i < n && !strands.empty() && !turned; ++i) turned = strands[ps.q[i]] != 0;
 
     PdPlan<RaPair> pl;
     std::vector<uint32_t> need;
     float total_ms = 0.f;
-    // the reverse complement of every uploaded row, `total` columns behind the row
-    auto write_rc = [&]() -> int {
-        PD_CK(who, s->rows.reserve(used.size()));
-        PD_CK(who, hipMemcpyAsync(s->rows.p, used.data(), used.size() * sizeof(RrRow),
-                                  hipMemcpyHostToDevice, st));
-        PD_CK(who, bounds_reset(c, st));
-        RrRcArgs R;
-        R.bd = make_bounds(c, kKerRowpairRc);
-        R.rows = s->rows.p;
-        R.n_rows = (uint32_t)used.size();
-        R.mask = s->mask.p;
-        R.half = total;
-        R.cols = 2 * total;
-        PD_CK(who, hipEventRecord(s->ev[0], st));
-        hipLaunchKernelGGL(rowpair_rc_kernel, dim3(R.n_rows), dim3(kRrRcBlock), 0, st, R);
-        PD_CK(who, hipGetLastError());
-        PD_CK(who, hipEventRecord(s->ev[1], st));
-        PD_CK(who, hipStreamSynchronize(st));   // `used` is pageable
-        if (const int brc = bounds_check(c, who)) return brc;
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-        total_ms += ms;
-        rc_written = true;
-        return DMX_OK;
-    };
     if (turned)
-        if (const int rc = write_rc()) return rc;
+        if (const int rc = rows.write_rc(c, who, s->ev, &total_ms)) return rc;
     // one launch of pairs[lo .. ) of a list and its decision; in[i]: the list's pair i among the
     // call's pairs; pass 0 brings the launch's retry bitmap back (bit b: sorted pair b)
     auto launch = [&](const uint32_t* lq, const uint32_t* lr, const uint32_t* lcap,
@@ -2877,13 +2788,13 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
             RaPair& P = pl.pairs[k];
             const size_t i = lo + pl.place(k);
             const bool rev = (pass != 0) != (turned && strands[P.q] != 0);
-            P.row = goff[P.t] + (rev ? total : 0u);
+            P.row = rows.off(P.t, rev);
             P.k = ps.place[in ? in[i] : i];
         }
         RaArgs A;
         if (const int rc = pd_stage(c, who, *s, pl, np, kKerRowassign, A)) return rc;
-        A.mask = s->mask.p;
-        A.cols = rc_written ? 2 * total : total;
+        A.mask = rows.mask.p;
+        A.cols = rows.cols();
         A.out = s->out.p;
         PD_CK(who, s->need.reserve(words));
         if (pass == 0) PD_CK(who, hipMemsetAsync(s->need.p, 0, words * 4, st));
@@ -2902,19 +2813,13 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
         hipLaunchKernelGGL(rowassign_decide_kernel,
                            dim3((uint32_t)((np + kRrRcBlock - 1) / kRrRcBlock)), dim3(kRrRcBlock),
                            0, st, D);
-        PD_CK(who, hipGetLastError());
-        PD_CK(who, hipEventRecord(s->ev[1], st));
+        if (const int rc = pd_mark(c, who, s->ev[1])) return rc;
         if (pass == 0) {
             need.resize(words);
             PD_CK(who, hipMemcpyAsync(need.data(), s->need.p, words * 4, hipMemcpyDeviceToHost, st));
         }
-        PD_CK(who, hipStreamSynchronize(st));   // the plan's pair records are pageable
-        if (const int brc = bounds_check(c, who)) return brc;
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-        total_ms += ms;
         *end = hi;
-        return DMX_OK;
+        return pd_finish(c, who, s->ev, 2, &total_ms);   // waits: the pair records are pageable
     };
 
     std::vector<uint32_t> fcap(n), retry;
@@ -2924,25 +2829,17 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
         if (const int rc = launch(ps.q.data(), ps.row.data(), fcap.data(), ps.tn.data(), n, lo,
                                   nullptr, 0, &hi))
             return rc;
-        for (size_t w = 0; w < need.size(); ++w)
-            for (uint32_t bits = need[w]; bits; bits &= bits - 1u) {
-                const size_t b = 32 * w + (size_t)__builtin_ctz(bits);
-                if (b < hi - lo) retry.push_back((uint32_t)(lo + pl.place(b)));
-            }
+        // the decision sets bit b for the b-th pair the launch ran
+        pd_retry_list(need, pl, lo, hi, /*sorted=*/true, retry);
     }
     const size_t n2 = retry.size();
     if (n2) {
-        if (!rc_written)
-            if (const int rc = write_rc()) return rc;
-        std::sort(retry.begin(), retry.end());
-        std::vector<uint32_t> q2(n2), r2(n2), cap2(n2), tn2(n2);
-        for (size_t k = 0; k < n2; ++k) {
-            const uint32_t i = retry[k];
-            q2[k] = ps.q[i];
-            r2[k] = ps.row[i];
-            tn2[k] = ps.tn[i];
-            cap2[k] = (uint32_t)cap_hit[ps.L[i]];   // >= 0 where a retry is asked for
-        }
+        if (const int rc = rows.write_rc(c, who, s->ev, &total_ms)) return rc;
+        std::sort(retry.begin(), retry.end());   // pair-generation order again
+        // the second pass's list; a cap is >= 0 where a retry is asked for
+        const std::vector<uint32_t> q2 = pd_pick(ps.q.data(), retry), r2 = pd_pick(ps.row.data(), retry),
+                                    tn2 = pd_pick(ps.tn.data(), retry),
+                                    cap2 = pd_pick(cap_hit, pd_pick(ps.L.data(), retry));
         for (size_t lo = 0, hi = 0; lo < n2; lo = hi)
             if (const int rc = launch(q2.data(), r2.data(), cap2.data(), tn2.data(), n2, lo,
                                       retry.data(), 1, &hi))
@@ -2958,18 +2855,14 @@ extern "C" int dmx_rowassign(dmx_ctx* c, size_t n_rows, const uint8_t* masks,
     hipLaunchKernelGGL(rowassign_finish_kernel,
                        dim3((uint32_t)((n_sel + kRrRcBlock - 1) / kRrRcBlock)), dim3(kRrRcBlock), 0,
                        st, F);
-    PD_CK(who, hipGetLastError());
-    PD_CK(who, hipEventRecord(s->ev[1], st));
+    if (const int rc = pd_mark(c, who, s->ev[1])) return rc;
     unsigned long long lines = 0;
     PD_CK(who, hipMemcpyAsync(best_row, s->o_row.p, n_sel * 4, hipMemcpyDeviceToHost, st));
     PD_CK(who, hipMemcpyAsync(best_d, s->o_d.p, n_sel * 4, hipMemcpyDeviceToHost, st));
     PD_CK(who, hipMemcpyAsync(best_class, s->o_class.p, n_sel * 2, hipMemcpyDeviceToHost, st));
     PD_CK(who, hipMemcpyAsync(&lines, s->cnt.p, sizeof lines, hipMemcpyDeviceToHost, st));
-    PD_CK(who, hipStreamSynchronize(st));
-    if (const int brc = bounds_check(c, who)) return brc;
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, s->ev[0], s->ev[1]);
-    s->ms = total_ms + ms;
+    if (const int rc = pd_finish(c, who, s->ev, 2, &total_ms)) return rc;
+    s->ms = total_ms;
     *n_lines = lines;
     return DMX_OK;
 }
