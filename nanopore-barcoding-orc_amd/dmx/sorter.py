@@ -15,8 +15,9 @@ assign_best() is one pass of process_consensuslist / similarity_species / update
 (:1628-1755) as one dmx_rowassign call (pairs, decision and best line per read
 inside the call), rest_reads() the loop around it (:1962-2014), species_consensuses() the second
 half of read_indexes (:1431-1456), and sort_species() runs them per gene group.  NOT replaced:
-that random sampling, finetune (rest_reads has a hook where it runs) and the .group / results
-files.  The
+that random sampling and the .group / results files.  finetune() restates finetune (:838-965)
+with the first reads in order where the reference samples; it runs as rest_reads'
+hook when asked for (dmx-similarity --finetune) and stays with the reference otherwise.  The
 random selection modes (-ra, -a) are out of scope.  Alphabet: A, C, G, T, N (a read with any other byte is refused;
 the reference would compare such bytes literally).
 
@@ -33,6 +34,7 @@ and the callers' random sampling.
 from __future__ import annotations
 
 import argparse
+import functools
 import sys
 
 import numpy as np
@@ -786,6 +788,217 @@ def rest_reads(ctx, reads, indexes, groups, consensuses, similar_species: float 
     return state["groups"], state["cons"]
 
 
+def _ft_select(rl, track, ln, row_len):
+    """The host half of check_consensus (:866-872) on a group's readlist `rl` (entries [read,
+    strand, iden, d1, d2]): every entry's identity against the track's consensus from the
+    distance the lock-step call left in x[3 + track], the in-place stable string sort, then the
+    reads at > 0.94 (the last 20 when those are fewer than 20), of which the last 50 make the
+    consensus.  Returns those entries."""
+    for x in rl:
+        x[2] = identity(int(x[3 + track]), max(int(ln[x[0]]), row_len))
+    rl.sort(key=lambda x: str(x[2]))
+    sel = [x for x in rl if x[2] > 0.94]
+    if len(sel) < 20:
+        sel = rl[-20:]
+    return sel[-50:]
+
+
+def finetune(ctx, reads, groups, consensuses, n_threads: int = 16, max_cycles: int = 10):
+    """finetune (:838-965) for all species groups of a gene group at once, restated literally
+    per group and run in lock-step over the groups.  reads: a list of reads or
+    Operands; groups: index arrays into them; consensuses: one string per group, ignored but
+    where a group comes back unchanged (the reference strips them, :882-883).
+    functools.partial(finetune, ctx, reads) is rest_reads' hook.  Per group:
+      orientation   reads_direction (:854-862): the first read x anchors; read y is turned iff
+                    identity(d(x, y)) < identity(d(x, rc(y))), a tie keeps it.  A turned read
+                    enters every later step turned: as strand 1 of the consensus calls and
+                    against mask_rc of the row in the distance calls; none is turned on the host.
+      S1            where the reference draws random.sample(readlist, 100) (:889-892): the
+                    first min(100, n) entries.  Read 0 of them against the others, stable sort
+                    by identity, the start sequences at int(len // 1.25) and int(len // 5).
+      the loop      (:903-912) check_consensus (:864-875) for track 1, then for track 2 on the
+                    order track 1's sort left, then iden3 of the two new consensuses; until
+                    iden1 and iden2 are both 1, max_cycles cycles at most (the reference's 10).
+      S2            where the reference draws random.sample(seqlist, 150): seqlist[:150] in the
+                    order seqlist has at that point.
+      outcomes      iden3 == 1: the reads at >= 0.95 (of track 2's last check) stay, in the
+                    group's order, with a fresh consensus; fewer than 5: the group is empty.
+                    Otherwise group B, the reads at >= 0.95 in readlist order with their
+                    consensus, or the original group and consensus when fewer than 5; then,
+                    when more than 5 reads are left, check_consensus against consensus1 and
+                    group A of the reads at >= 0.95, appended after all groups.  (That last
+                    check_consensus builds a consensus nothing reads; it is not built here.)
+    distance_finetune (:840-852, HW) is dead code in the reference and has no part here.  A
+    group of fewer than 2 reads is returned unchanged (the reference fails on scorelist[0]).
+    Schedule: one pairdist call for every group's orientation and scorelist; per cycle one
+    rowdist call for both tracks of every group still in its loop, the selections on the host,
+    one consensus call, one rowpairdist call; one rowdist and one consensus call for the
+    outcomes.  ctx: a Context, or None for the host twins.  The batch of an unchanged list
+    stays resident, as in assign_best().  Returns (groups, consensuses); an emptied group is an
+    empty array with consensus ''."""
+    if int(max_cycles) < 1:
+        raise ValueError("finetune: max_cycles must be at least 1")
+    gin = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+    cin = [c.decode("ascii") if isinstance(c, (bytes, bytearray)) else str(c)
+           for c in consensuses]
+    if len(gin) != len(cin):
+        raise ValueError("finetune: one consensus per group")
+    if (ctx is None or isinstance(reads, Operands)
+            or getattr(ctx, "_resident", None) is not reads):
+        seqs, ln, p = _pack_reads(ctx, reads)
+        if ctx is not None and not isinstance(reads, Operands) and p is not None:
+            ctx._resident = reads
+    else:   # the list's batch is loaded: the distances and alignments run on it as it lies
+        seqs, p = _clean(reads), None
+        ln = np.array([len(s) for s in seqs], dtype=np.int64)
+    for k, g in enumerate(gin):
+        if len(g) and (int(g.min()) < 0 or int(g.max()) >= len(seqs)):
+            raise DmxError(f"finetune: group {k} names a read outside the reads")
+    out_g, out_c, added = list(gin), list(cin), []
+    live = [i for i, g in enumerate(gin) if len(g) >= 2]
+    if not live:
+        return out_g, out_c
+
+    def rowdist(rows, q, r):
+        if ctx is not None:
+            return ctx.rowdist(rows, q, r).astype(np.int64)
+        return lib.rowdist_host(p, rows, q, r, n_threads=n_threads).astype(np.int64)
+
+    def track_rows(rows, row, rl):
+        """The row of a track's consensus, and its reverse complement where a read is turned:
+        per entry of rl the read and the index of the row it goes against."""
+        sd = np.array([x[1] for x in rl], dtype=np.int64)
+        base = len(rows)
+        rows.append(row)
+        if sd.any():
+            rows.append(lib.mask_rc(row))
+        return np.array([x[0] for x in rl], dtype=np.int64), base + sd
+
+    # 1. orientation and S1: the first read against every other one, forward and turned
+    q = np.concatenate([np.full(len(gin[i]) - 1, gin[i][0], dtype=np.int64) for i in live])
+    t = np.concatenate([gin[i][1:] for i in live])
+    swap = ln[q] > ln[t]                       # distance(): the shorter one is the query
+    q, t = np.where(swap, t, q), np.where(swap, q, t)
+    fl = np.concatenate([np.zeros(len(q), dtype=np.uint8),
+                         np.full(len(q), lib.PD_RC, dtype=np.uint8)])
+    q2, t2 = np.concatenate([q, q]), np.concatenate([t, t])
+    d = (ctx.pairdist(q2, t2, lib.PD_NW, flags=fl) if ctx is not None
+         else lib.pairdist_host(p, q2, t2, lib.PD_NW, flags=fl, n_threads=n_threads))
+    d = d.astype(np.int64)
+    state, at = {}, 0
+    for i in live:
+        g = gin[i]
+        rl, score = [[int(g[0]), 0, "", 0, 0]], []
+        for k, y in enumerate(g[1:]):
+            L = int(ln[t[at + k]])
+            iden, iden_r = identity(int(d[at + k]), L), identity(int(d[len(q) + at + k]), L)
+            rl.append([int(y), int(iden < iden_r), "", 0, 0])
+            score.append(iden_r if iden < iden_r else iden)
+        at += len(g) - 1
+        m = min(100, len(rl)) - 1              # readlist2[1:100] of the first 100 entries
+        order = sorted(range(m), key=lambda k: score[k])
+        starts = [rl[1 + order[int(m // 1.25)]], rl[1 + order[int(m // 5)]]]
+        rows = [lib.mask_row(seqs[x[0]]) for x in starts]
+        state[i] = {"rl": rl, "row": [lib.mask_rc(r) if x[1] else r
+                                      for r, x in zip(rows, starts)],
+                    "iden3": 0, "cycles": 0}
+
+    # 2. the loop, all groups still in it advancing together
+    active = list(live)
+    while active:
+        rows, qs, rs = [], [], []
+        for i in active:
+            st = state[i]
+            for tr in (0, 1):
+                a, b = track_rows(rows, st["row"][tr], st["rl"])
+                qs.append(a)
+                rs.append(b)
+        d = rowdist(rows, np.concatenate(qs), np.concatenate(rs))
+        at, picks = 0, []
+        for i in active:
+            rl = state[i]["rl"]
+            for tr in (0, 1):                  # the entries as they stood when the call was made
+                for k, x in enumerate(rl):
+                    x[3 + tr] = d[at + k]
+                at += len(rl)
+            for tr in (0, 1):                  # track 2 starts from the order track 1 left
+                picks.append(_ft_select(rl, tr, ln, len(state[i]["row"][tr])))
+        fresh = _consensus(ctx, p, seqs, ln, [[x[0] for x in s] for s in picks],
+                           [[x[1] for x in s] for s in picks], n_threads)
+        rows, pq, pt = [], [], []
+        for k, i in enumerate(active):
+            b = len(rows)
+            rows += [state[i]["row"][0], lib.mask_row(fresh[2 * k]),
+                     state[i]["row"][1], lib.mask_row(fresh[2 * k + 1])]
+            pq += [b + 1, b + 3, b + 1]        # new 1 : old 1, new 2 : old 2, new 1 : new 2
+            pt += [b, b + 2, b + 3]
+        d = (ctx.rowpairdist(rows, pq, pt, lib.PD_NW) if ctx is not None
+             else lib.rowpairdist_host(rows, pq, pt, lib.PD_NW, n_threads=n_threads))
+        still = []
+        for k, i in enumerate(active):
+            st = state[i]
+            iden = [identity(int(d[3 * k + j]), max(len(rows[pq[3 * k + j]]),
+                                                    len(rows[pt[3 * k + j]]))) for j in range(3)]
+            st["row"] = [rows[4 * k + 1], rows[4 * k + 3]]
+            st["iden3"] = iden[2]
+            st["cycles"] += 1
+            if (iden[0] < 1 or iden[1] < 1) and st["cycles"] < int(max_cycles):
+                still.append(i)
+        active = still
+
+    # 3. the outcomes
+    jobs, rest_of = [], {}
+    for i in live:
+        rl = state[i]["rl"]
+        keep = [x for x in rl if x[2] >= 0.95]
+        if state[i]["iden3"] == 1:
+            if len(keep) >= 5:
+                grp = [int(x) for x in gin[i]]
+                for x in rl:
+                    if x[2] < 0.95:
+                        grp.remove(x[0])
+                out_g[i] = np.array(grp, dtype=np.int64)
+                jobs.append((i, False, keep[:150]))
+            else:
+                out_g[i], out_c[i] = np.zeros(0, dtype=np.int64), ""
+            continue
+        rest = rl
+        if len(keep) >= 5:                     # group B; fewer: the original group stays
+            out_g[i] = np.array([x[0] for x in keep], dtype=np.int64)
+            jobs.append((i, False, keep[:150]))
+            rest = [x for x in rl if x[2] < 0.95]
+        if len(rest) > 5:
+            rest_of[i] = rest
+    if rest_of:                                # group A: the rest against consensus1
+        rows, qs, rs = [], [], []
+        for i, rest in rest_of.items():
+            a, b = track_rows(rows, state[i]["row"][0], rest)
+            qs.append(a)
+            rs.append(b)
+        d = rowdist(rows, np.concatenate(qs), np.concatenate(rs))
+        at = 0
+        for i, rest in rest_of.items():
+            for k, x in enumerate(rest):
+                x[3] = d[at + k]
+            at += len(rest)
+            _ft_select(rest, 0, ln, len(state[i]["row"][0]))
+            keep = [x for x in rest if x[2] >= 0.95]
+            if len(keep) >= 5:
+                jobs.append((i, True, keep[:150]))
+                added.append(np.array([x[0] for x in keep], dtype=np.int64))
+    if jobs:
+        fresh = _consensus(ctx, p, seqs, ln, [[x[0] for x in s] for _, _, s in jobs],
+                           [[x[1] for x in s] for _, _, s in jobs], n_threads)
+        extra = []
+        for (i, is_a, _), c in zip(jobs, fresh):
+            if is_a:
+                extra.append(c)
+            else:
+                out_c[i] = c
+        return out_g + added, out_c + extra
+    return out_g, out_c
+
+
 def compare_consensuses(ctx, consensuses, length_diff: float = 8.0, threshold: float = 0.60,
                         n_threads: int = 16) -> list:
     """The pair loop of comp_consensus_groups / compare_consensus (:1276-1296, :1869-1889) with
@@ -1295,9 +1508,10 @@ def main(argv=None) -> int:
                     "(consensuses compared on the GPU, dmx_rowhits), and with "
                     "--species-groups the species groups of every group at the estimated or "
                     "given ssg, and with --assigned the species group every read ends up in "
-                    "(the rest_reads loop, reads assigned on the GPU, dmx_rowassign); the "
-                    "random sampling, finetune and the .group / results files stay with the "
-                    "reference.")
+                    "(the rest_reads loop, reads assigned on the GPU, dmx_rowassign), with "
+                    "--finetune the finetune pass inside that loop (first reads in order "
+                    "where the reference samples at random); the random sampling, the .group / "
+                    "results files and, without --finetune, finetune stay with the reference.")
     ap.add_argument("-i", "--input", required=True, help="bin in FASTQ/FASTA, optionally .gz")
     ap.add_argument("-o", "--output", default=None,
                     help="similarity lines (i:j:iden[:reverse]); optional with --groups")
@@ -1336,7 +1550,15 @@ def main(argv=None) -> int:
                          "line '# ss N sc N ldc N', then '<gene group>.<k>: ' and the read "
                          "indices per final group; FILE.fasta gets a "
                          "'>consensus_<gene group>_<k>(<n reads>)' record per group.  finetune "
-                         "is not run")
+                         "is run only with --finetune")
+    ap.add_argument("--finetune", action="store_true",
+                    help="with --assigned: run finetune (amplicon_sorter.py:838-965) where the "
+                         "reference does, at similarities 0.94 and 0.88 of the rest_reads loop: "
+                         "reads below 0.95 against their group's consensus leave the group, a "
+                         "group of two species is split.  Where the reference samples reads at "
+                         "random, the first in order are taken (the first 100 of a group for the "
+                         "start sequences, the first 150 for a consensus); a group of fewer than "
+                         "2 reads is left as it is.  Without the flag finetune is not run")
     ap.add_argument("-ss", "--similar_species", type=float, default=85.0, metavar="N",
                     help="lowest similarity (%%) at which a read joins a species group "
                          "(default 85.0)")
@@ -1363,6 +1585,8 @@ def main(argv=None) -> int:
         ap.error("--species-groups needs --groups")
     if a.assigned is not None and a.species_groups is None:
         ap.error("--assigned needs --species-groups")
+    if a.finetune and a.assigned is None:
+        ap.error("--finetune needs --assigned")
     if a.consensus_reads < 2:
         ap.error("--consensus-reads must be at least 2")
     try:
@@ -1419,6 +1643,8 @@ def main(argv=None) -> int:
                         done = sort_species(
                             ctx, kept, of, species, a.similar_species, a.similar_consensus,
                             a.length_diff_consensus,
+                            finetune=(functools.partial(finetune, ctx, kept) if a.finetune
+                                      else None),
                             log=lambda m: print(f"dmx-similarity: {m}", file=sys.stderr))
                         write_assigned(a.assigned, done, a.similar_species, a.similar_consensus,
                                        a.length_diff_consensus)
